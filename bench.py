@@ -11,7 +11,12 @@ One "step" = one pass over one batch of G synthetic ZINC-shaped graphs resident 
 Prints ONE JSON line (rank 0).  Multi-GPU: one process per GPU (torch.distributed / RCCL only for the barrier and the
 max-over-ranks timing); graphs are sharded across ranks, the data path has no collective ("weak" scaling: G per GPU fixed).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--graphs G]
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, ...).  `--full` adds what the
+headline does not need: the timed batch against the oracle, per-kernel times and the roofline, HIP-graph replays, the step variants,
+other sizes and configurations, the RCCL all-reduce and the CPU baseline (`--no-extras` / `--no-graph` / `--no-cpu-baseline` trim those).
+`--dump-outputs DIR` writes what the last timed step computed (a fixed seeded sample of its rows, dump_outputs) as DIR/<name>.npy.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--graphs G] [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -688,15 +693,55 @@ def linear_d300(dev):
     return out
 
 
+def headline_line(world, G, N, E, args, dt):
+    """The fields of the result line that a plain run and a --full run share (`dt`: the K timed steps, slowest rank)."""
+    return {
+        "metric": "graphs/sec (orbit-count + GSN-e fwd), ZINC-shape batch; % HBM roofline",
+        "value": round(world * G * args.steps / dt, 1), "unit": "graphs/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "int64 counts + f32 message passing (matrix products: fp16x3 -- two fp16 planes per fp32 operand, three plane products, f32 accumulate)", "data": "synthetic",
+        "config": {"workload": "ZINC-shape x%d graphs/GPU (N=%d, E=%d): integer atom / bond codes in -> cycle_graph k<=6 GSN-e (id_scope=local) "
+                               "orbit count (int64 identifiers written) + one-hot encoding (atoms, bonds and identifiers as exact fp16 operand rows: the layer kernel's "
+                               "input form; no fp32 one-hot tensor is materialised) + GSN_edge_sparse layer-0 forward (general, d_in=28, "
+                               "d_ef=4, d_id=12, d=128, bn, eval) -> layer rows out" % (G, N, E),
+                   "inputs": "int64 atom codes [N], bond codes [E], edge_index [2, E], graph pointers", "outputs": "int64 identifiers [E, 4], fp32 layer rows [N, 128]",
+                   "graphs_per_step_per_gpu": G, "parallelism": "graph-shard x%d, no data-path collective" % world},
+        "full": bool(args.full),
+    }
+
+
+DUMP_ROWS = 65536       # rows per output that --dump-outputs writes (a fixed seeded sample where the output has more)
+
+
+def dump_outputs(out_dir, ids, y):
+    """--dump-outputs: what the last timed step hands its caller -- the int64 identifiers [E, 4] and the layer rows [N, 128] -- as
+    <name>.npy (DUMP_ROWS rows drawn with a fixed seed, in row order; identifiers as float64, exact), <name>_rows.npy (the row numbers
+    drawn) and <name>_colsum.npy (float64 column sums over ALL rows).  About 35 MB at the default batch."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("identifiers", ids), ("layer_rows", y)):
+        n = t.shape[0]
+        rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(n, DUMP_ROWS, replace=False))
+        sample = t[torch.from_numpy(rows).to(t.device)].cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), sample.astype(np.float64 if t.dtype == torch.int64 else np.float32))
+        np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, name + "_colsum.npy"), t.sum(0, dtype=torch.float64).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--graphs", type=int, default=65536, help="graphs per step per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the supplementary measurements (profiling runs: only the headline launches)")
-    ap.add_argument("--no-graph", action="store_true", help="skip the HIP-graph replay of the timed steps (eager launches only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks and supplementary measurements: oracle comparison of the timed batch, per-kernel times and roofline, "
+                         "HIP-graph replays, step variants, other sizes / configurations, RCCL all-reduce, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (identifiers and layer rows: a fixed seeded sample) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the supplementary measurements (profiling runs: only the headline launches)")
+    ap.add_argument("--no-graph", action="store_true", help="with --full: skip the HIP-graph replay of the timed steps (eager launches only)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="process-group backend (nccl = RCCL; gloo only with --dry-run)")
     ap.add_argument("--dry-run", action="store_true",
                     help="plumbing check without a GPU: launch, rendezvous, barrier, max-over-ranks and the JSON line run for real, "
@@ -869,8 +914,10 @@ def main():
     # HIP events inside the timed region bracket the DOMINANT kernel only (the layer: `roofline.avg_launch_ms`); the full per-kernel breakdown
     # (`ms_per_step_by_kernel`) comes from K more steps right behind the timed region, bracketed everywhere (an event pair around every launch
     # keeps consecutive kernels from overlapping their ends: ~1 % of the step).
-    flags.KERNEL_TIMER = {}
-    flags.KERNEL_TIMER_ONLY = {"layer_fused"} if os.environ.get("GSN_BENCH_NO_EVENTS", "0") == "0" else set()      # (diagnostic: no event at all)
+    # (a plain run brackets nothing: the events only feed the per-kernel figures of --full)
+    if args.full:
+        flags.KERNEL_TIMER = {}
+        flags.KERNEL_TIMER_ONLY = {"layer_fused"} if os.environ.get("GSN_BENCH_NO_EVENTS", "0") == "0" else set()      # (diagnostic: no event at all)
     import gc
     _dm = os.environ.get("GSN_BENCH_DIAG_MODE", "")
     if "collect" in _dm:                      # (diagnostic: a collection here frees blocks and changes where the step's buffers land -- 0.754 -> 0.854 ms)
@@ -894,6 +941,30 @@ def main():
     if "drop" in _dm:
         y = step()
         sync()
+    if args.dump_outputs and rank == 0:      # (before any further step: the step's buffers are reused)
+        dump_outputs(args.dump_outputs, ids_out, y)
+    if not args.full:
+        dt_own = dt
+        dt = gdist.max_over_ranks(dt, dev)
+        assert torch.isfinite(y).all()
+        per_rank_ms, graphs_by_rank = [round(dt_own / args.steps * 1e3, 4)], [G]
+        if dist is not None and world > 1:
+            tl = [torch.zeros(1, device=dev, dtype=torch.float64) for _ in range(world)]
+            dist.all_gather(tl, torch.tensor([dt_own], device=dev, dtype=torch.float64))
+            per_rank_ms = [round(float(t.item()) / args.steps * 1e3, 4) for t in tl]
+            gl = [torch.zeros(1, device=dev, dtype=torch.int64) for _ in range(world)]
+            dist.all_gather(gl, torch.tensor([G], device=dev, dtype=torch.int64))
+            graphs_by_rank = [int(t.item()) for t in gl]
+        if rank == 0:
+            res = headline_line(world, G, N, E, args, dt)
+            res["kernels"] = {"ms_per_step_by_rank": per_rank_ms, "graphs_by_rank": graphs_by_rank,
+                              "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 4),
+                              "prewarm_steps_untimed": int(os.environ.get("GSN_BENCH_PREWARM", "60"))}
+            print(json.dumps(res))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     timer_dom, flags.KERNEL_TIMER, flags.KERNEL_TIMER_ONLY = flags.KERNEL_TIMER, {}, None
     for _ in range(args.steps):              # (untimed: the same K steps with every kernel family bracketed)
         step()
@@ -1381,21 +1452,11 @@ def main():
         extra["prewarm_steps_untimed"] = int(os.environ.get("GSN_BENCH_PREWARM", "60"))
         if model4 is not None:
             extra["full_model_step"] = model4
-        res = {
-            "metric": "graphs/sec (orbit-count + GSN-e fwd), ZINC-shape batch; % HBM roofline",
-            "value": round(world * G * args.steps / dt, 1), "unit": "graphs/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "int64 counts + f32 message passing (matrix products: fp16x3 -- two fp16 planes per fp32 operand, three plane products, f32 accumulate)", "data": "synthetic",
-            "config": {"workload": "ZINC-shape x%d graphs/GPU (N=%d, E=%d): integer atom / bond codes in -> cycle_graph k<=6 GSN-e (id_scope=local) "
-                                   "orbit count (int64 identifiers written) + one-hot encoding (atoms, bonds and identifiers as exact fp16 operand rows: the layer kernel's "
-                                   "input form; no fp32 one-hot tensor is materialised) + GSN_edge_sparse layer-0 forward (general, d_in=28, "
-                                   "d_ef=4, d_id=12, d=128, bn, eval) -> layer rows out" % (G, N, E),
-                       "inputs": "int64 atom codes [N], bond codes [E], edge_index [2, E], graph pointers", "outputs": "int64 identifiers [E, 4], fp32 layer rows [N, 128]",
-                       "graphs_per_step_per_gpu": G, "parallelism": "graph-shard x%d, no data-path collective" % world},
+        res = dict(headline_line(world, G, N, E, args, dt), **{
             "roofline": roof, "kernels": extra,
             "counts_checked": bool(checked["counts_bit_exact"]), "checked": checked,
             "tolerance": "counts bit-exact (int64); layer output vs the fp32 oracle: |got-ref| <= 1e-5 |ref| + 1e-5 max|ref row| element-wise",
-        }
+        })
         assert checked["counts_bit_exact"], "timed counts differ from the oracle"
         assert checked["layer_elementwise_1e-5_rel_plus_1e-5_rowmax"], "timed layer output differs from the oracle: %r" % (checked,)
         if not args.no_cpu_baseline and world == 1:

@@ -11,7 +11,7 @@ for f in tests/test_*gpu*.py; do
   case "$r" in *failed*|*error*) rc=1 ;; *passed*|*skipped*) ;; *) rc=1 ;; esac      # (a file whose tests all skip -- the capture tests, without the caching allocator -- is not a failure)
 done
 # the benchmark's launches (headline + supplementary steps; --no-graph: stream capture cannot free memory without the cache) and smoke()
-r=$(timeout 1200 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-graph 2>&1 | grep -v amdgpu.ids | tail -1 | cut -c1-60)
+r=$(timeout 1200 python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-graph 2>&1 | grep -v amdgpu.ids | tail -1 | cut -c1-60)
 echo "bench.py: $r"
 case "$r" in '{"metric"'*) ;; *) rc=1 ;; esac
 r=$(python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1)

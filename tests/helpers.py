@@ -1,5 +1,6 @@
 """Shared helpers for the parity tests: golden-fixture access."""
 import ast
+import glob
 import os
 
 import numpy as np
@@ -8,9 +9,39 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 _CACHE = {}
 
 
+class _Parts:
+    """A fixture committed as <name>.0.npz, <name>.1.npz, ... (make_golden.py::save_parts: every file under 1 MiB), read as one
+    mapping with the part of np.load's interface the tests use: `files`, `z[key]`, `key in z`."""
+
+    def __init__(self, paths):
+        self._where = {}
+        for p in paths:
+            z = np.load(p, allow_pickle=False)
+            for k in z.files:
+                self._where[k] = z
+        self.files = list(self._where)
+
+    def __getitem__(self, key):
+        return self._where[key][key]
+
+    def __contains__(self, key):
+        return key in self._where
+
+
+def load_npz(name):
+    """tests/golden/<name>.npz, or its parts <name>.<i>.npz in part order."""
+    whole = os.path.join(GOLDEN, name + ".npz")
+    if os.path.exists(whole):
+        return np.load(whole, allow_pickle=False)
+    parts = sorted(glob.glob(os.path.join(GOLDEN, name + ".[0-9]*.npz")), key=lambda p: int(p.rsplit(".", 2)[-2]))
+    if not parts:
+        raise FileNotFoundError(whole)
+    return _Parts(parts)
+
+
 def load(name):
     if name not in _CACHE:
-        _CACHE[name] = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+        _CACHE[name] = load_npz(name)
     return _CACHE[name]
 
 

@@ -39,24 +39,22 @@ print("dropin ok")
 '''
 
 
-def test_dropin_imports_resolve_to_gsn_amd():
+def test_dropin_imports_resolve_to_gsn_amd(tmp_path):
     env = dict(os.environ)
     env["PYTHONPATH"] = os.pathsep.join([os.path.join(REPO, "gsn_amd", "dropin"), REPO])
-    out = subprocess.run([sys.executable, "-c", SNIPPET], env=env, cwd="/tmp", capture_output=True, text=True, timeout=300)
+    out = subprocess.run([sys.executable, "-c", SNIPPET], env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr
     assert "dropin ok" in out.stdout
 
 
-def test_reference_callers_bind_to_the_dropins():
-    """scripts/check_reference_binding.py: the reference's unchanged utils.py (process_arguments, get_custom_edge_list) and the
-    subgraph_dicts loop of utils_data_gen.py:35-42 over gsn_amd/dropin -- selected callables are ours, 213 orbit tables equal orbits.npz.
-    Build container only (/root/reference does not exist on the GPU box)."""
-    import pytest
-    if not os.path.isdir("/root/reference"):
-        pytest.skip("needs /root/reference")
+def test_reference_callers_bind_to_the_dropins(tmp_path):
+    """scripts/check_reference_binding.py --recorded: what the reference's unchanged utils.py (process_arguments, get_custom_edge_list)
+    imported and selected over gsn_amd/dropin, as recorded in tests/golden/reference_binding.json (names and pattern edge lists) -- the
+    selected callables are ours, reached through the drop-ins, and the subgraph_dicts loop of utils_data_gen.py:35-42 over them gives
+    215 orbit tables equal to orbits.npz.  (Without --recorded the script runs the reference itself and --record rewrites the file.)"""
     env = dict(os.environ)
     env.pop("PYTHONPATH", None)
-    out = subprocess.run([sys.executable, os.path.join(REPO, "scripts", "check_reference_binding.py")], env=env, cwd="/tmp",
+    out = subprocess.run([sys.executable, os.path.join(REPO, "scripts", "check_reference_binding.py"), "--recorded"], env=env, cwd=str(tmp_path),
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     assert "binding ok" in out.stdout

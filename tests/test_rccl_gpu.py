@@ -61,7 +61,7 @@ def test_training_step_script_under_the_launcher():
 
 def test_bench_under_the_launcher():
     nog = ["--no-graph"] if os.environ.get("PYTORCH_NO_CUDA_MEMORY_CACHING") == "1" else []      # (scripts/oob_check.sh: no captures without the caching allocator)
-    d = _launch(["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--graphs", "4096"] + nog, 29543)
+    d = _launch(["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline", "--graphs", "4096"] + nog, 29543)
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["checked"]["counts_bit_exact"]
     assert d["kernels"]["rccl"]["version"] and d["kernels"]["rccl"]["allreduce_ms"] > 0
     assert len(d["kernels"]["ms_per_step_by_rank"]) == 1 and len(d["kernels"]["graphs_by_rank"]) == 1
