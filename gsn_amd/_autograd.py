@@ -6,7 +6,7 @@ import torch
 
 from . import _abi, flags
 from ._caches import _note_cache
-from ._dense import _Stage, _bn_resolve, _f16x3_takes, _linear_hip
+from ._dense import _Stage, _block_array, _bn_resolve, _f16x3_takes, _linear_hip
 from ._index import _csr_for, propagate
 from ._runtime import _ACT_CODE, _f32c, _timed, _zeros
 
@@ -94,8 +94,8 @@ class _DenseStagesFn(torch.autograd.Function):
                         nsp, n_next = spec[si + 1], tensors[w_pos].shape[0]
                         nbn = nsp["bn"]
                         next_stats = nbn is not None and (nbn.training or nbn.running_mean is None)
-                        to_planes = (flags.WGRAD_F16X3 and ctx.needs_input_grad[1 + w_pos] and _f16x3_takes(m_rows, n_next, [n_out])
-                                     and (not next_stats or (flags.LINEAR_F16X3_STATS and n_next % 4 == 0)))
+                        to_planes = (flags.WGRAD_F16X3 and ctx.needs_input_grad[1 + w_pos]
+                                     and _f16x3_takes(m_rows, n_next, [n_out], aligned=h.data_ptr() % 16 == 0, stats=next_stats))
                     with _abi.device_guard(h.device), _timed("bn_act", 8.0 * h.numel()):
                         if to_planes:
                             presplit_next = torch.empty(int(_abi.lib().gsn_linear_f16x3_scratch_bytes(m_rows, n_out)), dtype=torch.uint8, device=h.device)
@@ -169,7 +169,7 @@ class _DenseStagesFn(torch.autograd.Function):
             need_x = si > 0 or any(ctx.needs_input_grad[1 + bi] for bi in range(len(blocks0)))
             want_w = ctx.needs_input_grad[1 + ent["w_i"]]
             planes_only = (flags.BN_BWD_PLANES and kind in ("bn", "bn_eval") and want_w and ctx.x_scratch[si] is not None and n_out % 4 == 0 and n_out <= 640
-                           and g.data_ptr() % 16 == 0 and (not need_x or _f16x3_takes(m_rows, k_total, [n_out])))
+                           and g.data_ptr() % 16 == 0 and (not need_x or _f16x3_takes(m_rows, k_total, [n_out], aligned=saved[off].data_ptr() % 16 == 0)))
             gh = None if planes_only else torch.empty((m_rows, n_out), dtype=torch.float32, device=dev)
             gh_scratch = None
             with _abi.device_guard(dev), _timed("bn_act_bwd", 16.0 * m_rows * n_out):
@@ -238,8 +238,7 @@ class _DenseStagesFn(torch.autograd.Function):
                 if xs is not None and not g_scr and n_out % 4 == 0 and gh is not None and gh.data_ptr() % 16 == 0 and m_rows >= flags.WGRAD_F16X3_SPLIT_ROWS:
                     # no input-gradient product on the fp16x3 kernel beside it: the planes of gH from the pre-pass alone
                     sc = torch.empty(int(L.gsn_linear_f16x3_scratch_bytes(m_rows, n_out)), dtype=torch.uint8, device=dev)
-                    one = (_abi.gsn_block * 1)()
-                    one[0].data = gh.data_ptr(); one[0].idx = None; one[0].idx32 = None; one[0].width = n_out
+                    one = _block_array([(gh, None)], [])
                     with _abi.device_guard(dev):
                         _abi.check(L.gsn_linear_f16x3_split_rows_hip(m_rows, 1, one, sc.data_ptr(), _abi.current_stream()), "gsn_linear_f16x3_split_rows_hip")
                     g_scr.append(sc)
@@ -249,15 +248,10 @@ class _DenseStagesFn(torch.autograd.Function):
                                    "gsn_wgrad_f16x3_hip")
                 else:
                     xin = xin_rows()
-                    arr = (_abi.gsn_block * len(xin))()
                     keep = []
                     gather = spec[0].get("gather") if si == 0 else None
-                    for bi, t in enumerate(xin):
-                        t = _f32c(t); keep.append(t)
-                        arr[bi].data = t.data_ptr(); arr[bi].idx = None; arr[bi].idx32 = None; arr[bi].width = t.shape[1]
-                        if gather is not None and gather[2][bi] is not None:
-                            ix = gather[0][gather[2][bi]].contiguous(); keep.append(ix)
-                            arr[bi].idx = ix.data_ptr()
+                    modes = [None] * len(xin) if gather is None else gather[2]
+                    arr = _block_array([(t, None if m is None else gather[0][m]) for t, m in zip(xin, modes)], keep)
                     with _abi.device_guard(dev), _timed("wgrad", 2.0 * m_rows * n_out * k_total):
                         _abi.check(L.gsn_wgrad_hip(m_rows, n_out, gh.data_ptr(), len(xin), arr, gw.data_ptr(), _abi.current_stream()),
                                    "gsn_wgrad_hip")
@@ -440,13 +434,8 @@ class _GatherCatFn(torch.autograd.Function):
         # modes[b]: 0 / 1 = rows gathered through edge_index[0] / edge_index[1], None = one row per edge
         E = edge_index.shape[1]
         ts = [_f32c(t) for t in tensors]
-        arr = (_abi.gsn_block * len(ts))()
         keep = []
-        for b, (t, m) in enumerate(zip(ts, modes)):
-            arr[b].data = t.data_ptr(); arr[b].width = t.shape[1]; arr[b].idx32 = None; arr[b].idx = None
-            if m is not None:
-                idx = edge_index[m].contiguous(); keep.append(idx)
-                arr[b].idx = idx.data_ptr()
+        arr = _block_array([(t, None if m is None else edge_index[m]) for t, m in zip(ts, modes)], keep)
         k_total = sum(t.shape[1] for t in ts)
         out = torch.empty((E, k_total), dtype=torch.float32, device=edge_index.device)
         with _abi.device_guard(out.device), _timed("gather_cat", 8.0 * out.numel()):

@@ -43,11 +43,37 @@ def _f16x3_weights(weight, w32):
     return planes, col_inv
 
 
-def _f16x3_takes(m_rows, n_out, widths, aligned=True):
-    """Would _linear_hip run this product of direct rows (block widths ``widths``) on the fp16x3 kernel?  (the rule inside it, for callers that
-    decide what to keep or prepare for that kernel)"""
-    return (flags.LINEAR_F16X3 and m_rows > 0 and n_out > flags.LINEAR_F16X3_MIN_N
-            and ((m_rows + 127) // 128) * ((n_out + 127) // 128) > flags.LINEAR_F16X3_MIN_TILES and aligned and all(w % 4 == 0 for w in widths))
+def _block_array(blocks, keep, widths_only=False):
+    """gsn_block array of a list of (rows, idx or None): fp32 rows, an int32 index in ``idx32``, any other in ``idx``.  What the array points
+    at (and the array) is appended to ``keep``.  ``widths_only``: widths alone, for a supported() query (no row is converted)."""
+    arr = (_abi.gsn_block * max(len(blocks), 1))()
+    for b, (d, idx) in enumerate(blocks):
+        arr[b].width = d.shape[1]
+        if widths_only:
+            arr[b].data = 1
+            continue
+        d = _f32c(d); keep.append(d)
+        arr[b].data = d.data_ptr()
+        arr[b].idx = None; arr[b].idx32 = None
+        if idx is not None:
+            idx = idx.contiguous(); keep.append(idx)
+            if idx.dtype == torch.int32:
+                arr[b].idx32 = idx.data_ptr()
+            else:
+                arr[b].idx = idx.data_ptr()
+    keep.append(arr)
+    return arr
+
+
+def _f16x3_takes(m_rows, n_out, widths, aligned=True, direct=True, out=True, stats=False, bn=False, act=0):
+    """Does _linear_hip run this product on the fp16x3 kernel?  The one statement of the rule, also for callers that decide what to keep or
+    prepare for that kernel.  ``widths``: the block widths; ``aligned``: every block 16-byte aligned; ``direct``: no block gathered through an
+    index; ``stats``: column statistics wanted (a train-mode stage that keeps its pre-BN rows: then no BN vectors, ``bn``, and the identity
+    ``act``).  From two column tiles on the pre-pass over the rows that finds their scales is amortised -- at n_out <= 128 the bf16x6 kernel,
+    which reads the rows once, is faster: 99 vs 90 TF/s at K = 260."""
+    return (flags.LINEAR_F16X3 and out and (not stats or (flags.LINEAR_F16X3_STATS and not bn and act == 0 and n_out % 4 == 0))
+            and m_rows > 0 and n_out > flags.LINEAR_F16X3_MIN_N and ((m_rows + 127) // 128) * ((n_out + 127) // 128) > flags.LINEAR_F16X3_MIN_TILES
+            and direct and aligned and all(w % 4 == 0 for w in widths))
 
 
 def _linear_hip(blocks, weight, bias, bn_mean, bn_scale, bn_shift, act, m_rows, out=True, stats=None, split_k=False, scratch_out=None, presplit=None):
@@ -60,22 +86,8 @@ def _linear_hip(blocks, weight, bias, bn_mean, bn_scale, bn_shift, act, m_rows, 
     if len(blocks) > _MAX_BLOCKS:
         raise NotImplementedError("more than %d input blocks" % _MAX_BLOCKS)
     dev = weight.device
-    arr = (_abi.gsn_block * len(blocks))()
     keep = []
-    for i, (d, idx) in enumerate(blocks):
-        d = _f32c(d)
-        keep.append(d)
-        arr[i].data = d.data_ptr()
-        arr[i].idx = None
-        arr[i].idx32 = None
-        if idx is not None:
-            idx = idx.contiguous()
-            keep.append(idx)
-            if idx.dtype == torch.int32:
-                arr[i].idx32 = idx.data_ptr()
-            else:
-                arr[i].idx = idx.data_ptr()
-        arr[i].width = d.shape[1]
+    arr = _block_array(blocks, keep)
     n_out = weight.shape[0]
     y = torch.empty((m_rows, n_out), dtype=torch.float32, device=dev) if out else None
     if m_rows == 0:
@@ -86,34 +98,24 @@ def _linear_hip(blocks, weight, bias, bn_mean, bn_scale, bn_shift, act, m_rows, 
               and weight.stride(1) >= weight.shape[0] and flags.STRIDED_WEIGHTS)
     w = (weight.detach() if weight.requires_grad else weight) if w_view else _f32c(weight)
     vecs = [None if v is None else _f32c(v) for v in (bias, bn_mean, bn_scale, bn_shift)]
-    # direct rows (node-level stages): the fp16x3 kernel with the weights split once per weight version
-    # (from two column tiles on: the pre-pass over the rows that finds their scales is then amortised -- at n_out <= 128 the
-    #  bf16x6 kernel, which reads the rows once, is faster: 99 vs 90 TF/s at K = 260)
+    # direct rows (node-level stages): the fp16x3 kernel with the weights split once per weight version (_f16x3_takes: when)
     # (a train-mode stage that keeps its pre-BN rows: the same kernel with the column statistics taken in its epilogue)
-    takes16 = (flags.LINEAR_F16X3 and out and (stats is None or (flags.LINEAR_F16X3_STATS and bn_mean is None and act == 0 and n_out % 4 == 0)) and m_rows > 0 and n_out > flags.LINEAR_F16X3_MIN_N
-               and ((m_rows + 127) // 128) * ((n_out + 127) // 128) > flags.LINEAR_F16X3_MIN_TILES
-               and all(idx is None for _, idx in blocks) and all(d.shape[1] % 4 == 0 and d.data_ptr() % 16 == 0 for d in keep))
+    nb = len(blocks)
+    takes16 = _f16x3_takes(m_rows, n_out, [d.shape[1] for d, _ in blocks], aligned=all((arr[i].data or 0) % 16 == 0 for i in range(nb)),
+                           direct=all(idx is None for _, idx in blocks), out=out, stats=stats is not None, bn=bn_mean is not None, act=act)
     if presplit is not None and not takes16:
         raise RuntimeError("presplit rows given to a product that does not run on the fp16x3 kernel (_f16x3_takes decides)")
     if takes16:
         planes, col_inv = _f16x3_weights(weight, w)
         scratch = presplit if presplit is not None else torch.empty(int(_abi.lib().gsn_linear_f16x3_scratch_bytes(m_rows, w.shape[1])), dtype=torch.uint8, device=dev)
+        # four entry points: with / without column statistics (then no BN + activation epilogue), with / without presplit rows
+        name = "gsn_linear_f16x3_fwd%s%s_hip" % ("_stats" if stats is not None else "", "_presplit" if presplit is not None else "")
+        epilogue = () if stats is not None else (_abi.ptr(vecs[1]), _abi.ptr(vecs[2]), _abi.ptr(vecs[3]), act)
+        tail = () if stats is None else (stats.data_ptr(),)
         with _abi.device_guard(dev), _timed("linear_fwd", 2.0 * m_rows * w.shape[1] * n_out):
-            if presplit is not None and stats is not None:
-                rc = _abi.lib().gsn_linear_f16x3_fwd_stats_presplit_hip(m_rows, len(blocks), arr, planes.data_ptr(), col_inv.data_ptr(), _abi.ptr(vecs[0]), n_out,
-                                                                        scratch.data_ptr(), y.data_ptr(), stats.data_ptr(), _abi.current_stream())
-            elif presplit is not None:
-                rc = _abi.lib().gsn_linear_f16x3_fwd_presplit_hip(m_rows, len(blocks), arr, planes.data_ptr(), col_inv.data_ptr(), _abi.ptr(vecs[0]), n_out,
-                                                                  _abi.ptr(vecs[1]), _abi.ptr(vecs[2]), _abi.ptr(vecs[3]), act, scratch.data_ptr(),
-                                                                  y.data_ptr(), _abi.current_stream())
-            elif stats is not None:
-                rc = _abi.lib().gsn_linear_f16x3_fwd_stats_hip(m_rows, len(blocks), arr, planes.data_ptr(), col_inv.data_ptr(), _abi.ptr(vecs[0]), n_out,
-                                                               scratch.data_ptr(), y.data_ptr(), stats.data_ptr(), _abi.current_stream())
-            else:
-                rc = _abi.lib().gsn_linear_f16x3_fwd_hip(m_rows, len(blocks), arr, planes.data_ptr(), col_inv.data_ptr(), _abi.ptr(vecs[0]), n_out,
-                                                         _abi.ptr(vecs[1]), _abi.ptr(vecs[2]), _abi.ptr(vecs[3]), act, scratch.data_ptr(),
-                                                         y.data_ptr(), _abi.current_stream())
-        _abi.check(rc, "gsn_linear_f16x3_fwd_presplit_hip" if presplit is not None else ("gsn_linear_f16x3_fwd_stats_hip" if stats is not None else "gsn_linear_f16x3_fwd_hip"))
+            rc = getattr(_abi.lib(), name)(m_rows, nb, arr, planes.data_ptr(), col_inv.data_ptr(), _abi.ptr(vecs[0]), n_out, *epilogue,
+                                           scratch.data_ptr(), y.data_ptr(), *tail, _abi.current_stream())
+        _abi.check(rc, name)
         if scratch_out is not None:
             scratch_out.append(scratch)
         return y
@@ -122,7 +124,6 @@ def _linear_hip(blocks, weight, bias, bn_mean, bn_scale, bn_shift, act, m_rows, 
     if split_k and out and stats is None and act == 0 and bn_mean is None and bn_scale is None and flags.LINEAR_SPLITK:
         splits = int(_abi.lib().gsn_linear_splitk_plan(m_rows, w.shape[1], n_out))
         if splits > 1:
-            from ._runtime import _zeros
             y = _zeros(m_rows * n_out, torch.float32, dev).view(m_rows, n_out)
             with _abi.device_guard(dev), _timed("linear_fwd", 2.0 * m_rows * w.shape[1] * n_out):
                 rc = _abi.lib().gsn_linear_fwd_splitk_hip(m_rows, len(blocks), arr, w.data_ptr(), w.stride(0) if w_view else 0, w.stride(1) if w_view else 0,
@@ -180,28 +181,8 @@ def _launch_stages(stages, m_rows, stats=None, csr=None):
             arr = (_abi.gsn_chain_stage * n)()
             keep = []
             for j, st in enumerate(cand):
-                blks = (carry if j == 0 else []) + st.blocks
-                if j == 0 and y is not None:
-                    blks = st.blocks + carry          # concatenation order: own HBM blocks, then the previous output
-                barr = (_abi.gsn_block * max(len(blks), 1))()
-                for b, (d, idx) in enumerate(blks):
-                    d = _f32c(d); keep.append(d)
-                    barr[b].data = d.data_ptr(); barr[b].width = d.shape[1]
-                    barr[b].idx = None; barr[b].idx32 = None
-                    if idx is not None:
-                        idx = idx.contiguous(); keep.append(idx)
-                        if idx.dtype == torch.int32:
-                            barr[b].idx32 = idx.data_ptr()
-                        else:
-                            barr[b].idx = idx.data_ptr()
-                keep.append(barr)
-                w = _f32c(st.weight); keep.append(w)
-                arr[j].blocks = barr; arr[j].n_blocks = len(blks)
-                arr[j].W = w.data_ptr(); arr[j].n_out = w.shape[0]
-                vecs = [None if v is None else _f32c(v) for v in ((st.bias,) + (st.bn_params or (None, None, None)))]
-                keep.extend(vecs)
-                arr[j].bias, arr[j].bn_mean, arr[j].bn_scale, arr[j].bn_shift = [_abi.ptr(v) for v in vecs]
-                arr[j].act = _ACT_CODE[st.act]
+                # concatenation order: own HBM blocks, then the previous output
+                arr[j] = _stage_struct(st, st.blocks + carry if j == 0 else st.blocks, keep)
             if L.gsn_mlp_chain_supported(n, arr):
                 group = (n, arr, keep, cand)
                 break
@@ -221,10 +202,7 @@ def _launch_stages(stages, m_rows, stats=None, csr=None):
                                                         out.data_ptr(), _abi.current_stream()), "gsn_segsum_prepare_hip")
             else:
                 out = None if want_stats else torch.empty((m_rows, n_out), dtype=torch.float32, device=dev)
-            flops = 0.0
-            kprev = 0
-            for j, st in enumerate(cand):
-                flops += 2.0 * m_rows * st.weight.shape[1] * st.weight.shape[0]
+            flops = sum(2.0 * m_rows * st.weight.shape[1] * st.weight.shape[0] for st in cand)
             with _abi.device_guard(dev), _timed("mlp_chain%d" % n, flops):
                 rc = L.gsn_mlp_chain_fwd_hip(m_rows, n, arr, None,
                                              csr.tgt.data_ptr() if seg else None, _abi.ptr(out),
@@ -254,32 +232,17 @@ def _chain_fits(stages):
     arr = (_abi.gsn_chain_stage * n)()
     keep = []
     for j, st in enumerate(stages):
-        barr = (_abi.gsn_block * max(len(st.blocks), 1))()
-        for b, (d, idx) in enumerate(st.blocks):
-            barr[b].data = 1; barr[b].idx = None; barr[b].idx32 = None; barr[b].width = d.shape[1]
-        keep.append(barr)
-        arr[j].blocks = barr; arr[j].n_blocks = len(st.blocks)
+        arr[j].blocks = _block_array(st.blocks, keep, widths_only=True); arr[j].n_blocks = len(st.blocks)
         arr[j].W = 1; arr[j].n_out = st.weight.shape[0]; arr[j].act = _ACT_CODE[st.act]
     return bool(_abi.lib().gsn_mlp_chain_supported(n, arr))
 
 
-def _stage_struct(st, blocks, keep):
-    """gsn_chain_stage of a resolved _Stage (BN parameters already in st.bn_params)."""
+def _stage_struct(st, blocks, keep, rows_keep=None):
+    """gsn_chain_stage of a resolved _Stage (BN parameters already in st.bn_params) on the input ``blocks``.  What it points at goes to
+    ``keep``; the blocks' rows and indices to ``rows_keep`` when given."""
     g = _abi.gsn_chain_stage()
-    barr = (_abi.gsn_block * max(len(blocks), 1))()
-    for b, (d, idx) in enumerate(blocks):
-        d = _f32c(d); keep.append(d)
-        barr[b].data = d.data_ptr(); barr[b].width = d.shape[1]
-        barr[b].idx = None; barr[b].idx32 = None
-        if idx is not None:
-            idx = idx.contiguous(); keep.append(idx)
-            if idx.dtype == torch.int32:
-                barr[b].idx32 = idx.data_ptr()
-            else:
-                barr[b].idx = idx.data_ptr()
-    keep.append(barr)
+    g.blocks = _block_array(blocks, keep if rows_keep is None else rows_keep); g.n_blocks = len(blocks)
     w = _f32c(st.weight); keep.append(w)
-    g.blocks = barr; g.n_blocks = len(blocks)
     g.W = w.data_ptr(); g.n_out = w.shape[0]
     vecs = [None if v is None else _f32c(v) for v in ((st.bias,) + (st.bn_params or (None, None, None)))]
     keep.extend(vecs)
@@ -297,9 +260,29 @@ def _prep_key(st):
     return (st.weight.data_ptr(), st.weight._version, tuple(st.weight.shape), bk)
 
 
+def _prepared(kind, ge, g0, g1, d_x, dev, owner=None, attr=None, key=None):
+    """The one-launch layer's weights as its kernel reads them: gsn_layer_fused{kind}_prepared_bytes -> allocate -> gsn_layer_fused{kind}_prepare_hip
+    (kind "": the fp32-row and graph-aligned kernels, "_pack16": the packed-row kernel, another k-slot order).  Made once per ``key`` and kept on
+    ``owner.<attr>`` (parameters, BatchNorm buffers and folded weights live across calls); no ``owner``: made, not kept."""
+    hit = getattr(owner, attr, None) if owner is not None else None
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    L = _abi.lib()
+    nbytes = int(getattr(L, "gsn_layer_fused%s_prepared_bytes" % kind)(ctypes.byref(ge), d_x, ctypes.byref(g0), ctypes.byref(g1)))
+    prep = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+    name = "gsn_layer_fused%s_prepare_hip" % kind
+    with _abi.device_guard(dev):
+        _abi.check(getattr(L, name)(ctypes.byref(ge), d_x, ctypes.byref(g0), ctypes.byref(g1), prep.data_ptr(), _abi.current_stream()), name)
+    if owner is not None:
+        setattr(owner, attr, (key, prep))
+        _note_cache(owner, attr)
+    return prep
+
+
 def _layer_fused(x, csr, edge_stages, node_stages, training, owner=None, gen=0, pack16=None, pack_only=False, record=None):
-    """edge stage + per-target sum + two node stages in ONE launch (gsn_layer_fused_fwd_hip); None if the layer does not
-    fit (shape, activation, or a BatchNorm1d that needs batch statistics)."""
+    """edge stage + per-target sum + two node stages in ONE launch; None if the layer does not fit (shape, activation, or a BatchNorm1d
+    that needs batch statistics).  Tagged exact inputs (``pack16``, gsn_amd.packs) take the packed-row kernel, a collated batch with known
+    graph boundaries the graph-aligned one, anything else the fp32-row kernel.  ``record``: the first two leave their launch on ``owner._fplan``."""
     if not flags.FUSED_LAYER or len(edge_stages) != 1 or len(node_stages) != 2:
         return None
     stages = edge_stages + node_stages
@@ -315,125 +298,113 @@ def _layer_fused(x, csr, edge_stages, node_stages, training, owner=None, gen=0, 
         return None
     for st in stages:
         _bn_resolve(st, None, 0, False)
-    keep = []
-    ge = _stage_struct(edge_stages[0], edge_stages[0].blocks, keep)
+    # `keep`: the weights and BatchNorm vectors, what a recorded launch keeps; this call's rows and indices only live through the call
+    keep, rows = [], []
+    eb = edge_stages[0].blocks
+    ge = _stage_struct(edge_stages[0], eb, keep, rows)
     g0 = _stage_struct(node_stages[0], [], keep)
     g1 = _stage_struct(node_stages[1], [], keep)
-    L = _abi.lib()
     d_x = x.shape[1]
     if node_stages[0].weight.shape[1] != d_x + edge_stages[0].weight.shape[0] + 4:
         return None
-    n = x.shape[0]
-    E = csr.tgt.numel()
-    flops = 2.0 * E * edge_stages[0].weight.shape[1] * edge_stages[0].weight.shape[0]
-    flops += 2.0 * n * (node_stages[0].weight.shape[1] * node_stages[0].weight.shape[0] + node_stages[1].weight.shape[1] * node_stages[1].weight.shape[0])
-    # tagged exact inputs (gsn_amd.packs): the same layer on their fp16 packs -- own prepared weights (another k-slot order), kept beside
-    # the fp32 kernel's under their own key
+    L = _abi.lib()
+    fl = (2.0 * edge_stages[0].weight.shape[1] * edge_stages[0].weight.shape[0],          # per edge, per node
+          2.0 * (node_stages[0].weight.shape[1] * node_stages[0].weight.shape[0] + node_stages[1].weight.shape[1] * node_stages[1].weight.shape[0]))
+    pkey = (tuple(_prep_key(st) for st in stages), d_x, gen)
     if pack16 is not None and flags.PACK16_LAYER and L.gsn_layer_fused_pack16_supported(ctypes.byref(ge), d_x, ctypes.byref(g0), ctypes.byref(g1)):
-        key = (tuple(_prep_key(st) for st in stages), d_x, gen, "pack16")
-        hit = getattr(owner, "_fused_prep16", None) if owner is not None else None
-        if hit is not None and hit[0] == key:
-            prep = hit[1]
-        else:
-            nbytes = int(L.gsn_layer_fused_pack16_prepared_bytes(ctypes.byref(ge), d_x, ctypes.byref(g0), ctypes.byref(g1)))
-            prep = torch.empty(nbytes // 4, dtype=torch.int32, device=x.device)
-            with _abi.device_guard(x.device):
-                _abi.check(L.gsn_layer_fused_pack16_prepare_hip(ctypes.byref(ge), d_x, ctypes.byref(g0), ctypes.byref(g1), prep.data_ptr(),
-                                                                _abi.current_stream()), "gsn_layer_fused_pack16_prepare_hip")
-            if owner is not None:
-                owner._fused_prep16 = (key, prep)
-                _note_cache(owner, "_fused_prep16")
-        n_out = node_stages[1].weight.shape[0]
-        pk = _abi.gsn_pack16()
-        fl_e = 2.0 * edge_stages[0].weight.shape[1] * edge_stages[0].weight.shape[0]
-        fl_n = 2.0 * (node_stages[0].weight.shape[1] * node_stages[0].weight.shape[0] + node_stages[1].weight.shape[1] * n_out)
-
-        def launch16(x_ptr, n_rows, dev, csr_now, idx_now, pack_now):
-            """The recorded call with this forward's pointers (x placeholder / rows, block indices, packs): one foreign call, no Python-side
-            stage building.  None when the library declines (packs beyond 32-bit offsets)."""
-            nb = ge.n_blocks
-            for i in range(nb):
-                ge.blocks[i].data = x_ptr if i < 2 else pack_now[1].data_ptr()
-                ge.blocks[i].idx32 = idx_now[i].data_ptr()
-            y = torch.empty((n_rows, n_out), dtype=torch.float32, device=dev)
-            pk.node_rows = pack_now[0].data_ptr()
-            pk.edge_rows = None if pack_now[1] is None else pack_now[1].data_ptr()
-            e_now = csr_now.tgt.numel()
-            with _abi.device_guard(dev), _timed("layer_fused", fl_e * e_now + fl_n * n_rows):
-                rc16 = L.gsn_layer_fused_fwd_pack16_hip(n_rows, e_now, csr_now.seg_ptr.data_ptr(), ctypes.byref(ge), x_ptr, d_x, ctypes.byref(g0), ctypes.byref(g1),
-                                                        prep.data_ptr(), ctypes.byref(pk), 0 if pack_now[1] is None else pack_now[1].shape[0], y.data_ptr(),
-                                                        _abi.current_stream())
-            if rc16 == -2:
-                return None
-            _abi.check(rc16, "gsn_layer_fused_fwd_pack16_hip")
-            return y
-        launch16._keep = keep
-        out = launch16(x.data_ptr(), n, x.device, csr, [b[1] for b in edge_stages[0].blocks], pack16)
+        prep = _prepared("_pack16", ge, g0, g1, d_x, x.device, owner, "_fused_prep16", pkey + ("pack16",))
+        launch16 = _pack16_launch(ge, g0, g1, d_x, prep, fl, keep)
+        out = launch16(x.data_ptr(), x.shape[0], x.device, csr, [idx for _, idx in eb], pack16)
         if out is not None:               # (None = GSN_E_UNSUPPORTED: packs beyond 32-bit offsets -> the fp32 kernel below)
-            if record is not None and owner is not None and all(b[1] is not None and b[1].dtype == torch.int32 for b in edge_stages[0].blocks):
+            if record is not None and owner is not None and all(idx is not None and idx.dtype == torch.int32 for _, idx in eb):
                 owner._fplan = (record, "pack16", launch16)
                 _note_cache(owner, "_fplan")
             return out
     if pack_only:                         # (the caller holds no fp32 rows: it makes them and comes back)
         return None
-    # the weights as the kernel's register fragments: once per weight version (kept on the layer module)
     if not L.gsn_layer_fused_supported(ctypes.byref(ge), d_x, ctypes.byref(g0), ctypes.byref(g1)):
         return None
-    out = torch.empty((n, node_stages[1].weight.shape[0]), dtype=torch.float32, device=x.device)
     # (the kernel variant the buffer is for -- this file's kernel alone, with the register-resident fragments appended, the d = 128
     #  layout -- follows from the block properties of THIS call: its size is part of the key)
     nbytes = int(L.gsn_layer_fused_prepared_bytes(ctypes.byref(ge), d_x, ctypes.byref(g0), ctypes.byref(g1)))
-    key = (tuple(_prep_key(st) for st in stages), d_x, gen, nbytes)
-    hit = getattr(owner, "_fused_prep", None) if owner is not None else None
-    if hit is not None and hit[0] == key:
-        prep = hit[1]
-    else:
-        prep = torch.empty(nbytes // 4, dtype=torch.int32, device=x.device)
-        with _abi.device_guard(x.device):
-            _abi.check(L.gsn_layer_fused_prepare_hip(ctypes.byref(ge), d_x, ctypes.byref(g0), ctypes.byref(g1), prep.data_ptr(),
-                                                     _abi.current_stream()), "gsn_layer_fused_prepare_hip")
-        if owner is not None:
-            owner._fused_prep = (key, prep)
-            _note_cache(owner, "_fused_prep")
-    # a collated batch with known graph boundaries, every graph <= 128 vertices: the d = 128 layer on graph-aligned tiles (csrc/layer_g.hip:
-    # the node part of the edge stage once per node); same prepared buffer, no workspace, no row exponents
-    part = getattr(csr, "part", None)
-    if (flags.GRAPH_ALIGNED_LAYER and part is not None and d_x == 128 and part[2] <= 128 and int(part[0].numel()) > 1
+    prep = _prepared("", ge, g0, g1, d_x, x.device, owner, "_fused_prep", pkey + (nbytes,))
+    if (flags.GRAPH_ALIGNED_LAYER and getattr(csr, "part", None) is not None and d_x == 128
             and L.gsn_layer_fused_graphs_supported(ctypes.byref(ge), d_x, ctypes.byref(g0), ctypes.byref(g1))):
-        n_out_g = node_stages[1].weight.shape[0]
-        fl_e = 2.0 * edge_stages[0].weight.shape[1] * edge_stages[0].weight.shape[0]
-        fl_n = 2.0 * (node_stages[0].weight.shape[1] * node_stages[0].weight.shape[0] + node_stages[1].weight.shape[1] * n_out_g)
-        roles = [None if b[0] is x else i for i, b in enumerate(edge_stages[0].blocks)]      # blocks that are x itself follow the call's x
-
-        def launch_g(x_now, csr_now, blocks_now, y=None):
-            """The recorded graph-aligned call with this forward's rows / indices / partition.  None when this batch is outside it."""
-            part_now = getattr(csr_now, "part", None)
-            if part_now is None or part_now[2] > 128 or int(part_now[0].numel()) <= 1 or x_now.data_ptr() % 16:
-                return None
-            for i in range(ge.n_blocks):
-                d_i, idx_i = blocks_now[i]
-                ge.blocks[i].data = d_i.data_ptr()
-                ge.blocks[i].idx = None
-                ge.blocks[i].idx32 = idx_i.data_ptr()
-            n_now, e_now = x_now.shape[0], csr_now.tgt.numel()
-            if y is None:
-                y = torch.empty((n_now, n_out_g), dtype=torch.float32, device=x_now.device)
-            with _abi.device_guard(x_now.device), _timed("layer_fused", fl_e * e_now + fl_n * n_now):
-                rcg = L.gsn_layer_fused_fwd_graphs_hip(n_now, e_now, csr_now.seg_ptr.data_ptr(), ctypes.byref(ge), x_now.data_ptr(), d_x, ctypes.byref(g0),
-                                                       ctypes.byref(g1), prep.data_ptr(), int(part_now[0].numel()) - 1, part_now[0].data_ptr(), int(part_now[2]),
-                                                       y.data_ptr(), _abi.current_stream())
-            if rcg == -2:
-                return None
-            _abi.check(rcg, "gsn_layer_fused_fwd_graphs_hip")
-            return y
-        launch_g._keep = keep
-        got = launch_g(x, csr, edge_stages[0].blocks, out)
-        if got is not None:
+        launch_g = _graphs_launch(ge, g0, g1, d_x, prep, fl, keep)
+        out = launch_g(x, csr, eb)
+        if out is not None:
             if (record is not None and owner is not None
-                    and all(b[1] is not None and b[1].dtype == torch.int32 and b[0].dtype == torch.float32 and b[0].is_contiguous() for b in edge_stages[0].blocks)):
+                    and all(idx is not None and idx.dtype == torch.int32 and d.dtype == torch.float32 and d.is_contiguous() for d, idx in eb)):
                 owner._fplan = (record, "graphs", launch_g)
                 _note_cache(owner, "_fplan")
-            return got
+            return out
+    return _rows_forward(x, csr, ge, g0, g1, d_x, prep, fl)
+
+
+def _pack16_launch(ge, g0, g1, d_x, prep, fl, keep):
+    """The packed-row layer (csrc/layer_rp.hip) as a call on one forward's pointers: ``launch16(x_ptr, n_rows, dev, csr, idx, packs)`` with the x
+    placeholder / rows, the edge blocks' indices and the fp16 packs -- one foreign call, no Python-side stage building.  None when the library
+    declines (packs beyond 32-bit offsets)."""
+    L = _abi.lib()
+    n_out = g1.n_out
+    pk = _abi.gsn_pack16()
+
+    def launch16(x_ptr, n_rows, dev, csr_now, idx_now, pack_now):
+        for i in range(ge.n_blocks):
+            ge.blocks[i].data = x_ptr if i < 2 else pack_now[1].data_ptr()
+            ge.blocks[i].idx32 = idx_now[i].data_ptr()
+        y = torch.empty((n_rows, n_out), dtype=torch.float32, device=dev)
+        pk.node_rows = pack_now[0].data_ptr()
+        pk.edge_rows = None if pack_now[1] is None else pack_now[1].data_ptr()
+        e_now = csr_now.tgt.numel()
+        with _abi.device_guard(dev), _timed("layer_fused", fl[0] * e_now + fl[1] * n_rows):
+            rc16 = L.gsn_layer_fused_fwd_pack16_hip(n_rows, e_now, csr_now.seg_ptr.data_ptr(), ctypes.byref(ge), x_ptr, d_x, ctypes.byref(g0), ctypes.byref(g1),
+                                                    prep.data_ptr(), ctypes.byref(pk), 0 if pack_now[1] is None else pack_now[1].shape[0], y.data_ptr(),
+                                                    _abi.current_stream())
+        if rc16 == -2:
+            return None
+        _abi.check(rc16, "gsn_layer_fused_fwd_pack16_hip")
+        return y
+    launch16._keep = keep
+    return launch16
+
+
+def _graphs_launch(ge, g0, g1, d_x, prep, fl, keep):
+    """The d = 128 layer on graph-aligned tiles (csrc/layer_g.hip: the node part of the edge stage once per node; a collated batch with known
+    graph boundaries, every graph <= 128 vertices; the fp32-row kernel's prepared buffer, no workspace, no row exponents) as a call on one
+    forward's rows / indices / partition: ``launch_g(x, csr, blocks, y=None)``.  None when this batch is outside it."""
+    L = _abi.lib()
+    n_out = g1.n_out
+
+    def launch_g(x_now, csr_now, blocks_now, y=None):
+        part_now = getattr(csr_now, "part", None)
+        if part_now is None or part_now[2] > 128 or int(part_now[0].numel()) <= 1 or x_now.data_ptr() % 16:
+            return None
+        for i in range(ge.n_blocks):
+            d_i, idx_i = blocks_now[i]
+            ge.blocks[i].data = d_i.data_ptr()
+            ge.blocks[i].idx = None
+            ge.blocks[i].idx32 = idx_i.data_ptr()
+        n_now, e_now = x_now.shape[0], csr_now.tgt.numel()
+        if y is None:
+            y = torch.empty((n_now, n_out), dtype=torch.float32, device=x_now.device)
+        with _abi.device_guard(x_now.device), _timed("layer_fused", fl[0] * e_now + fl[1] * n_now):
+            rcg = L.gsn_layer_fused_fwd_graphs_hip(n_now, e_now, csr_now.seg_ptr.data_ptr(), ctypes.byref(ge), x_now.data_ptr(), d_x, ctypes.byref(g0),
+                                                   ctypes.byref(g1), prep.data_ptr(), int(part_now[0].numel()) - 1, part_now[0].data_ptr(), int(part_now[2]),
+                                                   y.data_ptr(), _abi.current_stream())
+        if rcg == -2:
+            return None
+        _abi.check(rcg, "gsn_layer_fused_fwd_graphs_hip")
+        return y
+    launch_g._keep = keep
+    return launch_g
+
+
+def _rows_forward(x, csr, ge, g0, g1, d_x, prep, fl):
+    """The layer on fp32 rows (gsn_layer_fused_fwd_ws_hip); None when this call's arguments are outside the kernel after all."""
+    L = _abi.lib()
+    n, E = x.shape[0], csr.tgt.numel()
+    out = torch.empty((n, g1.n_out), dtype=torch.float32, device=x.device)
     # layers of a d = 128 model hand the row exponents of their output to the next one (csrc/layer_w.hip takes its edge rows' scales from
     # them): kept on the output tensor together with its version counter, used only while the tensor is unchanged
     x_exp = None
@@ -446,7 +417,7 @@ def _layer_fused(x, csr, edge_stages, node_stages, training, owner=None, gen=0, 
     out_exp = torch.empty(n, dtype=torch.int32, device=x.device) if d_x == 128 and out.shape[1] == 128 and flags.CHAIN_ROW_EXPONENTS else None
     ws_bytes = 0 if x_exp is not None else int(L.gsn_layer_fused_workspace_bytes(n, ctypes.byref(ge), d_x, ctypes.byref(g0), ctypes.byref(g1)))
     ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=x.device) if ws_bytes else None      # (the caching allocator: capture-safe)
-    with _abi.device_guard(x.device), _timed("layer_fused", flops):
+    with _abi.device_guard(x.device), _timed("layer_fused", fl[0] * E + fl[1] * n):
         rc = L.gsn_layer_fused_fwd_ws_hip(n, E, csr.seg_ptr.data_ptr(), ctypes.byref(ge), x.data_ptr(), d_x, ctypes.byref(g0),
                                           ctypes.byref(g1), prep.data_ptr(), out.data_ptr(), _abi.ptr(ws), ws_bytes, _abi.ptr(x_exp),
                                           _abi.ptr(out_exp), _abi.current_stream())
@@ -544,10 +515,6 @@ def _bn_resolve(stage, stats_fn, m_rows, training, fuse_act=None):
         stage.bn_invstd = invstd.contiguous()
         bn._gsn_eval_cache = (key, stage.bn_params, stage.bn_invstd)
         _note_cache(bn, "_gsn_eval_cache")
-        return
-    scale = invstd * bn.weight.detach() if bn.affine else invstd
-    shift = bn.bias.detach() if bn.affine else torch.zeros_like(invstd)
-    stage.bn_params = (mean32, scale, shift)
 
 
 def run_stages(stages, m_rows, training, csr=None):

@@ -94,14 +94,12 @@ class CountLayerStep:
         for st in stages:
             _dense._bn_resolve(st, None, 0, False)
         keep = []
-        ge = _dense._stage_struct(edge_stages[0], [], keep)
-        # the edge stage's blocks: x through the sorted targets, x through the sorted sources, the edge pack's columns through perm
-        barr = (_abi.gsn_block * 3)()
-        x_ptr = b["npack"].data_ptr()
-        for i, (ptr, width, idx) in enumerate(((x_ptr, d_x, b["tgt"]), (x_ptr, d_x, b["src"]), (b["epack"].data_ptr(), w_e, b["perm"]))):
-            barr[i].data = ptr; barr[i].width = width; barr[i].idx = None; barr[i].idx32 = idx.data_ptr()
-        keep.append(barr)
-        ge.blocks = barr; ge.n_blocks = 3
+        # the edge stage's blocks: x through the sorted targets, x through the sorted sources, the edge pack's columns through perm -- their rows
+        # are the two packs (empty fp32 placeholders give the widths)
+        ew = torch.empty((0, w_e), dtype=torch.float32, device=dev)
+        ge = _dense._stage_struct(edge_stages[0], [(sb[0][0], b["tgt"]), (sb[0][0], b["src"]), (ew, b["perm"])], keep)
+        for i in range(3):
+            ge.blocks[i].data = b["npack"].data_ptr() if i < 2 else b["epack"].data_ptr()
         g0 = _dense._stage_struct(node_stages[0], [], keep)
         g1 = _dense._stage_struct(node_stages[1], [], keep)
         L = _abi.lib()
@@ -109,11 +107,7 @@ class CountLayerStep:
             raise ValueError("CountLayerStep: the layer's widths do not match the codes (d_x %d, edge-level columns %d)" % (d_x, w_e))
         if not L.gsn_layer_fused_pack16_supported(ctypes.byref(ge), d_x, ctypes.byref(g0), ctypes.byref(g1)):
             raise ValueError("CountLayerStep: shape outside the packed-row layer kernel (every stage 128 wide, d_x + 4 <= 32, <= 16 edge-level columns)")
-        nbytes = int(L.gsn_layer_fused_pack16_prepared_bytes(ctypes.byref(ge), d_x, ctypes.byref(g0), ctypes.byref(g1)))
-        prep = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
-        with _abi.device_guard(dev):
-            _abi.check(L.gsn_layer_fused_pack16_prepare_hip(ctypes.byref(ge), d_x, ctypes.byref(g0), ctypes.byref(g1), prep.data_ptr(),
-                                                            _abi.current_stream()), "gsn_layer_fused_pack16_prepare_hip")
+        prep = _dense._prepared("_pack16", ge, g0, g1, d_x, dev)
         d_out = node_stages[1].weight.shape[0]
         flops = 2.0 * E * edge_stages[0].weight.shape[1] * edge_stages[0].weight.shape[0]
         flops += 2.0 * N * (node_stages[0].weight.shape[1] * node_stages[0].weight.shape[0] + node_stages[1].weight.shape[1] * d_out)

@@ -30,8 +30,16 @@ def _full_path(layer, *args, **kw):
         return layer(*args, **kw)
 
 
+def _assert_record_holds_no_batch_tensor(layer, batch):
+    """a recorded launch keeps its stage descriptors, weights, BatchNorm vectors and prepared weights -- no rows, packs or CSR index of the
+    batch that recorded it (every later call writes its own pointers)"""
+    base = lambda ts: {t.untyped_storage().data_ptr() for t in ts if isinstance(t, torch.Tensor) and t.numel() > 0}
+    kept = base(layer._fplan[2]._keep)
+    assert kept and not kept & base(batch)
+
+
 def test_layer0_on_codes_recorded_launch_equals_the_full_path_and_follows_the_parameters():
-    from gsn_amd import layers
+    from gsn_amd import layers, packs
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     layer = layers.GSN_edge_sparse(**CTOR0).to(dev).eval()
@@ -41,11 +49,15 @@ def test_layer0_on_codes_recorded_launch_equals_the_full_path_and_follows_the_pa
         ids = torch.randint(0, 3, (b.num_edges, 4), device=dev)
         mk = lambda: dict(identifiers=layers.Codes(ids, [3, 3, 3, 3], clamp=True), degrees=torch.zeros(b.num_nodes, device=dev),
                           edge_features=layers.Codes(bonds, [4]))
+        xc, kw = layers.Codes(atoms, [28]), mk()
         with torch.no_grad():
-            y = layer(layers.Codes(atoms, [28]), ei, **mk())
+            y = layer(xc, ei, **kw)
         assert getattr(layer, "_fplan", None) is not None and layer._fplan[1] == "pack16"
+        pk = packs.from_codes(xc, [kw["identifiers"], kw["edge_features"]])     # (the packs of that call, tagged on its Codes objects)
         with torch.no_grad():
             y2 = layer(layers.Codes(atoms, [28]), ei, **mk())             # (recorded)
+        csr = layers._csr_for(ei, layer._sel(), b.num_nodes)
+        _assert_record_holds_no_batch_tensor(layer, [atoms, ids, bonds, csr.tgt, csr.src, csr.perm, pk[0], pk[1]])
         y_full = _full_path(layer, layers.Codes(atoms, [28]), ei, **mk())
         assert torch.equal(y, y_full) and torch.equal(y2, y_full)
         outs.append(y_full)
@@ -87,6 +99,8 @@ def test_wide_layer_recorded_launch(partition):
             y2 = layer(x, ei, **kw)
         if partition:
             assert layer._fplan[1] == "graphs"
+            csr = layers._csr_for(ei, layer._sel(), b.num_nodes)
+            _assert_record_holds_no_batch_tensor(layer, [x, ids, ef, csr.tgt, csr.src, csr.perm])
         y_full = _full_path(layer, x, ei, **kw)
         assert torch.equal(y1, y_full) and torch.equal(y2, y_full)
     # the post-stage's BatchNorm moves: refused, recorded again
