@@ -67,6 +67,10 @@ class gsn_code_slot(ctypes.Structure):
                 ("w_off", ctypes.c_int32), ("n_classes", ctypes.c_int32), ("clamp", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class gsn_dgn_agg(ctypes.Structure):
+    _fields_ = [("kind", c_i32), ("col", c_i32), ("alpha", ctypes.c_float), ("slot", c_i32)]
+
+
 SIGNATURES = {
     "gsn_last_error": (ctypes.c_char_p, []),
     "gsn_version": (c_int, []),
@@ -166,6 +170,10 @@ SIGNATURES = {
     "gsn_layer_fused_fwd_graphs_hip": (c_int, [c_i64, c_i64, c_vp, ctypes.POINTER(gsn_chain_stage), c_vp, c_i64, ctypes.POINTER(gsn_chain_stage),
                                                ctypes.POINTER(gsn_chain_stage), c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "gsn_mlp_chain_fwd_hip": (c_int, [c_i64, c_int, ctypes.POINTER(gsn_chain_stage), c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "gsn_dgn_aggregate_fwd_hip": (c_int, [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64,
+                                          ctypes.POINTER(gsn_dgn_agg), c_int, c_vp, c_int, ctypes.c_double, c_vp, c_vp]),
+    "gsn_dgn_aggregate_bwd_hip": (c_int, [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
+                                          c_i64, ctypes.POINTER(gsn_dgn_agg), c_int, c_vp, c_int, ctypes.c_double, c_vp, c_vp, c_vp, c_vp]),
 }
 
 

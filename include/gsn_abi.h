@@ -785,6 +785,45 @@ int gsn_bn_finalize_count_hip(int64_t n_cols, int64_t m_rows, double eps, double
                               const float *beta, float *running_mean, float *running_var, float *mean, float *invstd, float *scale,
                               float *shift, int64_t *num_batches_tracked, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Directional GSN aggregation (directional_gsn/nets/dgn_layer.py:30-56, nets/aggregators.py, nets/scalers.py).
+ * For each node v, over its in-edges e = (u -> v) in edge-id order (the target-sorted CSR of edge_index[1]: seg_ptr [N+1],
+ * perm [E] edge ids stable by target, src [E] = edge_index[0][perm]), with message h[u] (fp32 [N, d]) and vector field
+ * w = cat(node_field[u] - node_field[v], edge_field[e]) (either part may be absent: width 0; edge_field rows by edge id):
+ *   out[v, (s * A + slot) * d + f] = scaler_s(D) * aggregator(h[src], w[:, col], h[v])[f]        out fp32 [N, S * A * d]
+ * for the n_aggs descriptors (A = n_aggs, slots a permutation of 0 .. A-1) and the n_scalers (<= 4) scaler codes; avg_d_log is
+ * avg_d['log'].  The reference scales only when more than one scaler is given (dgn_layer.py:50): the caller then passes
+ * GSN_DGN_IDENTITY alone.  Nodes without in-edges get a zero row.  A directional descriptor whose column is outside the field
+ * returns GSN_E_INVALID before any launch (the reference raises IndexError).
+ * Backward: grad_h [N, d] (fully written) = d L / d h from grad_out; grad_msg [E, d] is caller scratch (per-edge message gradients
+ * at edge ids), src_seg_ptr / src_perm the CSR of edge_index[0].  Deterministic (no atomics); max / min route the gradient to the
+ * lowest edge id holding the extremum.  The fields carry no gradient.
+ * ---------------------------------------------------------------------------------------------------------------- */
+enum {
+    GSN_DGN_MEAN = 0, GSN_DGN_SUM = 1, GSN_DGN_MAX = 2, GSN_DGN_MIN = 3, GSN_DGN_VAR = 4, GSN_DGN_STD = 5,
+    GSN_DGN_DIR_AV = 6,          /* sum h |w| / (sum |w| + EPS) */
+    GSN_DGN_DIR_SOFTMAX = 7,     /* sum h softmax_edges(alpha |w|) */
+    GSN_DGN_DIR_DX = 8,          /* |sum h w' - (sum w') h_in|, w' = w / (sum |w| + EPS) */
+    GSN_DGN_DIR_DX_NOABS = 9,    /* the same without abs */
+    GSN_DGN_DIR_DX_BALANCED = 10 /* dx with w' = (relu(w) / (sum relu(w) + EPS) + relu(-w) / (sum relu(-w) + EPS)) / 2 */
+};
+enum { GSN_DGN_IDENTITY = 0, GSN_DGN_AMPLIFICATION = 1, GSN_DGN_ATTENUATION = 2 };
+typedef struct {
+    int32_t kind;  /* GSN_DGN_* */
+    int32_t col;   /* vector-field column of the directional kinds */
+    float alpha;   /* GSN_DGN_DIR_SOFTMAX */
+    int32_t slot;  /* output aggregator index */
+} gsn_dgn_agg;
+int gsn_dgn_aggregate_fwd_hip(int64_t n_nodes, int64_t n_edges, int64_t d, const int32_t *seg_ptr, const int32_t *perm, const int32_t *src,
+                              const float *h, const float *node_field, int64_t node_stride, int64_t node_width, const float *edge_field,
+                              int64_t edge_stride, int64_t edge_width, const gsn_dgn_agg *aggs, int n_aggs, const int32_t *scalers,
+                              int n_scalers, double avg_d_log, float *out, void *stream);
+int gsn_dgn_aggregate_bwd_hip(int64_t n_nodes, int64_t n_edges, int64_t d, const int32_t *seg_ptr, const int32_t *perm, const int32_t *src,
+                              const int32_t *src_seg_ptr, const int32_t *src_perm, const float *h, const float *node_field,
+                              int64_t node_stride, int64_t node_width, const float *edge_field, int64_t edge_stride, int64_t edge_width,
+                              const gsn_dgn_agg *aggs, int n_aggs, const int32_t *scalers, int n_scalers, double avg_d_log,
+                              const float *grad_out, float *grad_msg, float *grad_h, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
