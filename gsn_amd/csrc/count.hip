@@ -90,6 +90,7 @@ struct CountArgs {
     int side_mask;             // bit 0: CSR, bit 1: node pack, bit 2: edge codes; != 0: the grid holds side workgroups
     int n_items;               // counting work items of the launch (graphs, or pairs of graphs)
     int lds_bytes;             // dynamic LDS of the launch (a side workgroup sorts as many graphs at a time as fit there)
+    unsigned cyc_len;          // cycle instantiation: the cycle length of output column c in byte c (count_core.h: cycle_plan_lengths)
     SideArgs side;
 };
 
@@ -376,7 +377,9 @@ __device__ unsigned long long *g_count_prof2;  // [12] wave-level sums over the 
 // classes (symmetric rows), four output columns, one workgroup per pair of graphs (no split), encoded rows staged as class
 // indices -- instead of ~12 launch arguments that are tested in every arm of the pool and held in scalar registers
 // through the whole kernel (106 of them + spills before).  The launcher selects it when all of that holds (launch<>()).
-template <int W, int T, bool DIR, bool TAIL, bool MOL>
+// CYC = L > 0 (with MOL): every column is a non-induced cycle of length <= L -- no plan table, candidate stack or distance tables in LDS,
+// and the task pool is one bitset path walk per searching row (count_core.h: cycle_walk) that yields the row's four cells at once.
+template <int W, int T, bool DIR, bool TAIL, bool MOL, int CYC = 0>
 __device__ __forceinline__ int count_body(const CountArgs &a, unsigned char *smem, const int item, const int part, const int g, const int ng, const bool report) {
 #ifdef COUNT_PROF
     unsigned long long t_prev = __builtin_amdgcn_s_memtime();
@@ -399,7 +402,7 @@ __device__ __forceinline__ int count_body(const CountArgs &a, unsigned char *sme
     uint16_t *revof = reinterpret_cast<uint16_t *>(smem + a.off_revof);
     uint16_t *out_lds = reinterpret_cast<uint16_t *>(smem + a.off_out);   // staged counts as 16-bit values; 0xffff = this cell went to HBM by itself
     int *misc = reinterpret_cast<int *>(smem + a.off_misc);  // [0] next task  [1] n_active  [2] status
-    uint64_t *balls = a.off_ball >= 0 ? reinterpret_cast<uint64_t *>(smem + a.off_ball) : nullptr;
+    uint64_t *balls = (!CYC && a.off_ball >= 0) ? reinterpret_cast<uint64_t *>(smem + a.off_ball) : nullptr;
     uint64_t *cores = reinterpret_cast<uint64_t *>(smem + a.off_core);   // [CORE_MAX + 1][W]
     uint64_t *degp = (TAIL && a.off_degp >= 0) ? reinterpret_cast<uint64_t *>(smem + a.off_degp) : nullptr;     // (TAIL = false: none of this exists)
     uint64_t *A_in = DIR ? reinterpret_cast<uint64_t *>(smem + a.off_ain) : nullptr;
@@ -459,7 +462,8 @@ __device__ __forceinline__ int count_body(const CountArgs &a, unsigned char *sme
     for (int i = tid; i < n * W; i += T) A[i] = 0ull;
     if (DIR)
         for (int i = tid; i < n * W; i += T) A_in[i] = 0ull;
-    for (int i = tid; i < a.plan_words; i += T) plan[i] = a.plan[i];
+    if (!CYC)
+        for (int i = tid; i < a.plan_words; i += T) plan[i] = a.plan[i];
     if (a_enc)                                          // (first float, n_classes) per column
         for (int c = tid; c < n_cols; c += T) {
             int o = 0;
@@ -666,20 +670,6 @@ __device__ __forceinline__ int count_body(const CountArgs &a, unsigned char *sme
     }
 
     COUNT_T(4);
-    // ---- phase 3: task pool -- (column, row) cells, pulled by lanes as they go idle --------------------------------
-    // this workgroup takes the tasks  part, part + split, part + 2*split, ...  (strided, so the heavy columns of a
-    // pattern family are spread over all the workgroups of a graph); n_tasks = how many of them
-    const int n_div = edge_mode ? misc[3] : rows;            // rows that run searches
-    const int n_tasks_all = n_div * n_cols;
-    const int n_tasks = n_tasks_all > part ? (n_tasks_all - part + a_split - 1) / a_split : 0;
-    const float div_rcp = n_div > 0 ? 1.0f / (float)n_div : 0.f;
-    const bool div_float = n_tasks_all < (1 << 22);        // task index exact in fp32: quotient by one multiply + one correction
-    const uint32_t *col_ptr = plan + PLAN_HEADER_WORDS;
-    const uint32_t *col_order = col_ptr + n_cols + 1;
-    const uint32_t *plans = plan + a.plans_off;
-    const int lane = tid & 63;
-    const uint64_t lane_lt = (1ull << lane) - 1ull;
-
 #ifdef COUNT_PROF
     unsigned prof_iters = 0, prof_lanes = 0;          // pool loop trips of the wave, lanes inside a rooted search summed over the trips
     unsigned prof_arm[4] = {0, 0, 0, 0};              // cycles of the wave in the pull / begin / step / finish arm
@@ -689,117 +679,167 @@ __device__ __forceinline__ int count_body(const CountArgs &a, unsigned char *sme
 #define COUNT_ARM(I, T0)
 #define COUNT_ARM_T0() 0ull
 #endif
-    Lane<W> s;
-#ifdef COUNT_PROF_STEP
-    for (int q = 0; q < 12; ++q) s.prof[q] = 0;
+    if constexpr (CYC > 0) {
+        // ---- phase 3 (cycle columns): one path walk per searching row, a row per lane; the walk's counts are the row's four cells and
+        // those of its mirror row.  Inner vertices are pruned with the 2-core, the core the cycle plans name (and the one phase 2
+        // filtered the roots with).
+        static_assert(W == 1 && MOL, "the cycle walk is the molecule instantiation's: one-word adjacency rows, four columns");
+        const uint64_t core2 = cores[2 * W];
+        const int n_div = misc[3];                         // rows that run walks
+        for (int i = tid; i < n_div; i += T) {
+#ifdef COUNT_PROF
+            prof_iters += 1; prof_lanes += (unsigned)__popcll(__ballot(1));      // passes of the wave, rows walked per pass
 #endif
-    s.l = -1; s.cnt = 0; s.k = 0; s.nfix = 0; s.fvec = fv_roots<W>(0, 0); s.plan = plans;
-    s.balls = balls; s.ball_n = a.n_cap; s.degp = nullptr; s.loop = 0;
-    if (TAIL) { s.degp = degp; s.loop = a.tail_loop; }
+            const unsigned long long t0 = COUNT_ARM_T0();
+            (void)t0;
+            const int row = prim[i];
+            uint64_t cnt[CYC - 2];
+            cycle_walk<CYC>(A, eu[row], ev[row], core2, cnt);
+            COUNT_ARM(2, t0);
+            const unsigned long long t0f = COUNT_ARM_T0();
+            (void)t0f;
+            const int rev = revof[row] == 0xffffu ? -1 : (int)revof[row];
+            bool any = false;
 #pragma unroll
-    for (int w = 0; w < W; ++w) s.used.w[w] = 0ull;
-    bool has_task = false, exhausted = false;
-    int t_row = 0, t_col = 0, p_i = 0, p_e = 0;
-    FVec<W> roots = fv_roots<W>(0, 0);
-    bool rev_missing = false;
-    int mirror_row = -1;
-    const uint64_t *lane_valid = valid;     // candidate universe of the lane's current plan (a core of the graph)
+            for (int col = 0; col < 4; ++col) {
+                const int j = (int)((a.cyc_len >> (8 * col)) & 0xffu) - 3;
+                uint64_t c = 0;
+#pragma unroll
+                for (int q = 0; q < CYC - 2; ++q) c = j == q ? cnt[q] : c;
+                emit_cell(row, col, c);
+                if (rev >= 0) emit_cell(rev, col, c);
+                any = any || c != 0;
+            }
+            if (rev < 0 && any) atomicMax(&misc[2], (int)GSN_ST_KEYERROR);
+            COUNT_ARM(3, t0f);
+        }
+    } else {
+        // ---- phase 3: task pool -- (column, row) cells, pulled by lanes as they go idle --------------------------------
+        // this workgroup takes the tasks  part, part + split, part + 2*split, ...  (strided, so the heavy columns of a
+        // pattern family are spread over all the workgroups of a graph); n_tasks = how many of them
+        const int n_div = edge_mode ? misc[3] : rows;            // rows that run searches
+        const int n_tasks_all = n_div * n_cols;
+        const int n_tasks = n_tasks_all > part ? (n_tasks_all - part + a_split - 1) / a_split : 0;
+        const float div_rcp = n_div > 0 ? 1.0f / (float)n_div : 0.f;
+        const bool div_float = n_tasks_all < (1 << 22);        // task index exact in fp32: quotient by one multiply + one correction
+        const uint32_t *col_ptr = plan + PLAN_HEADER_WORDS;
+        const uint32_t *col_order = col_ptr + n_cols + 1;
+        const uint32_t *plans = plan + a.plans_off;
+        const int lane = tid & 63;
+        const uint64_t lane_lt = (1ull << lane) - 1ull;
 
-    // The loop is a state machine per lane (pull a cell, begin a plan, one search step, finish the cell) and a wave executes every arm
-    // some lane is in: on molecules a trip is ~350 instructions of which the step arm is ~100, and the whole pool is ~9 trips of ~4 000
-    // cycles (profiles/r05_count_phase_profile.txt) -- dependent LDS round trips, not arithmetic.  So (i) a cell that ends inside a begin
-    // or a step is finished in the SAME trip (its own arm behind them), and (ii) idle lanes are refilled in batches: the pull arm (an LDS
-    // atomic, the task decode, five dependent table reads) runs when GSN_PULL_BATCH lanes wait or when no lane is inside a search, not
-    // in every trip for the one lane that happened to finish.
-    for (;;) {
-        const bool need = !has_task && !exhausted;
-        uint64_t m = __ballot(need);
-        if (m && __popcll(m) < a.pull_batch && __ballot(has_task) != 0ull) m = 0ull;
-        const unsigned long long arm_t0 = COUNT_ARM_T0();
-        if (m) {
-            const int leader = __ffsll((unsigned long long)m) - 1;
-            int base = 0;
-            if (lane == leader) base = atomicAdd(&misc[0], __popcll(m));
-            base = __shfl(base, leader);
-            if (need) {
-                const int t = base + __popcll(m & lane_lt);
-                if (t < n_tasks) {
-                    const int tt = part + t * a_split;
-                    int t_idx;
-                    if (div_float) {
-                        t_col = (int)((float)tt * div_rcp);
-                        t_idx = tt - t_col * n_div;
-                        if (t_idx < 0) { --t_col; t_idx += n_div; }
-                        if (t_idx >= n_div) { ++t_col; t_idx -= n_div; }
+        Lane<W> s;
+#ifdef COUNT_PROF_STEP
+        for (int q = 0; q < 12; ++q) s.prof[q] = 0;
+#endif
+        s.l = -1; s.cnt = 0; s.k = 0; s.nfix = 0; s.fvec = fv_roots<W>(0, 0); s.plan = plans;
+        s.balls = balls; s.ball_n = a.n_cap; s.degp = nullptr; s.loop = 0;
+        if (TAIL) { s.degp = degp; s.loop = a.tail_loop; }
+#pragma unroll
+        for (int w = 0; w < W; ++w) s.used.w[w] = 0ull;
+        bool has_task = false, exhausted = false;
+        int t_row = 0, t_col = 0, p_i = 0, p_e = 0;
+        FVec<W> roots = fv_roots<W>(0, 0);
+        bool rev_missing = false;
+        int mirror_row = -1;
+        const uint64_t *lane_valid = valid;     // candidate universe of the lane's current plan (a core of the graph)
+
+        // The loop is a state machine per lane (pull a cell, begin a plan, one search step, finish the cell) and a wave executes every arm
+        // some lane is in: on molecules a trip is ~350 instructions of which the step arm is ~100, and the whole pool is ~9 trips of ~4 000
+        // cycles (profiles/r05_count_phase_profile.txt) -- dependent LDS round trips, not arithmetic.  So (i) a cell that ends inside a begin
+        // or a step is finished in the SAME trip (its own arm behind them), and (ii) idle lanes are refilled in batches: the pull arm (an LDS
+        // atomic, the task decode, five dependent table reads) runs when GSN_PULL_BATCH lanes wait or when no lane is inside a search, not
+        // in every trip for the one lane that happened to finish.
+        for (;;) {
+            const bool need = !has_task && !exhausted;
+            uint64_t m = __ballot(need);
+            if (m && __popcll(m) < a.pull_batch && __ballot(has_task) != 0ull) m = 0ull;
+            const unsigned long long arm_t0 = COUNT_ARM_T0();
+            if (m) {
+                const int leader = __ffsll((unsigned long long)m) - 1;
+                int base = 0;
+                if (lane == leader) base = atomicAdd(&misc[0], __popcll(m));
+                base = __shfl(base, leader);
+                if (need) {
+                    const int t = base + __popcll(m & lane_lt);
+                    if (t < n_tasks) {
+                        const int tt = part + t * a_split;
+                        int t_idx;
+                        if (div_float) {
+                            t_col = (int)((float)tt * div_rcp);
+                            t_idx = tt - t_col * n_div;
+                            if (t_idx < 0) { --t_col; t_idx += n_div; }
+                            if (t_idx >= n_div) { ++t_col; t_idx -= n_div; }
+                        } else {
+                            t_col = tt / n_div;
+                            t_idx = tt - t_col * n_div;
+                        }
+                        // columns in the plan compiler's order of falling estimated cost: the lanes that go idle at the end of the pool
+                        // should be left with the short searches, not with the long ones
+                        t_col = (int)col_order[t_col];
+                        has_task = true;
+                        s.cnt = 0; s.l = -1;
+                        p_i = (int)col_ptr[t_col]; p_e = (int)col_ptr[t_col + 1];
+                        rev_missing = false;
+                        mirror_row = -1;
+                        if (edge_mode) {
+                            t_row = prim[t_idx];
+                            const int rev = revof[t_row] == 0xffffu ? -1 : (int)revof[t_row];
+                            rev_missing = rev < 0;
+                            if (a_sym && rev >= 0) mirror_row = rev;
+                            roots = fv_roots<W>(eu[t_row], ev[t_row]);
+                        } else {
+                            t_row = t_idx;
+                            if (!((valid[t_row >> 6] >> (t_row & 63)) & 1ull)) p_i = p_e;  // vertex beyond the largest id: not a vertex of the matched graph
+                            roots = fv_roots<W>(t_row, 0);
+                        }
                     } else {
-                        t_col = tt / n_div;
-                        t_idx = tt - t_col * n_div;
+                        exhausted = true;
                     }
-                    // columns in the plan compiler's order of falling estimated cost: the lanes that go idle at the end of the pool
-                    // should be left with the short searches, not with the long ones
-                    t_col = (int)col_order[t_col];
-                    has_task = true;
-                    s.cnt = 0; s.l = -1;
-                    p_i = (int)col_ptr[t_col]; p_e = (int)col_ptr[t_col + 1];
-                    rev_missing = false;
-                    mirror_row = -1;
-                    if (edge_mode) {
-                        t_row = prim[t_idx];
-                        const int rev = revof[t_row] == 0xffffu ? -1 : (int)revof[t_row];
-                        rev_missing = rev < 0;
-                        if (a_sym && rev >= 0) mirror_row = rev;
-                        roots = fv_roots<W>(eu[t_row], ev[t_row]);
-                    } else {
-                        t_row = t_idx;
-                        if (!((valid[t_row >> 6] >> (t_row & 63)) & 1ull)) p_i = p_e;  // vertex beyond the largest id: not a vertex of the matched graph
-                        roots = fv_roots<W>(t_row, 0);
+                }
+            }
+            if (m) COUNT_ARM(0, arm_t0);
+            if (__ballot(has_task) == 0ull) break;
+#ifdef COUNT_PROF
+            prof_iters += 1; prof_lanes += (unsigned)__popcll(__ballot(has_task && s.l >= 0));
+#endif
+            if (has_task) {
+                if (s.l < 0) {
+                    if (p_i < p_e) {
+                        const unsigned long long t0 = COUNT_ARM_T0();
+                        const uint32_t *pl = plans + p_i * (DIR ? PLAN_STRIDE_DIRECTED : PLAN_STRIDE_WORDS);
+                        lane_valid = cores + plan_core(pl) * W;
+                        lane_begin<W, DIR, TAIL>(s, pl, roots, A, lane_valid, stack, T, tid, A_in);
+                        ++p_i;
+                        COUNT_ARM(1, t0);
                     }
                 } else {
-                    exhausted = true;
-                }
-            }
-        }
-        if (m) COUNT_ARM(0, arm_t0);
-        if (__ballot(has_task) == 0ull) break;
-#ifdef COUNT_PROF
-        prof_iters += 1; prof_lanes += (unsigned)__popcll(__ballot(has_task && s.l >= 0));
-#endif
-        if (has_task) {
-            if (s.l < 0) {
-                if (p_i < p_e) {
                     const unsigned long long t0 = COUNT_ARM_T0();
-                    const uint32_t *pl = plans + p_i * (DIR ? PLAN_STRIDE_DIRECTED : PLAN_STRIDE_WORDS);
-                    lane_valid = cores + plan_core(pl) * W;
-                    lane_begin<W, DIR, TAIL>(s, pl, roots, A, lane_valid, stack, T, tid, A_in);
-                    ++p_i;
-                    COUNT_ARM(1, t0);
-                }
-            } else {
-                const unsigned long long t0 = COUNT_ARM_T0();
-                lane_step<W, DIR, TAIL>(s, A, lane_valid, stack, T, tid, A_in);
-                COUNT_ARM(2, t0);
+                    lane_step<W, DIR, TAIL>(s, A, lane_valid, stack, T, tid, A_in);
+                    COUNT_ARM(2, t0);
 #ifdef COUNT_PROF_STEP
-                s.prof[9] += 1; s.prof[10] += (unsigned long long)__popcll(__ballot(1));      // lane_step visits / active lanes
+                    s.prof[9] += 1; s.prof[10] += (unsigned long long)__popcll(__ballot(1));      // lane_step visits / active lanes
 #endif
-            }
-            const unsigned long long t0f = COUNT_ARM_T0();
-            if (s.l < 0 && p_i >= p_e) {
-                // cell finished (its last plan ended in this trip's begin or step, or it had none)
-                emit_cell(t_row, t_col, s.cnt);
-                if (mirror_row >= 0) emit_cell(mirror_row, t_col, s.cnt);
-                if (edge_mode && rev_missing && s.cnt != 0) atomicMax(&misc[2], (int)GSN_ST_KEYERROR);
-                has_task = false;
-                COUNT_ARM(3, t0f);
+                }
+                const unsigned long long t0f = COUNT_ARM_T0();
+                if (s.l < 0 && p_i >= p_e) {
+                    // cell finished (its last plan ended in this trip's begin or step, or it had none)
+                    emit_cell(t_row, t_col, s.cnt);
+                    if (mirror_row >= 0) emit_cell(mirror_row, t_col, s.cnt);
+                    if (edge_mode && rev_missing && s.cnt != 0) atomicMax(&misc[2], (int)GSN_ST_KEYERROR);
+                    has_task = false;
+                    COUNT_ARM(3, t0f);
+                }
             }
         }
+#ifdef COUNT_PROF_STEP
+        if ((threadIdx.x & 63) == 0 && g_count_prof2) for (int q = 0; q < 12; ++q) atomicAdd(&g_count_prof2[q], s.prof[q]);
+#endif
     }
     __syncthreads();
 
     COUNT_T(5);
 #ifdef COUNT_PROF
-#ifdef COUNT_PROF_STEP
-    if ((threadIdx.x & 63) == 0 && g_count_prof2) for (int q = 0; q < 12; ++q) atomicAdd(&g_count_prof2[q], s.prof[q]);
-#endif
     if (threadIdx.x == 0 && g_count_prof) { g_count_prof[(size_t)blockIdx.x * 16 + 7] = ((unsigned long long)prof_iters << 32) | prof_lanes; for (int q = 0; q < 4; ++q) g_count_prof[(size_t)blockIdx.x * 16 + 8 + q] = prof_arm[q]; }
 #endif
     // ---- phase 4: coalesced write of the staged rows --------------------------------------------------------------
@@ -898,7 +938,7 @@ __device__ __forceinline__ int count_body(const CountArgs &a, unsigned char *sme
 #ifndef COUNT_W4_WAVES
 #define COUNT_W4_WAVES 1
 #endif
-template <int W, int T, bool DIR, bool TAIL, bool MOL = false>
+template <int W, int T, bool DIR, bool TAIL, bool MOL = false, int CYC = 0>
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(DIR ? 1 : (W == 1 ? COUNT_W1_WAVES : (W == 2 ? COUNT_W2_WAVES : (W == 4 ? COUNT_W4_WAVES : 1))))))
 void count_kernel(CountArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -926,7 +966,7 @@ void count_kernel(CountArgs a) {
     for (int pass = 0; pass < 3; ++pass) {
         const int g = pass == 2 ? g0 + 1 : g0;
         const int ng = (pass == 0 && two) ? 2 : 1;
-        const int rc = count_body<W, T, DIR, TAIL, MOL>(a, smem, item, (MOL || a.pair) ? 0 : part, g, ng, ng == 1);
+        const int rc = count_body<W, T, DIR, TAIL, MOL, CYC>(a, smem, item, (MOL || a.pair) ? 0 : part, g, ng, ng == 1);
         if (!two || (pass == 0 && rc == 0)) break;
     }
 }
@@ -969,12 +1009,12 @@ __global__ void status_zero_kernel(const int32_t *graph_ids, int n, int32_t *sta
 
 static inline int align_up(int x, int a) { return (x + a - 1) / a * a; }
 
-template <int W, int T, bool DIR, bool TAIL, bool MOL = false>
+template <int W, int T, bool DIR, bool TAIL, bool MOL = false, int CYC = 0>
 static int launch_d(CountArgs &a, int n_items, size_t lds, hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&count_kernel<W, T, DIR, TAIL, MOL>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&count_kernel<W, T, DIR, TAIL, MOL, CYC>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
-    hipLaunchKernelGGL((count_kernel<W, T, DIR, TAIL, MOL>), dim3((unsigned)n_items), dim3(T), lds, stream, a);
+    hipLaunchKernelGGL((count_kernel<W, T, DIR, TAIL, MOL, CYC>), dim3((unsigned)n_items), dim3(T), lds, stream, a);
     e = hipGetLastError();
     if (e != hipSuccess) return set_error(GSN_E_HIP, "count_kernel launch: %s", hipGetErrorString(e));
 #ifdef COUNT_PROF
@@ -989,7 +1029,7 @@ static int launch_d(CountArgs &a, int n_items, size_t lds, hipStream_t stream) {
             unsigned long long *buf2 = buf + (size_t)n_items * 16 - 16;      // (the last item's slots 16..: its own row is read first)
             (void)hipMalloc(&buf2, 128); (void)hipMemset(buf2, 0, 128);
             (void)hipMemcpyToSymbol(HIP_SYMBOL(g_count_prof2), &buf2, sizeof(buf2));
-            hipLaunchKernelGGL((count_kernel<W, T, DIR, TAIL, MOL>), dim3((unsigned)n_items), dim3(T), lds, stream, a);
+            hipLaunchKernelGGL((count_kernel<W, T, DIR, TAIL, MOL, CYC>), dim3((unsigned)n_items), dim3(T), lds, stream, a);
             (void)hipStreamSynchronize(stream);
             unsigned long long *h = new unsigned long long[(size_t)n_items * 16];
             (void)hipMemcpy(h, buf, (size_t)n_items * 128, hipMemcpyDeviceToHost);
@@ -1002,7 +1042,7 @@ static int launch_d(CountArgs &a, int n_items, size_t lds, hipStream_t stream) {
             }
             fprintf(stderr, "countprof pool: %.1f loop trips per workgroup (wave 0), %.1f lanes of 64 inside a search per trip; cycles per workgroup in the arms: pull %.0f begin %.0f step %.0f finish %.0f\n",
                     it_sum / n_items, it_sum > 0 ? ln_sum / it_sum : 0.0, arm[0] / n_items, arm[1] / n_items, arm[2] / n_items, arm[3] / n_items);
-            fprintf(stderr, "countprof W %d T %d items %d: cycles per workgroup: clear+plan %.0f adjacency %.0f cores %.0f balls %.0f edge ranks %.0f task pool %.0f write %.0f\n", W, T, n_items,
+            fprintf(stderr, "countprof W %d T %d cycle walk %d items %d: cycles per workgroup: clear+plan %.0f adjacency %.0f cores %.0f balls %.0f edge ranks %.0f task pool %.0f write %.0f\n", W, T, CYC, n_items,
                     s[0] / n_items, s[1] / n_items, s[2] / n_items, s[3] / n_items, s[4] / n_items, s[5] / n_items, s[6] / n_items);
             delete[] h;
             {
@@ -1035,15 +1075,17 @@ static int launch(CountArgs &a, int n_items, size_t lds, hipStream_t stream) {
         if (a.off_ain >= 0) return tail ? launch_d<W, T, true, true>(a, n_items, lds, stream) : launch_d<W, T, true, false>(a, n_items, lds, stream);
         if constexpr (T == 64) {
 #ifdef COUNT_PROF
-            static const bool mol_on = false;           // (the phase profile is read from the generic instantiation)
+            static const bool mol_on = false;           // (the phase profile is read from the generic instantiation, or from the cycle one)
 #else
             static const bool mol_on = [] { const char *d = getenv("GSN_COUNT_MOL"); return !d || atoi(d) != 0; }();
 #endif
             const bool mol = mol_on && !tail && a.mode == GSN_MODE_EDGE && a.sym && a.n_cols == 4 && a.pair && a.split == 1 && a.enc_out &&
                              a.enc_stage && !a.graph_ids;
             if (getenv("GSN_CHAIN_TRACE"))
-                fprintf(stderr, "gsn count: molecule instantiation %d (tail %d mode %d sym %d cols %d pair %d split %d stage %d out %d enc %d enc_stage %d ids %d)\n", (int)mol, (int)tail,
-                        a.mode, a.sym, a.n_cols, a.pair, a.split, a.stage_out, a.out != nullptr, a.enc_out != nullptr, a.enc_stage, a.graph_ids != nullptr);
+                fprintf(stderr, "gsn count: molecule instantiation %d cycle walk %d (tail %d mode %d sym %d cols %d pair %d split %d stage %d out %d enc %d enc_stage %d ids %d)\n", (int)mol,
+                        (int)(a.cyc_len != 0), (int)tail, a.mode, a.sym, a.n_cols, a.pair, a.split, a.stage_out, a.out != nullptr, a.enc_out != nullptr, a.enc_stage, a.graph_ids != nullptr);
+            // every column a cycle of length <= 6 (count_launch: the launch's LDS was laid out for it, under these very conditions): the walk
+            if (a.cyc_len) return launch_d<1, 64, false, false, true, 6>(a, n_items, lds, stream);
             if (mol) {
                 hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&count_kernel_mol), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                 if (e != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
@@ -1182,6 +1224,38 @@ static int count_launch(const uint32_t *plan_host, const uint32_t *plan_dev, int
     const int64_t rows_cap_u = edge_mode ? max_edges : max_nodes;      // (of what a workgroup holds: a graph, or the union of two)
     a.n_cap = (int)max_nodes; a.e_cap = (int)max_edges;
 
+    // degree planes only when a plan ends in a chain (patterns.cpp: plan_tail_mode == 3): cycles, cliques -- the molecule workloads -- do not
+    a.off_degp = -1; a.degp_mask = 0; a.any_tail = 0;
+    for (int p = 0; p < a.n_plans; ++p) {
+        const uint32_t *w = plan_host + a.plans_off + (int64_t)p * a.stride;
+        if (plan_tail(w)) a.any_tail = 1;
+        if (plan_tail(w) == 3) a.degp_mask |= 1 << plan_core(w);
+    }
+    // one-word graphs: the tight loop over the images of level k - 2 pays where those sets are long -- dense graphs (average degree >= 8 by
+    // the caller's capacities: clique-rich ego networks 1.81 -> 0.96 ms per 1000, 12-regular n = 25 +5 %), not molecules (ZINC 0.073 ->
+    // 0.082 ms with it).  GSN_COUNT_TAIL_LOOP=0 / 1 forces it off / on.
+    a.tail_loop = 0;
+    if (W == 1) {
+        static const int forced = [] { const char *e = getenv("GSN_COUNT_TAIL_LOOP"); return e ? atoi(e) : -1; }();
+        a.tail_loop = forced >= 0 ? (forced != 0) : ((int64_t)a.e_decl >= 8 * (int64_t)a.n_decl);     // (the caller's capacities, before pairing)
+    }
+    // Cycle columns (count_core.h: cycle_plan_lengths / cycle_walk): a launch that meets the molecule instantiation's conditions (launch<>())
+    // and whose four columns are all non-induced cycles of length <= 6 counts by path walks -- no candidate stack, plan table or distance
+    // tables in its LDS.  Longer cycles (7, 8) keep the interpreter.  GSN_COUNT_CYCLE=0 sends such a launch down the interpreter.
+    a.cyc_len = 0;
+    if (W == 1 && T == 64 && pair && edge_mode && a.sym && !directed && a.n_cols == 4 && enc_out && enc_bytes && !a.any_tail && !a.tail_loop) {
+        static const bool cyc_on = [] { const char *d = getenv("GSN_COUNT_CYCLE"); return !d || atoi(d) != 0; }();
+#ifdef COUNT_PROF
+        static const bool mol_on = true;
+#else
+        static const bool mol_on = [] { const char *d = getenv("GSN_COUNT_MOL"); return !d || atoi(d) != 0; }();
+#endif
+        uint8_t len[4];
+        const int lmax = (cyc_on && mol_on) ? cycle_plan_lengths(plan_host, plan_words, len, 4) : 0;
+        if (lmax >= 3 && lmax <= 6) a.cyc_len = (unsigned)len[0] | ((unsigned)len[1] << 8) | ((unsigned)len[2] << 16) | ((unsigned)len[3] << 24);
+    }
+    const bool cyc = a.cyc_len != 0;
+
     int o = align_up((int)max_nodes * W * 8, 16);
     a.off_ain = -1;
     if (directed) { a.off_ain = o; o += align_up((int)max_nodes * W * 8, 16); }
@@ -1195,8 +1269,8 @@ static int count_launch(const uint32_t *plan_host, const uint32_t *plan_dev, int
     // (W >= 2: levels k - 2 and k - 1 never get a frame -- count_core.h counts them in closed form or in tail_loop)
     const int last_frame = W >= 2 ? a.kmax - 2 : a.kmax - 1;
     const int depth = last_frame - nfix_min > 1 ? last_frame - nfix_min : 1;
-    a.off_stack = o; o += depth * W * T * 8;
-    a.off_plan = o; o += align_up((int)plan_words * 4, 16);
+    a.off_stack = o; o += cyc ? 0 : depth * W * T * 8;
+    a.off_plan = o; o += cyc ? 0 : align_up((int)plan_words * 4, 16);
     const int vid_bytes = W > 4 ? 2 : 1;
     a.off_eu = o; o += edge_mode ? align_up((int)max_edges * vid_bytes, 16) : 0;
     a.off_ev = o; o += edge_mode ? align_up((int)max_edges * vid_bytes, 16) : 0;
@@ -1213,23 +1287,8 @@ static int count_launch(const uint32_t *plan_host, const uint32_t *plan_dev, int
     // pruning tables only for graphs of <= 64 vertices (molecules): on larger, denser targets the balls are (nearly)
     // everything and the extra AND per step costs more than it saves (measured: ER G(128,1000) +8 %)
     a.off_ball = -1;
-    if (W == 1 && a.kmax >= 4 && !directed) { a.off_ball = o; o += align_up(2 * (int)max_nodes * W * 8, 16); }
-    // degree planes only when a plan ends in a chain (patterns.cpp: plan_tail_mode == 3): cycles, cliques -- the molecule workloads -- do not
-    a.off_degp = -1; a.degp_mask = 0; a.any_tail = 0;
-    for (int p = 0; p < a.n_plans; ++p) {
-        const uint32_t *w = plan_host + a.plans_off + (int64_t)p * a.stride;
-        if (plan_tail(w)) a.any_tail = 1;
-        if (plan_tail(w) == 3) a.degp_mask |= 1 << plan_core(w);
-    }
+    if (W == 1 && a.kmax >= 4 && !directed && !cyc) { a.off_ball = o; o += align_up(2 * (int)max_nodes * W * 8, 16); }
     if (a.degp_mask) { a.off_degp = o; o += align_up((CORE_MAX + 1) * DEG_PLANES * W * 8, 16); }
-    // one-word graphs: the tight loop over the images of level k - 2 pays where those sets are long -- dense graphs (average degree >= 8 by
-    // the caller's capacities: clique-rich ego networks 1.81 -> 0.96 ms per 1000, 12-regular n = 25 +5 %), not molecules (ZINC 0.073 ->
-    // 0.082 ms with it).  GSN_COUNT_TAIL_LOOP=0 / 1 forces it off / on.
-    a.tail_loop = 0;
-    if (W == 1) {
-        static const int forced = [] { const char *e = getenv("GSN_COUNT_TAIL_LOOP"); return e ? atoi(e) : -1; }();
-        a.tail_loop = forced >= 0 ? (forced != 0) : ((int64_t)a.e_decl >= 8 * (int64_t)a.n_decl);     // (the caller's capacities, before pairing)
-    }
     a.off_out = o;
     const int64_t stage_bytes = align_up((int)(rows_cap_u * a.n_cols * 2 < ((int64_t)1 << 28) ? rows_cap_u * a.n_cols * 2 : ((int64_t)1 << 28)), 16);      // (16-bit staged counts)
     // Stage the output rows in LDS (coalesced final write) only while that keeps the workgroup small: the search is
@@ -1270,6 +1329,8 @@ static int count_launch(const uint32_t *plan_host, const uint32_t *plan_dev, int
         if (need > o) o = align_up((int)need, 16);
     }
     if (o > 160 * 1024) return set_error(GSN_E_UNSUPPORTED, "graph too large for LDS (%d B needed)", o);
+    // (a pair of one-word graphs of <= 128 columns each: a few KiB, class indices in a byte -- always staged)
+    if (cyc && !(a.enc_stage && a.split == 1)) return set_error(GSN_E_UNSUPPORTED, "gsn_count_hip: cycle launch without staged class indices (%d B of LDS)", o);
     if (enc16 && !a.enc_stage)
         return set_error(GSN_E_UNSUPPORTED, "gsn_count_encode_pack16_hip: the fp16 rows are written from the staged class indices (one workgroup per graph, "
                                             "n_classes <= 255); pack the fp32 rows with gsn_pack16_rows_hip instead");

@@ -496,4 +496,82 @@ GSN_HD void lane_step(Lane<W> &s, const uint64_t *A, const uint64_t *valid, uint
     s.l = cl >= s.nfix ? cl : -1;
 }
 
+// ---- cycle columns of one-word graphs: bitset path walks instead of the plan interpreter ---------------------------------------
+// A non-induced k-cycle rooted at one of its arcs has no automorphism that fixes the arc, so its edge-mode identifier of row (u, v)
+// is the number of simple k-cycles through the edge {u, v} = the number of simple paths of k - 1 edges from v to u whose inner
+// vertices avoid u and v.  On a graph of <= 64 vertices (A[x] = the one-word adjacency row of x) one depth-first walk from v counts
+// the paths of every length 2 .. L - 1 at once: at a vertex reached by d edges, popc(A[x] & A[u] & ~used) closes the (d + 2)-cycles.
+// `mask` prunes the inner vertices (the 2-core: every vertex of a cycle lies in it; ~0 = no pruning -- it never changes the result).
+// cnt[k - 3] = the count for length k, k = 3 .. L.  L is a compile-time bound: the loops unroll, nothing but A is read from memory.
+template <int L, int D, class Acc>
+GSN_HD void cycle_walk_level(const uint64_t *A, const uint64_t au, const uint64_t mask, const int x, const uint64_t used, Acc *cnt) {
+    const uint64_t row = A[x] & ~used;
+    cnt[D] += (Acc)popc64(row & au);
+    if constexpr (D + 1 < L - 2) {
+        uint64_t m = row & mask;
+        while (m) {
+            const int y = ctz64(m);
+            m &= m - 1ull;
+            cycle_walk_level<L, D + 1, Acc>(A, au, mask, y, used | (1ull << y), cnt);
+        }
+    }
+}
+// (a path of <= 5 inner steps on 62 free vertices: 62 * 61 * 60 * 59 < 2^32 for L <= 6; 64-bit counters above)
+template <int L>
+struct CycleAcc { typedef uint64_t type; };
+template <> struct CycleAcc<3> { typedef uint32_t type; };
+template <> struct CycleAcc<4> { typedef uint32_t type; };
+template <> struct CycleAcc<5> { typedef uint32_t type; };
+template <> struct CycleAcc<6> { typedef uint32_t type; };
+template <int L>
+GSN_HD void cycle_walk(const uint64_t *A, const int u, const int v, const uint64_t mask, uint64_t *cnt /* [L - 2] */) {
+    static_assert(L >= 3 && L <= GSN_KMAX, "cycle lengths 3 .. GSN_KMAX");
+    typename CycleAcc<L>::type c[L - 2];
+#pragma unroll
+    for (int i = 0; i < L - 2; ++i) c[i] = 0;
+    cycle_walk_level<L, 0, typename CycleAcc<L>::type>(A, A[u] & mask, mask, v, (1ull << u) | (1ull << v), c);
+#pragma unroll
+    for (int i = 0; i < L - 2; ++i) cnt[i] = (uint64_t)c[i];
+}
+
+// Is this plan table a set of such columns?  Judged from the plans' structure, not from pattern names: edge mode, non-induced, undirected
+// orbit classes; every column has exactly one plan (a cycle has one arc orbit: a second plan would ADD to the column), rooted at an arc,
+// without non-adjacency or order masks, and the pattern rebuilt from its levels' adjacency masks plus the root edge is one cycle: k
+// vertices, k edges, every degree 2, connected.  len[c] = the cycle length of column c; returns the largest length, 0 = not recognised.
+inline int cycle_plan_lengths(const uint32_t *plan, int64_t plan_words, uint8_t *len, int len_cap) {
+    if (!plan || plan_words < PLAN_HEADER_WORDS || plan[0] != PLAN_MAGIC) return 0;
+    if (plan[1] != (uint32_t)GSN_MODE_EDGE || plan[2] != 0u || plan[6] != 0u) return 0;
+    const int n_plans = (int)plan[3], n_cols = (int)plan[4], plans_off = (int)plan[7];
+    if (n_cols < 1 || n_cols > len_cap || n_plans != n_cols || plan_words < plans_off + (int64_t)n_plans * PLAN_STRIDE_WORDS) return 0;
+    int lmax = 0;
+    for (int c = 0; c < n_cols; ++c) {
+        if (plan[PLAN_HEADER_WORDS + c] != (uint32_t)c) return 0;            // col_ptr: plan c is the one plan of column c
+        const uint32_t *w = plan + plans_off + c * PLAN_STRIDE_WORDS;
+        const int k = (int)(w[0] & 0xffu), nfix = (int)((w[0] >> 8) & 0xffu);
+        if (k < 3 || k > GSN_KMAX || nfix != 2 || (int)(w[0] >> 16) != c) return 0;
+        uint32_t nb[GSN_KMAX];
+        for (int l = 0; l < k; ++l) nb[l] = 0;
+        nb[0] |= 2u; nb[1] |= 1u;                                             // the root edge
+        for (int l = 0; l < k; ++l) {
+            if (w[2 + l] >> 8) return 0;                                      // non-adjacency (induced) or order (symmetry) constraints
+            const uint32_t adj = w[2 + l] & 0xffu;
+            if (adj >> l) return 0;                                           // (a level names earlier levels only)
+            for (int j = 0; j < l; ++j)
+                if ((adj >> j) & 1u) { nb[l] |= 1u << j; nb[j] |= 1u << l; }
+        }
+        for (int l = 0; l < k; ++l)
+            if (popc64(nb[l]) != 2) return 0;                                 // 2-regular: k vertices, k edges
+        uint32_t seen = 1u;                                                   // connected: one cycle, not several
+        for (int prev = 0, cur = ctz64(nb[0]), i = 1; i < k; ++i) {
+            if ((seen >> cur) & 1u) return 0;
+            seen |= 1u << cur;
+            const int nxt = ctz64(nb[cur] & ~(1u << prev));
+            prev = cur; cur = nxt;
+        }
+        len[c] = (uint8_t)k;
+        lmax = k > lmax ? k : lmax;
+    }
+    return lmax;
+}
+
 }  // namespace gsn
