@@ -46,6 +46,16 @@ __all__ = ["mlp", "central_encoder", "GSN_sparse", "GSN_edge_sparse", "MPNN_spar
            "global_add_pool_sparse", "global_mean_pool_sparse", "Codes", "run_linear_module", "invalidate_caches", "drop_input_caches", "drop_capture_caches", "set_graph_partition", "build_csr_graphs"]
 
 
+def _post_params(post):
+    """Parameters of ``post = (BatchNorm1d or None, activation name)``, the between-layer stage fused behind a module's last Linear."""
+    return list(post[0].parameters()) if (post is not None and post[0] is not None) else []
+
+
+def _post_agrees(post, module):
+    """Is the fused BatchNorm1d of ``post`` in the train / eval mode of the mlp ``module`` it rides on?"""
+    return post is None or post[0] is None or post[0].training == module.training
+
+
 class mlp(nn.Module):
     """models_misc.mlp (models_misc.py:18-59): Linear -> [BatchNorm1d] -> activation ... -> Linear, same attribute
     names (``fc``, ``bn``) so state dicts are interchangeable; forward runs on the HIP dense stages."""
@@ -85,7 +95,7 @@ class mlp(nn.Module):
 
     def hip_forward(self, blocks, m_rows, upto=None, first_weight=None, first_bias=None, csr=None, post=None):
         stages = self.stages(blocks, upto, first_weight, first_bias, post)
-        if post is not None and post[0] is not None and post[0].training != self.training:
+        if not _post_agrees(post, self):
             raise RuntimeError("mlp and the fused BatchNorm1d must be in the same train/eval mode")
         return run_stages(stages, m_rows, self.training, csr=csr)
 
@@ -115,10 +125,9 @@ class mlp(nn.Module):
             return run_stages_autograd(self.stages([(x, None)], post=post), x.shape[0], self.training)
         # eval mode: the fused forward; if a gradient is asked for after all, the stages are re-run on the kernels that keep what
         # their HIP adjoints need (no PyTorch twin: BatchNorm on running statistics is a per-column affine map there)
-        extra = list(post[0].parameters()) if (post is not None and post[0] is not None) else []
         again = (lambda x_: run_stages_autograd(self.stages([(x_, None)], post=post), x_.shape[0], self.training)) if native and not self.training \
             else (lambda x_: self.torch_forward(x_, post=post))
-        return _run(self, lambda: self.hip_forward([(x, None)], x.shape[0], post=post), again, [x], extra_params=extra,
+        return _run(self, lambda: self.hip_forward([(x, None)], x.shape[0], post=post), again, [x], extra_params=_post_params(post),
                     native=native and not self.training)
 
 
@@ -192,6 +201,60 @@ class central_encoder(nn.Module):
 # ------------------------------------------------------------------------------------------------------------------
 # the layers
 # ------------------------------------------------------------------------------------------------------------------
+class _MessageRow:
+    """The input row of a `general` layer's msg_fn, stated once:  x_i | x_j | ids (id_scope 'local') or ids_i | ids_j ('global') | ef
+    (GSN_sparse.py:166-171, GSN_edge_sparse.py:160-165).  ``node``: the inputs with one row per vertex, each read at both ends of an edge;
+    ``edge``: the inputs with one row per edge -- fp32 rows or Codes, whatever the caller of :meth:`_SparseLayer._row` holds."""
+    __slots__ = ("node", "edge")
+
+    def __init__(self, node, edge):
+        self.node, self.edge = node, edge
+
+    def blocks(self, i, j, e):
+        """[(rows, index)] in concatenation order: the per-vertex inputs through ``i`` (the aggregating end) and ``j``, the per-edge inputs
+        through ``e`` -- edge_index rows, sorted CSR indices, or the 0 / 1 / None gather modes of the training path."""
+        out = []
+        for t in self.node:
+            out += ((t, i), (t, j))
+        return out + [(t, e) for t in self.edge]      # (plain loops: this runs in front of every recorded launch)
+
+    def columns(self):
+        """[(first, end)]: the columns of msg_fn's first weight that multiply each block of :meth:`blocks`."""
+        ends = [0]
+        for t, _ in self.blocks(None, None, None):
+            ends.append(ends[-1] + t.shape[1])
+        return list(zip(ends[:-1], ends[1:]))
+
+
+class _Call:
+    """One forward of a `general` layer: the caller's tensors and, made on first use, what the routes of ``_hip`` share (fp32 rows, CSR)."""
+    __slots__ = ("layer", "edge_index", "raw", "n", "E", "sel", "post", "x", "_row", "_csr")
+
+    def __init__(self, layer, edge_index, raw, n, E, sel, post):
+        self.layer, self.edge_index, self.raw, self.n, self.E, self.sel, self.post = layer, edge_index, raw, n, E, sel, post
+        self.x = _f32c(_dense(raw[0]))
+        self._row = self._csr = None
+
+    def row(self):
+        if self._row is None:
+            self._row = self.layer._row(self.x, _dense(self.raw[1]), _dense(self.raw[2]))
+        return self._row
+
+    def csr(self):
+        if self._csr is None:
+            self._csr = _csr_for(self.edge_index, self.sel, self.n)
+        return self._csr
+
+    def sorted_blocks(self):
+        """rows in target-sorted order, every block gathered through ONE int32 index: the scatter-add can ride a kernel's epilogue"""
+        row, csr = self.row(), self.csr()
+        return row.blocks(csr.tgt, csr.src, csr.perm)
+
+    def coo_blocks(self):
+        """the same rows in the caller's edge order"""
+        return self.row().blocks(self.edge_index[self.sel].contiguous(), self.edge_index[1 - self.sel].contiguous(), None)
+
+
 class _SparseLayer(nn.Module):
     """Shared implementation; subclasses fix (has_ids, has_ef, ogb)."""
 
@@ -215,7 +278,6 @@ class _SparseLayer(nn.Module):
             d_in = d_in + d_degree if retain_features else d_degree
         d_id = d_id if self.has_ids else 0
         d_ef = d_ef if self.has_ef else 0
-        name = self.__class__.__name__
         if self.ogb:
             if msg_kind != "ogb":
                 raise NotImplementedError("msg kind {} is not currently supported.".format(msg_kind))
@@ -239,7 +301,6 @@ class _SparseLayer(nn.Module):
         else:
             raise NotImplementedError("msg kind {} is not currently supported.".format(msg_kind))
         self.update_fn = mlp(update_input_dim, d_up, d_h, seed, activation_name, bn)
-        del name
 
     def _init_eps(self, eps, train_eps):
         self.initial_eps = eps
@@ -255,9 +316,7 @@ class _SparseLayer(nn.Module):
         if self.degree_as_tag:
             x = _dense(x)
         degrees = kwargs["degrees"]
-        identifiers = kwargs["identifiers"] if self.has_ids or self.ogb else None
-        if not self.has_ids:
-            identifiers = None
+        identifiers = kwargs["identifiers"] if self.has_ids else None
         if degrees is not None:
             degrees = degrees.unsqueeze(-1) if degrees.dim() == 1 else degrees
         if self.degree_as_tag:
@@ -309,59 +368,56 @@ class _SparseLayer(nn.Module):
             ts = list(ts)
             return tuple(None if t is None else (t.dense() if isinstance(t, Codes) else ts.pop(0)) for t in given)
 
-        if torch.is_grad_enabled() and flags.NATIVE_DENSE_BACKWARD and self.training:
-            # training: compositions of kernels that each have a HIP adjoint -- no PyTorch twin
+        def native(x_, ids_, ef_):      # the layer as a composition of kernels that each have a HIP adjoint -- no PyTorch twin
             if self.ogb or self.msg_kind == "gin":   # propagate -> axpy -> update_fn
-                return self._twin(edge_index, _dense(x), _dense(ids), _dense(ef), post=post, native=True)
-            if self._general_native_ok():
-                return self._general_train(edge_index, _dense(x), _dense(ids), _dense(ef), post)
-        extra = list(post[0].parameters()) if (post is not None and post[0] is not None) else []
+                return self._twin(edge_index, x_, ids_, ef_, post=post, native=True)
+            return self._general_train(edge_index, x_, ids_, ef_, post)
+
+        if torch.is_grad_enabled() and flags.NATIVE_DENSE_BACKWARD and self.training:
+            return native(_dense(x), _dense(ids), _dense(ef))
+        hip = lambda: self._hip(edge_index, x, ids, ef, post)
         if flags.NATIVE_DENSE_BACKWARD and not self.training:
-            # eval mode: the fused forward keeps nothing; a gradient asked for after all re-runs the layer as the composition of kernels
-            # that have HIP adjoints (the train-mode paths above; every BatchNorm1d in eval mode is an affine map there) -- no twin
-            if self.ogb or self.msg_kind == "gin":
-                again = lambda *ts: self._twin(edge_index, *unpack(ts), post=post, native=True)
-            else:
-                again = lambda *ts: self._general_train(edge_index, *unpack(ts), post)
-            return _run(self, lambda: self._hip(edge_index, x, ids, ef, post), again, inputs, extra_params=extra, native=True)
-        return _run(self, lambda: self._hip(edge_index, x, ids, ef, post), lambda *ts: self._twin(edge_index, *unpack(ts), post=post), inputs,
-                    extra_params=extra)
+            # eval mode: the fused forward keeps nothing; a gradient asked for after all re-runs the layer as that composition
+            return _run(self, hip, lambda *ts: native(*unpack(ts)), inputs, extra_params=_post_params(post), native=True)
+        return _run(self, hip, lambda *ts: self._twin(edge_index, *unpack(ts), post=post), inputs, extra_params=_post_params(post))
 
     # -- message blocks ------------------------------------------------------------------------------------------
     def _sel(self):
         return 0 if self.flow == "target_to_source" else 1
 
-    def _gin_parts(self, x, ids, ef, n):
-        """(self parts, neighbour ids, neighbour ef, ids per node?) for the gin formulation"""
-        self_parts = [x]
-        ids_nb, ids_per_node = None, False
-        if self.has_ids:
-            if self.id_scope == "global":
-                self_parts.append(ids); ids_nb, ids_per_node = ids, True
-            else:
-                c, ids_nb = self.central_node_id_encoder(ids, n)
-                self_parts.append(c)
-        ef_nb = None
+    def _ids_per_node(self):
+        """identifiers with one row per vertex (id_scope 'global', GSN-v) rather than one per edge ('local', GSN-e)"""
+        return self.has_ids and self.id_scope != "local"
+
+    def _per_edge(self, ids, ef):
+        """Which of the inputs have one row per edge, in the order of the message row."""
+        edge = [ids] if (self.has_ids and not self._ids_per_node()) else []
         if self.has_ef:
-            c, ef_nb = self.central_node_edge_encoder(ef, n)
-            self_parts.append(c)
-        return self_parts, ids_nb, ef_nb, ids_per_node
+            edge.append(ef)
+        return edge
+
+    def _row(self, x, ids, ef):
+        """The message row of this layer over the given inputs (see _MessageRow)."""
+        return _MessageRow([x, ids] if self._ids_per_node() else [x], self._per_edge(ids, ef))
+
+    def _one_launch_shape(self):
+        """The layers the one-launch kernels are written for (widths, activations, BatchNorm mode: gsn_layer_fused*_supported answers)."""
+        return not self.ogb and self.msg_kind == "general" and len(self.msg_fn.fc) == 2 and not self._ids_per_node()
 
     def _self_plus_messages(self, edge_index, x, ids, ef):
         """(1 + eps) * self + sum of messages of the gin / ogb layers in ONE pass of the propagate kernel (forward: no elementwise
         tensor op, no concatenation; GSN_sparse.py:157-163, GSN_edge_sparse.py:95-109, GSN_edge_sparse_ogb.py:63-84 / :103-106)."""
         n, sel = x.shape[0], self._sel()
+        per_node = self._ids_per_node()
         if self.ogb:
-            per_node = self.has_ids and self.id_scope == "global"
             return propagate(1, edge_index, sel, n, a=x, b=ids if self.has_ids else None, c=ef, b_per_node=per_node,
                              selfs=[x, ids] if per_node else [x], eps=self.eps)
-        selfs, ids_nb, ef_nb, per_node, pads = [x], None, None, False, [0, 0]
-        if self.has_ids:
-            if self.id_scope == "global":
-                selfs.append(ids); ids_nb, per_node = ids, True
-            else:
-                row, pads[0] = self.central_node_id_encoder.central_row(x.device)
-                selfs.append(row); ids_nb = ids
+        selfs, ids_nb, ef_nb, pads = [x], None, None, [0, 0]
+        if per_node:
+            selfs.append(ids); ids_nb = ids
+        elif self.has_ids:
+            row, pads[0] = self.central_node_id_encoder.central_row(x.device)
+            selfs.append(row); ids_nb = ids
         if self.has_ef:
             row, pad = self.central_node_edge_encoder.central_row(x.device)
             selfs.append(row); ef_nb = ef
@@ -401,20 +457,13 @@ class _SparseLayer(nn.Module):
         """Second and later eval forwards of a `general` layer: the launch recorded by the first one with this call's pointers -- no stage
         lists, no BatchNorm resolution, no descriptor building (at the reference's batch sizes that Python was 3-4 x the kernel's time:
         models_graph_classification.py:204-247 calls four layers per forward).  None: no valid record (first call, a parameter moved, other
-        input kinds), or this batch is outside the recorded kernel -- the caller takes the full path, which records again."""
-        plan = getattr(self, "_fplan", None)
-        if plan is None or E == 0 or self.training or torch.cuda.is_current_stream_capturing():
+        input kinds), or this batch is outside the recorded kernel -- the next routes take the call, and record again."""
+        plan, key = getattr(self, "_fplan", None), self._fplan_record
+        if plan is None or E == 0 or key is None or plan[0] != key or torch.cuda.is_current_stream_capturing():
             return None
-        key = self._fplan_key(raw, post)
-        if key is None or plan[0] != key:
-            return None
-        x, ids, ef = raw
-        per_edge = [t for t in (ids if self.has_ids else None, ef if self.has_ef else None) if t is not None]
+        x, per_edge = raw[0], self._per_edge(raw[1], raw[2])
         if plan[1] == "pack16":
-            if isinstance(x, Codes):
-                pk = packs.from_codes(x, per_edge)
-            else:
-                pk = packs.lookup(x, per_edge)
+            pk = packs.from_codes(x, per_edge) if isinstance(x, Codes) else packs.lookup(x, per_edge)
             if pk is None:
                 return None
             csr = _csr_for(edge_index, sel, n)
@@ -426,118 +475,100 @@ class _SparseLayer(nn.Module):
             if isinstance(x, Codes) or x.dtype != torch.float32 or not x.is_contiguous():
                 return None
             csr = _csr_for(edge_index, sel, n)
-            blocks = [(x, csr.tgt), (x, csr.src)]
+            rows = []
             for t in per_edge:
-                if isinstance(t, Codes):
-                    t = t.dense()
+                t = _dense(t)
                 if t.dtype != torch.float32 or not t.is_contiguous():
                     return None
-                blocks.append((t, csr.perm))
-            return plan[2](x, csr, blocks)
+                rows.append(t)
+            return plan[2](x, csr, _MessageRow([x], rows).blocks(csr.tgt, csr.src, csr.perm))
         return None
 
     # -- HIP forward ---------------------------------------------------------------------------------------------
     def _hip(self, edge_index, x, ids, ef, post=None):
-        n = x.shape[0]
-        sel = self._sel()
-        E = edge_index.shape[1]
-        raw = (x, ids, ef)
-        record = None
-        if (flags.FUSED_LAYER and not self.training and not self.ogb and self.msg_kind == "general" and len(self.msg_fn.fc) == 2
-                and not (self.has_ids and self.id_scope != "local")):
-            y = self._hip_recorded(edge_index, raw, n, E, sel, post)
-            if y is not None:
-                return y
-            record = self._fplan_key(raw, post)
-        self._fplan_record = record
-        use_codes = (not self.ogb and self.msg_kind == "general" and len(self.msg_fn.fc) == 2 and E > 0
-                     and all(isinstance(t, Codes) for t in raw if t is not None))
-        # integer codes in, one launch: the one-hot encodings go straight into exact fp16 row packs (gsn_one_hot_pack16_hip: 64 / 32 bytes
-        # per row, no fp32 one-hot tensor at all) and the layer runs on them (csrc/layer_rp.hip).  Identifiers may also be the tagged rows
-        # of the counting kernel (gsn_amd.counting.count_batch(encoded_pack=...)).
-        if (flags.PACK16_LAYER and flags.FUSED_LAYER and isinstance(raw[0], Codes) and not self.ogb and self.msg_kind == "general" and len(self.msg_fn.fc) == 2
-                and E > 0 and not self.training and not (self.has_ids and self.id_scope != "local")
-                and (raw[2] is None or isinstance(raw[2], Codes)) and (raw[1] is None or isinstance(raw[1], (Codes, torch.Tensor)))):
-            y = self._fused_on_code_packs(edge_index, raw, n, E, sel, post)
-            if y is not None:
-                return y
-        x = _f32c(_dense(x))
-        if not use_codes:
-            ids, ef = _dense(ids), _dense(ef)
         if self.ogb or self.msg_kind == "gin":
-            xin = self._self_plus_messages(edge_index, x, ids, ef)
-            return self.update_fn.hip_forward([(xin, None)], n, post=post)
-        # general
-        idx_i, idx_j = edge_index[sel].contiguous(), edge_index[1 - sel].contiguous()
-        blocks = [(x, idx_i), (x, idx_j)]
-        if self.has_ids:
-            blocks += [(ids, None)] if self.id_scope == "local" else [(ids, idx_i), (ids, idx_j)]
-        if self.has_ef:
-            blocks.append((ef, None))
-        mf = self.msg_fn
-        uf = self.update_fn
-        if len(mf.fc) >= 2:
-            # all stages but the last Linear of msg_fn on E rows, then the sum aggregation S = sum_e r_e; the last Linear
-            # commutes with the sum:  agg = W2 S + deg*b2, and it feeds update_fn's first Linear (weights [W3x | W3a]):
-            #     [x | agg] W3^T = x W3x^T + S (W3a W2)^T + deg (W3a b2)^T
-            # so it is folded into that Linear's weight (a [d_h x d_msg] by [d_msg x d_h] product, once per call).
-            csr = _csr_for(edge_index, sel, n)
-            s_agg = None
-            if use_codes:
-                # every input of msg_fn's first Linear is a one-hot code column: weight-row gather, no dense one-hot
-                cblocks = [(raw[0], csr.tgt), (raw[0], csr.src)]
-                if self.has_ids:
-                    cblocks += [(raw[1], csr.perm)] if self.id_scope == "local" else [(raw[1], csr.tgt), (raw[1], csr.src)]
-                if self.has_ef:
-                    cblocks.append((raw[2], csr.perm))
-                s_agg = _code_stage_segsum(mf, cblocks, csr, E)
-                if s_agg is None:
-                    ids, ef = _dense(ids), _dense(ef)
-                    blocks = [(x, idx_i), (x, idx_j)]
-                    if self.has_ids:
-                        blocks += [(ids, None)] if self.id_scope == "local" else [(ids, idx_i), (ids, idx_j)]
-                    if self.has_ef:
-                        blocks.append((ef, None))
-            # fused path: rows walked in target-sorted order; every block is gathered through ONE int32 index
-            # (x_i: sorted target, x_j: sorted source, per-edge rows: perm), the scatter-add happens in the epilogue
-            if s_agg is None and E > 0:
-                sblocks = [(x, csr.tgt), (x, csr.src)]
-                if self.has_ids:
-                    sblocks += [(ids, csr.perm)] if self.id_scope == "local" else [(ids, csr.tgt), (ids, csr.src)]
-                if self.has_ef:
-                    sblocks.append((ef, csr.perm))
-                # the whole layer in one launch where it fits (eval-mode BatchNorm, K_edge <= 80, widths <= 128)
-                if post is None or post[0] is None or post[0].training == uf.training:
-                    pk = None
-                    if flags.PACK16_LAYER and not (self.has_ids and self.id_scope != "local"):
-                        # exact fp16 packs of the inputs, when their producers left them (gsn_amd.packs): looked up on the caller's tensors
-                        pk = packs.lookup(raw[0], [t for t in (raw[1] if self.has_ids else None, raw[2] if self.has_ef else None) if t is not None])
-                    y = _layer_fused(x, csr, mf.stages(sblocks, upto=len(mf.fc) - 1),
-                                     uf.stages([(x, None)], first_weight=self._folded_first_weight(x.shape[1]), post=post),
-                                     self.training, owner=self, gen=getattr(self, "_fold_gen", 0), pack16=pk, record=self._fplan_record)
-                    if y is not None:
-                        return y
-                # wide edge rows (K > 160: layers 1.. of a d = 128 model, K = 260): the node part of the Linear once per NODE,
-                # the rest as a gather-add inside the scatter kernel
-                s_agg = self._split_edge_stage(x, ids, ef, csr, n, E)
-                if s_agg is None:
-                    s_agg = mf.hip_forward(sblocks, E, upto=len(mf.fc) - 1, csr=csr)
-            if s_agg is None:
-                r = mf.hip_forward(blocks, E, upto=len(mf.fc) - 1)
-                s_agg = propagate(0, edge_index, sel, n, b=r)
-            w_first = self._folded_first_weight(x.shape[1])
-            return uf.hip_forward([(x, None), (s_agg, None), (csr.deg4, None)], n, first_weight=w_first, post=post)
-        msgs = mf.hip_forward(blocks, E)
-        agg = propagate(0, edge_index, sel, n, b=msgs)
-        return uf.hip_forward([(x, None), (agg, None)], n, post=post)
+            self._fplan_record = None
+            x = _f32c(_dense(x))
+            xin = self._self_plus_messages(edge_index, x, _dense(ids), _dense(ef))
+            return self.update_fn.hip_forward([(xin, None)], x.shape[0], post=post)
+        raw, n, E, sel = (x, ids, ef), x.shape[0], edge_index.shape[1], self._sel()
+        one_launch = flags.FUSED_LAYER and not self.training and self._one_launch_shape()
+        # (what a one-launch kernel records its launch under; a plain attribute, set past nn.Module's bookkeeping: this runs per forward)
+        object.__setattr__(self, "_fplan_record", self._fplan_key(raw, post) if one_launch else None)
+        if one_launch:      # the whole layer in one launch, straight from the caller's tensors
+            for route in self._FROM_CALLER:
+                y = route(self, edge_index, raw, n, E, sel, post)
+                if y is not None:
+                    return y
+        c = _Call(self, edge_index, raw, n, E, sel, post)
+        mf, uf = self.msg_fn, self.update_fn
+        if len(mf.fc) < 2:      # a single Linear as msg_fn: nothing to fold (GSN_sparse.py:166-171 with d_h = [])
+            msgs = mf.hip_forward(c.coo_blocks(), E)
+            agg = propagate(0, edge_index, sel, n, b=msgs)
+            return uf.hip_forward([(c.x, None), (agg, None)], n, post=post)
+        # all stages but the last Linear of msg_fn on E rows, then the sum aggregation S = sum_e r_e; the last Linear
+        # commutes with the sum:  agg = W2 S + deg*b2, and it feeds update_fn's first Linear (weights [W3x | W3a]):
+        #     [x | agg] W3^T = x W3x^T + S (W3a W2)^T + deg (W3a b2)^T
+        # so it is folded into that Linear's weight (a [d_h x d_msg] by [d_msg x d_h] product, once per call).
+        # The routes in order, each None when it declines: to S, or (the one-launch kernel) to the layer's rows themselves
+        for route, gives_sum in self._ON_ROWS:
+            out = route(self, c)
+            if out is not None:
+                break
+        if not gives_sum:
+            return out
+        return uf.hip_forward([(c.x, None), (out, None), (c.csr().deg4, None)], n, first_weight=self._folded_first_weight(c.x.shape[1]), post=post)
 
+    def _route_code_packs(self, edge_index, raw, n, E, sel, post):
+        """integer codes in: straight into exact fp16 row packs (no fp32 one-hot tensor at all), the layer in one launch on them (layer_rp.hip)"""
+        if not (flags.PACK16_LAYER and isinstance(raw[0], Codes) and E > 0 and (raw[2] is None or isinstance(raw[2], Codes))):
+            return None
+        return self._fused_on_code_packs(edge_index, raw, n, E, sel, post)
+
+    def _route_code_stage(self, c):
+        """every input of msg_fn's first Linear is a one-hot code column: weight-row gather, no dense one-hot"""
+        if len(self.msg_fn.fc) != 2 or c.E == 0 or not all(isinstance(t, Codes) for t in c.raw if t is not None):
+            return None
+        csr = c.csr()
+        return _code_stage_segsum(self.msg_fn, self._row(*c.raw).blocks(csr.tgt, csr.src, csr.perm), csr, c.E)
+
+    def _route_one_launch(self, c):
+        """the whole layer in one launch where it fits (eval-mode BatchNorm, K_edge <= 80, widths <= 128)"""
+        mf, uf = self.msg_fn, self.update_fn
+        if c.E == 0 or not _post_agrees(c.post, uf):
+            return None
+        sblocks = c.sorted_blocks()
+        # exact fp16 packs of the inputs, when their producers left them (gsn_amd.packs): looked up on the caller's tensors
+        pk = packs.lookup(c.raw[0], self._per_edge(c.raw[1], c.raw[2])) if (flags.PACK16_LAYER and not self._ids_per_node()) else None
+        return _layer_fused(c.x, c.csr(), mf.stages(sblocks, upto=len(mf.fc) - 1),
+                            uf.stages([(c.x, None)], first_weight=self._folded_first_weight(c.x.shape[1]), post=c.post),
+                            self.training, owner=self, gen=getattr(self, "_fold_gen", 0), pack16=pk, record=self._fplan_record)
+
+    def _route_split_edge(self, c):
+        """wide edge rows (K > 160: layers 1.. of a d = 128 model, K = 260): the node part of the Linear once per NODE (_split_edge_stage)"""
+        return self._split_edge_stage(c.x, _dense(c.raw[1]), _dense(c.raw[2]), c.csr(), c.n, c.E) if c.E else None
+
+    def _route_chain_segsum(self, c):
+        """the chain kernel with the scatter-add in its epilogue"""
+        return self.msg_fn.hip_forward(c.sorted_blocks(), c.E, upto=len(self.msg_fn.fc) - 1, csr=c.csr()) if c.E else None
+
+    def _route_materialised(self, c):
+        """edge rows written out, then the stand-alone scatter-add; never declines (an edge-less batch: zero rows, zero sums)"""
+        blocks = c.coo_blocks()
+        c.csr()     # (built in front of the stages, and for an edge-less batch too: the tail reads csr.deg4)
+        r = self.msg_fn.hip_forward(blocks, c.E, upto=len(self.msg_fn.fc) - 1)
+        return propagate(0, c.edge_index, c.sel, c.n, b=r)
+
+    _FROM_CALLER = (_hip_recorded, _route_code_packs)
+    _ON_ROWS = ((_route_code_stage, True), (_route_one_launch, False), (_route_split_edge, True), (_route_chain_segsum, True),
+                (_route_materialised, True))       # (route, does it give the sum S rather than the layer's rows?)
 
     def _fused_on_code_packs(self, edge_index, raw, n, E, sel, post):
-        """The one-launch layer fed from integer codes (see _hip); None when the shapes are outside the packed-row kernel."""
+        """The one-launch layer fed from integer codes (see _route_code_packs); None when the shapes are outside the packed-row kernel."""
         mf, uf = self.msg_fn, self.update_fn
-        if post is not None and post[0] is not None and post[0].training != uf.training:
+        if not _post_agrees(post, uf):
             return None
-        per_edge = [t for t in (raw[1] if self.has_ids else None, raw[2] if self.has_ef else None) if t is not None]
+        per_edge = self._per_edge(raw[1], raw[2])
         d_x = sum(raw[0].n_classes)
         if d_x > packs.NODE_COLS - 4 or sum(packs._width(t) for t in per_edge) > packs.EDGE_COLS:
             return None
@@ -548,36 +579,23 @@ class _SparseLayer(nn.Module):
         dev = edge_index.device
         # (shapes and block identities for the stage descriptors: the packed-row kernel does not read the fp32 pointers -- no kernel runs here)
         xph = torch.empty((n, d_x), dtype=torch.float32, device=dev)
-        sblocks = [(xph, csr.tgt), (xph, csr.src)]
-        for t in per_edge:
-            sblocks.append((t if isinstance(t, torch.Tensor) else torch.empty((E, packs._width(t)), dtype=torch.float32, device=dev), csr.perm))
-        return _layer_fused(xph, csr, mf.stages(sblocks, upto=len(mf.fc) - 1),
+        eph = [t if isinstance(t, torch.Tensor) else torch.empty((E, packs._width(t)), dtype=torch.float32, device=dev) for t in per_edge]
+        return _layer_fused(xph, csr, mf.stages(_MessageRow([xph], eph).blocks(csr.tgt, csr.src, csr.perm), upto=len(mf.fc) - 1),
                             uf.stages([(xph, None)], first_weight=self._folded_first_weight(d_x), post=post),
                             self.training, owner=self, gen=getattr(self, "_fold_gen", 0), pack16=pk, pack_only=True, record=self._fplan_record)
 
     # -- differentiable `general` path on native adjoints ------------------------------------------------------------------
-    def _general_native_ok(self):
-        return self.training
-
     def _general_train(self, edge_index, x, ids, ef, post):
         """msg_fn's hidden stages on materialised edge rows -> sum per target -> [x | S | deg] through update_fn with the
         folded first weight (the fold itself is three tiny PyTorch matrix products, so it stays differentiable)."""
-        n, sel = x.shape[0], self._sel()
-        E = edge_index.shape[1]
-        tensors, modes = [x, x], [sel, 1 - sel]
-        if self.has_ids:
-            if self.id_scope == "local":
-                tensors.append(ids); modes.append(None)
-            else:
-                tensors += [ids, ids]; modes += [sel, 1 - sel]
-        if self.has_ef:
-            tensors.append(ef); modes.append(None)
+        n, E, sel = x.shape[0], edge_index.shape[1], self._sel()
+        tensors, modes = zip(*self._row(x, ids, ef).blocks(sel, 1 - sel, None))
         mf, uf = self.msg_fn, self.update_fn
         # (an edge-less batch walks the same graph with zero rows: every parameter and input then gets the ZERO gradient PyTorch gives it)
         # the edge rows cat(x_i, x_j, ids.., e) are read where they lie (gathered blocks), by the product and by its weight gradient
-        eblocks, gather = [(t, None) for t in tensors], (edge_index, n, tuple(modes))
+        eblocks, gather = [(t, None) for t in tensors], (edge_index, n, modes)
         if flags.GATHER_CAT_TRAIN or len(tensors) > _MAX_BLOCKS:      # (the assembled-rows form: A/B switch)
-            eblocks, gather = [(_GatherCatFn.apply(edge_index, n, tuple(modes), *tensors), None)], None
+            eblocks, gather = [(_GatherCatFn.apply(edge_index, n, modes, *tensors), None)], None
         if len(mf.fc) < 2:      # a single Linear as msg_fn: nothing to fold (GSN_sparse.py:166-171 with d_h = [])
             msgs = run_stages_autograd(mf.stages(eblocks), E, True, gather=gather)
             agg = propagate(0, edge_index, sel, n, b=msgs)
@@ -617,11 +635,8 @@ class _SparseLayer(nn.Module):
         if act is None or (st.bn is not None and (st.bn.training or st.bn.running_mean is None)):
             return None
         d_x, d_h = x.shape[1], st.weight.shape[0]
-        node_blocks, edge_blocks = [x], []
-        if self.has_ids:
-            (edge_blocks if self.id_scope == "local" else node_blocks).append(ids)
-        if self.has_ef:
-            edge_blocks.append(ef)
+        row = self._row(x, ids, ef)
+        node_blocks, edge_blocks = row.node, row.edge
         d_n = sum(b.shape[1] for b in node_blocks)
         d_r = sum(b.shape[1] for b in edge_blocks)
         if 2 * d_n + d_r <= flags.SPLIT_EDGE_MIN_K or d_h % 4 or d_h > 256 or any(b.shape[1] % 4 for b in edge_blocks) \
@@ -640,12 +655,10 @@ class _SparseLayer(nn.Module):
             if st.bn_params is not None:
                 mean, scale, shift = st.bn_params
                 bias = (bias - mean) * scale + shift
-            # column layout of W1: x_i, x_j, then ids_i, ids_j (global scope) or ids (local), then edge features
-            cols_i, cols_j, off = [w[:, :d_x]], [w[:, d_x:2 * d_x]], 2 * d_x
-            if self.has_ids and self.id_scope != "local":
-                d_id = ids.shape[1]
-                cols_i.append(w[:, off:off + d_id]); cols_j.append(w[:, off + d_id:off + 2 * d_id]); off += 2 * d_id
-            w_i, w_j, w_z = torch.cat(cols_i, 1), torch.cat(cols_j, 1), w[:, off:]
+            # W1's columns per block of the row: the per-vertex inputs' i and j columns alternate, the per-edge columns follow
+            cols = row.columns()[:2 * len(node_blocks)]
+            w_i, w_j = (torch.cat([w[:, a:b] for a, b in cols[k::2]], 1) for k in (0, 1))
+            w_z = w[:, cols[-1][1]:]
             if scale is not None:
                 w_i, w_j, w_z = w_i * scale[:, None], w_j * scale[:, None], w_z * scale[:, None]
             w_n = torch.cat([w_i, w_j], 0).contiguous()                                   # [2 d_h, d_n]
@@ -689,27 +702,12 @@ class _SparseLayer(nn.Module):
 
     # -- differentiable twin (PyTorch ops + the HIP propagate with its own adjoint) ---------------------------------
     def _twin(self, edge_index, x, ids, ef, post=None, native=False):
-        n = x.shape[0]
-        sel = self._sel()
-        if native and (self.ogb or self.msg_kind == "gin"):
-            return self.update_fn(self._self_plus_messages(edge_index, x, ids, ef), post=post)
-        if self.ogb:
-            per_node = self.has_ids and self.id_scope == "global"
-            agg = propagate(1, edge_index, sel, n, a=x, b=ids if self.has_ids else None, c=ef, b_per_node=per_node)
-            self_msg = x + ids if per_node else x
-            xin = (1 + self.eps) * self_msg + agg
+        """``native``: update_fn on its kernels with their adjoints (the gin / ogb training path) instead of its PyTorch form."""
+        n, sel = x.shape[0], self._sel()
+        if self.ogb or self.msg_kind == "gin":
+            xin = self._self_plus_messages(edge_index, x, ids, ef)
             return self.update_fn(xin, post=post) if native else self.update_fn.torch_forward(xin, post=post)
-        if self.msg_kind == "gin":
-            self_parts, ids_nb, ef_nb, per_node = self._gin_parts(x, ids, ef, n)
-            agg = propagate(0, edge_index, sel, n, a=x, b=ids_nb, c=ef_nb, b_per_node=per_node)
-            xin = (1 + self.eps) * torch.cat(self_parts, -1) + agg
-            return self.update_fn(xin, post=post) if native else self.update_fn.torch_forward(xin, post=post)
-        idx_i, idx_j = edge_index[sel], edge_index[1 - sel]
-        parts = [x[idx_i], x[idx_j]]
-        if self.has_ids:
-            parts += [ids] if self.id_scope == "local" else [ids[idx_i], ids[idx_j]]
-        if self.has_ef:
-            parts.append(ef)
+        parts = [t if idx is None else t[idx] for t, idx in self._row(x, ids, ef).blocks(edge_index[sel], edge_index[1 - sel], None)]
         msgs = self.msg_fn.torch_forward(torch.cat(parts, -1))
         agg = propagate(0, edge_index, sel, n, b=msgs)
         return self.update_fn.torch_forward(torch.cat((x, agg), -1), post=post)

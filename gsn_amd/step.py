@@ -44,7 +44,7 @@ class CountLayerStep:
             raise ValueError("CountLayerStep: one class count >= 1 per identifier column (%d columns)" % plan.n_cols)
         self.clamp = bool(clamp)
         self._enc_tab = np.asarray(self.id_classes, dtype=np.int32)
-        if (layer.ogb or layer.msg_kind != "general" or len(layer.msg_fn.fc) != 2 or not layer.has_ids or layer.id_scope != "local"):
+        if not (layer._one_launch_shape() and layer.has_ids):      # (with identifiers, and those per edge: the counting kernel's GSN-e rows)
             raise ValueError("CountLayerStep: a `general` GSN_edge_sparse layer with id_scope='local' and a two-stage msg_fn")
         self._bufs = None          # (key, dict) of the batch-shaped device buffers
         self._lay = None           # (key, structs) of the layer call
