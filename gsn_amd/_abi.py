@@ -73,6 +73,7 @@ class gsn_dgn_agg(ctypes.Structure):
 
 SIGNATURES = {
     "gsn_last_error": (ctypes.c_char_p, []),
+    "gsn_propagate_last_route": (ctypes.c_char_p, []),
     "gsn_version": (c_int, []),
     "gsn_device_count": (c_int, []),
     "gsn_stream_capture_id": (c_i64, [c_vp]),
@@ -189,7 +190,9 @@ def build(verbose: bool = False) -> str:
 
 
 def lib():
-    """The loaded library; raises if it has not been built (no silent fallback)."""
+    """The loaded library; raises if it has not been built (no silent fallback).  Every foreign call of the package goes through this
+    function and the module global ``_lib`` behind it: tests/test_layer_routes_gpu.py and tests/test_propagate_routes_gpu.py put a recording
+    proxy into ``_lib`` for the length of a case, so keep both when this is refactored."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):

@@ -11,10 +11,30 @@
 // dimension with float4 (VEC=4) accesses when every block width is a multiple of 4, scalar otherwise.
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include <cstring>
 
 #include "gsn_internal.h"
 
 namespace gsn {
+
+// ----------------------------------------------------------------------------------------------------------------
+// Route report (gsn_propagate_last_route).  The host dispatchers below choose among some twenty kernel instantiations by width, alignment,
+// segment length, row count, self term and the gradients asked for.  Every launch site notes what it launched -- kernel, template
+// arguments, grid -- in a thread-local record that each entry point of this file clears on entry; the text is formatted only when it is
+// asked for, so a launch pays a few host stores.  tests/test_propagate_routes_gpu.py pins every rung with it: a moved threshold shows there.
+// ----------------------------------------------------------------------------------------------------------------
+struct RouteRec { const char *fmt; int t[6]; unsigned grid, grid_y; };
+constexpr int ROUTE_MAX = 8;                 // (the multi-launch CSR build: seven)
+static thread_local RouteRec g_route[ROUTE_MAX];
+static thread_local int g_route_n = 0;
+constexpr int ROUTE_ENTRY = 96;              // bytes of text per launch (the longest name is 40 characters)
+static thread_local char g_route_text[ROUTE_MAX * ROUTE_ENTRY];
+static inline void route_clear() { g_route_n = 0; }
+static inline void route_note(const char *fmt, int64_t grid, int t0 = 0, int t1 = 0, int t2 = 0, int t3 = 0, int t4 = 0, int t5 = 0, int64_t grid_y = 1) {
+    if (g_route_n >= ROUTE_MAX) return;
+    RouteRec &r = g_route[g_route_n++];
+    r.fmt = fmt; r.t[0] = t0; r.t[1] = t1; r.t[2] = t2; r.t[3] = t3; r.t[4] = t4; r.t[5] = t5; r.grid = (unsigned)grid; r.grid_y = (unsigned)grid_y;
+}
 
 // ----------------------------------------------------------------------------------------------------------------
 // CSR build: stable counting sort of edge ids by aggregation target
@@ -1100,9 +1120,13 @@ static int launch_fwd(const PropArgs &p, hipStream_t st) {
     const int64_t cap = 256 * 8 * 4;  // enough workgroups to fill 256 CUs several times; grid-stride beyond
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
-    if (p.n_self || p.pad_b || p.pad_c) hipLaunchKernelGGL((propagate_fwd_kernel<VEC, LPR, MAXC, true>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-    else if (blocks <= 128) hipLaunchKernelGGL((propagate_fwd_kernel<VEC, LPR, MAXC, false, true>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((propagate_fwd_kernel<VEC, LPR, MAXC, false>), dim3((unsigned)blocks), dim3(256), 0, st, p);
+    // (one pair of literals names the instantiation in the route report and launches it)
+#define FWD(EXT, U4) do { route_note("propagate_fwd<%d,%d,%d,ext%d,u%d>", blocks, VEC, LPR, MAXC, EXT, U4); \
+                          hipLaunchKernelGGL((propagate_fwd_kernel<VEC, LPR, MAXC, EXT, U4>), dim3((unsigned)blocks), dim3(256), 0, st, p); } while (0)
+    if (p.n_self || p.pad_b || p.pad_c) FWD(true, false);
+    else if (blocks <= 128) FWD(false, true);
+    else FWD(false, false);
+#undef FWD
     return hip_check("propagate_fwd_kernel");
 }
 
@@ -1113,11 +1137,14 @@ static int launch_rs3(const PropArgs &p, hipStream_t st, int64_t cap) {
     int64_t blocks = (waves_needed + 3) / 4;
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
+#define RS(EXT, HASC) do { route_note("relu_sum3<%d,%d,%d,nt%d,ext%d,c%d>", blocks, LPR, MAXC, UNR, NT, EXT, HASC); \
+                           hipLaunchKernelGGL((relu_sum3_kernel<LPR, MAXC, UNR, NT, EXT, HASC>), dim3((unsigned)blocks), dim3(256), 0, st, p); } while (0)
     if (!p.c) {        // two streams: relu(x_j + e_e), or the identifier and edge-feature embeddings summed by their encoder (models.GNN_OGB)
-        if (p.n_self) hipLaunchKernelGGL((relu_sum3_kernel<LPR, MAXC, UNR, NT, true, false>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((relu_sum3_kernel<LPR, MAXC, UNR, NT, false, false>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-    } else if (p.n_self) hipLaunchKernelGGL((relu_sum3_kernel<LPR, MAXC, UNR, NT, true>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((relu_sum3_kernel<LPR, MAXC, UNR, NT, false>), dim3((unsigned)blocks), dim3(256), 0, st, p);
+        if (p.n_self) RS(true, false);
+        else RS(false, false);
+    } else if (p.n_self) RS(true, true);
+    else RS(false, true);
+#undef RS
     return hip_check("relu_sum3_kernel");
 }
 
@@ -1128,8 +1155,11 @@ static int launch_cp(const PropArgs &p, hipStream_t st, int64_t cap) {
     int64_t blocks = (waves_needed + 3) / 4;
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
-    if (p.n_self) hipLaunchKernelGGL((cat_pipe_kernel<LPR, MAXC, UNR, true>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((cat_pipe_kernel<LPR, MAXC, UNR, false>), dim3((unsigned)blocks), dim3(256), 0, st, p);
+#define CPL(EXT) do { route_note("cat_pipe<%d,%d,%d,ext%d>", blocks, LPR, MAXC, UNR, EXT); \
+                      hipLaunchKernelGGL((cat_pipe_kernel<LPR, MAXC, UNR, EXT>), dim3((unsigned)blocks), dim3(256), 0, st, p); } while (0)
+    if (p.n_self) CPL(true);
+    else CPL(false);
+#undef CPL
     return hip_check("cat_pipe_kernel");
 }
 
@@ -1373,13 +1403,34 @@ __global__ __launch_bounds__(64) void csr_graphs_kernel(const int64_t *__restric
 
 using namespace gsn;
 
+extern "C" const char *gsn_propagate_last_route(void) {
+    // every record is formatted into its own ROUTE_ENTRY bytes (snprintf truncates there), so the text cannot outgrow the buffer.
+    // r.fmt is one of the literals at the launch sites of this file: at most six %d, filled from r.t in order.
+    constexpr size_t cap = sizeof(g_route_text);
+    size_t o = 0;
+    g_route_text[0] = 0;
+    for (int i = 0; i < g_route_n && o + ROUTE_ENTRY <= cap; ++i) {
+        const RouteRec &r = g_route[i];
+        char name[56], entry[ROUTE_ENTRY];
+        snprintf(name, sizeof(name), r.fmt, r.t[0], r.t[1], r.t[2], r.t[3], r.t[4], r.t[5]);
+        const int len = r.grid_y > 1 ? snprintf(entry, sizeof(entry), "%s%s grid=%ux%u", i ? ";" : "", name, r.grid, r.grid_y)
+                                     : snprintf(entry, sizeof(entry), "%s%s grid=%u", i ? ";" : "", name, r.grid);
+        const size_t n = len < 0 ? 0 : ((size_t)len < sizeof(entry) ? (size_t)len : sizeof(entry) - 1);
+        memcpy(g_route_text + o, entry, n + 1);
+        o += n;
+    }
+    return g_route_text;
+}
+
 extern "C" int64_t gsn_csr_scratch_elems(int64_t n_nodes) { return (n_nodes + 1) + (n_nodes + 1) / SCAN_TILE + 2; }
 
 extern "C" int gsn_segsum_prepare_hip(int64_t n_seg, int64_t n_rows, const int32_t *seg_ptr, const int32_t *row_target,
                                       int64_t n_out, float *out, void *stream) {
+    route_clear();
     if (!seg_ptr || !out || (n_rows > 0 && !row_target) || n_out <= 0) return set_error(GSN_E_INVALID, "gsn_segsum_prepare_hip: bad argument");
     const int64_t items = n_seg + n_rows / GSN_SEG_RANGE_ROWS;
     if (items <= 0) return GSN_OK;
+    route_note("segsum_prepare", (items + 255) / 256);
     hipLaunchKernelGGL(segsum_prepare_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        seg_ptr, row_target, n_seg, n_rows, (int)n_out, out);
     return hip_check("gsn_segsum_prepare_hip");
@@ -1387,6 +1438,7 @@ extern "C" int gsn_segsum_prepare_hip(int64_t n_seg, int64_t n_rows, const int32
 
 extern "C" int gsn_csr_build_hip(int64_t n_nodes, int64_t n_edges, const int64_t *index, const int64_t *other, int32_t *seg_ptr,
                                  int32_t *perm, int32_t *sorted_target, int32_t *sorted_other, int32_t *scratch, void *stream) {
+    route_clear();
     if (sorted_other && !other) return set_error(GSN_E_INVALID, "gsn_csr_build_hip: sorted_other needs `other`");
     if (n_nodes < 0 || n_edges < 0 || !seg_ptr || !scratch || (n_edges > 0 && (!index || !perm)))
         return set_error(GSN_E_INVALID, "gsn_csr_build_hip: bad argument");
@@ -1402,6 +1454,7 @@ extern "C" int gsn_csr_build_hip(int64_t n_nodes, int64_t n_edges, const int64_t
                 return set_error(GSN_E_HIP, "gsn_csr_build_hip: cannot raise the LDS limit of csr_small_kernel");
             lds_set.mark(lds_dev);
         }
+        route_note("csr_small", 1);
         hipLaunchKernelGGL(csr_small_kernel, dim3(1), dim3(1024), (size_t)(2 * (n_nodes + 1)) * sizeof(int32_t), st, index, n_edges,
                            (int)n_nodes, seg_ptr, perm, sorted_target, other, sorted_other);
         return hip_check("gsn_csr_build_hip");
@@ -1410,19 +1463,26 @@ extern "C" int gsn_csr_build_hip(int64_t n_nodes, int64_t n_edges, const int64_t
     int32_t *cnt = scratch;                 // [n1] histogram, later the fill cursor
     int32_t *tiles = scratch + n1;          // [n_tiles]
     const int64_t n_tiles = (n1 + SCAN_TILE - 1) / SCAN_TILE;
+    route_note("csr_zero", (n1 + CSR_T - 1) / CSR_T);
     hipLaunchKernelGGL(csr_zero, dim3((unsigned)((n1 + CSR_T - 1) / CSR_T)), dim3(CSR_T), 0, st, cnt, n1);
     if (n_edges > 0) {
         int64_t blocks = (n_edges + CSR_T - 1) / CSR_T;
         if (blocks > 32768) blocks = 32768;
+        route_note("csr_hist", blocks);
         hipLaunchKernelGGL(csr_hist, dim3((unsigned)blocks), dim3(CSR_T), 0, st, index, n_edges, cnt);
     }
+    route_note("scan_tile_sums", n_tiles);
     hipLaunchKernelGGL(scan_tile_sums, dim3((unsigned)n_tiles), dim3(SCAN_T), 0, st, cnt, n1, tiles);
+    route_note("scan_tile_offsets", 1);
     hipLaunchKernelGGL(scan_tile_offsets, dim3(1), dim3(64), 0, st, tiles, n_tiles);
+    route_note("scan_apply", n_tiles);
     hipLaunchKernelGGL(scan_apply, dim3((unsigned)n_tiles), dim3(SCAN_T), 0, st, cnt, n1, tiles, seg_ptr, cnt);
     if (n_edges > 0) {
         int64_t blocks = (n_edges + CSR_T - 1) / CSR_T;
         if (blocks > 32768) blocks = 32768;
+        route_note("csr_fill", blocks);
         hipLaunchKernelGGL(csr_fill, dim3((unsigned)blocks), dim3(CSR_T), 0, st, index, n_edges, cnt, perm);
+        route_note("csr_sort_segments", (n_nodes + CSR_T - 1) / CSR_T);
         hipLaunchKernelGGL(csr_sort_segments, dim3((unsigned)((n_nodes + CSR_T - 1) / CSR_T)), dim3(CSR_T), 0, st, seg_ptr, n_nodes, perm, sorted_target, other, sorted_other);
     }
     return hip_check("gsn_csr_build_hip");
@@ -1444,6 +1504,7 @@ extern "C" int gsn_propagate_self_fwd_hip(int kind, int64_t n_nodes, int64_t n_e
                                           const int32_t *perm, const int32_t *sorted_src, const float *a, int64_t da, const float *b,
                                           int64_t db, int b_per_node, const float *c, int64_t dc, int64_t pad_b, int64_t pad_c,
                                           int n_self, const gsn_self_block *self_blocks, const float *eps, float *out, void *stream) {
+    route_clear();
     return propagate_fwd_impl(kind, n_nodes, n_edges, src, seg_ptr, perm, sorted_src, a, da, b, db, db, b_per_node, c, dc, pad_b, pad_c, n_self,
                               self_blocks, eps, out, stream);
 }
@@ -1452,6 +1513,7 @@ extern "C" int gsn_propagate_self_fwd_hip(int kind, int64_t n_nodes, int64_t n_e
 // a gathered block's input gradient, taken where the input-gradient product left it (no contiguous copy of the slice)
 extern "C" int gsn_segment_sum_rows_hip(int64_t n_nodes, int64_t n_edges, const int64_t *src, const int32_t *seg_ptr, const int32_t *perm,
                                         const int32_t *sorted_src, const float *b, int64_t width, int64_t ld, float *out, void *stream) {
+    route_clear();
     if (width < 1 || ld < width) return set_error(GSN_E_INVALID, "gsn_segment_sum_rows_hip: width %lld, row stride %lld", (long long)width, (long long)ld);
     return propagate_fwd_impl(GSN_MSG_CAT, n_nodes, n_edges, src, seg_ptr, perm, sorted_src, nullptr, 0, b, width, ld, 0, nullptr, 0, 0, 0, 0, nullptr,
                               nullptr, out, stream);
@@ -1514,6 +1576,7 @@ static int propagate_fwd_impl(int kind, int64_t n_nodes, int64_t n_edges, const 
     const bool aligned = ((da | db | dc | ldb | pad_b | pad_c | self_or) % 4 == 0) && pad_b == 0 && pad_c == 0 &&
                          (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)out | self_align) % 16 == 0);
     if (aligned && kind == GSN_MSG_CAT && !da && !dc && db && !b_per_node && !n_self && n_nodes <= 512 && n_edges >= 8 * n_nodes) {
+        route_note("segment_sum_wg", n_nodes);
         hipLaunchKernelGGL(segment_sum_wg_kernel, dim3((unsigned)n_nodes), dim3(256), 0, st, p);
         return hip_check("segment_sum_wg_kernel");
     }
@@ -1573,6 +1636,7 @@ extern "C" int gsn_propagate_pad_bwd_hip(int kind, int64_t n_nodes, int64_t n_ed
                                          const int32_t *seg_ptr_src, const int32_t *perm_src, const float *a, int64_t da,
                                          const float *b, int64_t db, int b_per_node, const float *c, int64_t dc, int64_t pad_b,
                                          int64_t pad_c, const float *g_out, float *g_a, float *g_b, float *g_c, void *stream) {
+    route_clear();
     return propagate_bwd_impl(kind, n_nodes, n_edges, src, tgt, seg_ptr_src, perm_src, a, da, b, db, b_per_node, c, dc, pad_b, pad_c, g_out, g_a, g_b,
                               g_c, stream, 0, nullptr, nullptr);
 }
@@ -1586,6 +1650,7 @@ extern "C" int gsn_propagate_bwd_fold_self_hip(int64_t n_nodes, int64_t n_edges,
                                                const int32_t *seg_ptr_src, const int32_t *perm_src, const float *a, int64_t d, const float *b,
                                                int64_t db, const float *c, int64_t dc, const float *g_out, float *g_a, float *g_b, float *g_c,
                                                const float *eps, double *g_eps, void *stream) {
+    route_clear();
     static const bool pipe = [] { const char *e = getenv("GSN_PROP_BWD_PIPE"); return !e || atoi(e) != 0; }();
     static const bool fold = [] { const char *e = getenv("GSN_PROP_FOLD_SELF"); return !e || atoi(e) != 0; }();
     const bool need_edge = (g_b && db) || (g_c && dc);
@@ -1633,12 +1698,20 @@ static int propagate_bwd_impl(int kind, int64_t n_nodes, int64_t n_edges, const 
             int64_t blocks = (n_edges + 15) / 16;
             if (blocks > 16384) blocks = 16384;
             static const bool pipe = [] { const char *e = getenv("GSN_PROP_BWD_PIPE"); return !e || atoi(e) != 0; }();
-            if (vec4 && pipe && d_out <= 320) hipLaunchKernelGGL(propagate_bwd_edge_relu4p_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
-            else if (vec4) hipLaunchKernelGGL(propagate_bwd_edge_relu4_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
-            else hipLaunchKernelGGL(propagate_bwd_edge_cat4_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
+            if (vec4 && pipe && d_out <= 320) {
+                route_note("propagate_bwd_edge_relu4p", blocks);
+                hipLaunchKernelGGL(propagate_bwd_edge_relu4p_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
+            } else if (vec4) {
+                route_note("propagate_bwd_edge_relu4", blocks);
+                hipLaunchKernelGGL(propagate_bwd_edge_relu4_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
+            } else {
+                route_note("propagate_bwd_edge_cat4", blocks);
+                hipLaunchKernelGGL(propagate_bwd_edge_cat4_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
+            }
         } else {
             int64_t blocks = (n_edges * d_out + 255) / 256;
             if (blocks > 16384) blocks = 16384;
+            route_note("propagate_bwd_edge", blocks);
             hipLaunchKernelGGL(propagate_bwd_edge_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
         }
     }
@@ -1654,12 +1727,19 @@ static int propagate_bwd_impl(int kind, int64_t n_nodes, int64_t n_edges, const 
             static const bool pipe = [] { const char *e = getenv("GSN_PROP_BWD_PIPE"); return !e || atoi(e) != 0; }();
             if (p.fold_self) {
                 if (!(pipe && d_out <= 320)) return set_error(GSN_E_UNSUPPORTED, "gsn_propagate_bwd_fold_self_hip: the folded self term rides the pipelined node pass (d <= 320)");
+                route_note("propagate_bwd_node_edge4p<fold%d>", blocks, 1);
                 hipLaunchKernelGGL(propagate_bwd_node_edge4p_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, p);
-            } else if (pipe && d_out <= 320) hipLaunchKernelGGL(propagate_bwd_node_edge4p_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, p);
-            else hipLaunchKernelGGL(propagate_bwd_node_edge4_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
+            } else if (pipe && d_out <= 320) {
+                route_note("propagate_bwd_node_edge4p<fold%d>", blocks, 0);
+                hipLaunchKernelGGL(propagate_bwd_node_edge4p_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, p);
+            } else {
+                route_note("propagate_bwd_node_edge4", blocks);
+                hipLaunchKernelGGL(propagate_bwd_node_edge4_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
+            }
         } else {
             int64_t blocks = (n_nodes + 3) / 4;
             if (blocks > 16384) blocks = 16384;
+            route_note("propagate_bwd_node", blocks);
             hipLaunchKernelGGL(propagate_bwd_node_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
         }
     }
@@ -1669,6 +1749,7 @@ static int propagate_bwd_impl(int kind, int64_t n_nodes, int64_t n_edges, const 
 extern "C" int gsn_propagate_self_bwd_hip(int kind, int64_t n_nodes, int64_t d_out, const float *g_out, int n_self,
                                           const gsn_self_block *self_blocks, float *const *g_self, const float *eps, double *g_eps,
                                           double *g_colsum, void *stream) {
+    route_clear();
     if (kind != GSN_MSG_CAT && kind != GSN_MSG_RELU_SUM) return set_error(GSN_E_INVALID, "gsn_propagate_self_bwd_hip: unknown kind %d", kind);
     if (n_self < 1 || n_self > 3 || !self_blocks || !g_out || d_out < 1 || d_out > 1024)
         return set_error(GSN_E_INVALID, "gsn_propagate_self_bwd_hip: bad arguments");
@@ -1693,6 +1774,7 @@ extern "C" int gsn_propagate_self_bwd_hip(int kind, int64_t n_nodes, int64_t d_o
         const int64_t n4 = n_nodes * d_out / 4;
         int64_t bx = (n4 + 255) / 256;
         if (bx > 4096) bx = 4096;
+        route_note("propagate_self_bwd_flat", bx);
         hipLaunchKernelGGL(propagate_self_bwd_flat_kernel, dim3((unsigned)bx), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), n4,
                            reinterpret_cast<const float4 *>(g_out), reinterpret_cast<const float4 *>(self_blocks[0].data),
                            reinterpret_cast<float4 *>(p.g_self[0]), eps, g_eps);
@@ -1700,6 +1782,7 @@ extern "C" int gsn_propagate_self_bwd_hip(int kind, int64_t n_nodes, int64_t d_o
     }
     int64_t bx = (n_nodes + 3) / 4;
     if (bx > 1024) bx = 1024;
+    route_note("propagate_self_bwd", bx, 0, 0, 0, 0, 0, 0, (d_out + 63) / 64);
     hipLaunchKernelGGL(propagate_self_bwd_kernel, dim3((unsigned)bx, (unsigned)((d_out + 63) / 64)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), p);
     return hip_check("propagate_self_bwd_kernel");
@@ -1709,6 +1792,7 @@ extern "C" int gsn_csr_build_graphs_hip(int64_t n_graphs, const int64_t *node_pt
                                         int64_t n_edges, int64_t max_nodes, int64_t max_edges, const int64_t *index,
                                         const int64_t *other, int32_t *seg_ptr, int32_t *perm, int32_t *sorted_target,
                                         int32_t *sorted_other, int32_t *status, void *stream) {
+    route_clear();
     if (sorted_other && !other) return set_error(GSN_E_INVALID, "gsn_csr_build_graphs_hip: sorted_other needs `other`");
     if (n_graphs < 1 || !node_ptr || !edge_ptr || n_nodes < 0 || n_edges < 0 || !seg_ptr || !status || (n_edges > 0 && (!index || !perm)))
         return set_error(GSN_E_INVALID, "gsn_csr_build_graphs_hip: bad argument");
@@ -1728,6 +1812,7 @@ extern "C" int gsn_csr_build_graphs_hip(int64_t n_graphs, const int64_t *node_pt
             return set_error(GSN_E_HIP, "gsn_csr_build_graphs_hip: cannot raise the LDS limit of csr_graphs_kernel");
         lds_set.mark(lds_dev);
     }
+    route_note("csr_graphs", n_graphs);
     hipLaunchKernelGGL(csr_graphs_kernel, dim3((unsigned)n_graphs), dim3(64), (size_t)lds, st, node_ptr, edge_ptr, (int)n_graphs, n_nodes, n_edges,
                        (int)max_nodes, (int)max_edges, index, other, seg_ptr, perm, sorted_target, sorted_other, status);
     return hip_check("gsn_csr_build_graphs_hip");
@@ -1738,6 +1823,7 @@ static int launch_split_sum(const SplitSumArgs &p, hipStream_t st) {
     int64_t blocks = ((p.n_nodes + 1) / 2 + 3) / 4;
     if (blocks > 256 * 32) blocks = 256 * 32;
     if (blocks < 1) blocks = 1;
+    route_note("edge_split_sum<%d,%d>", blocks, MAXC, NZ4);
     hipLaunchKernelGGL((edge_split_sum_kernel<MAXC, NZ4>), dim3((unsigned)blocks), dim3(256), 0, st, p);
     return hip_check("edge_split_sum_kernel");
 }
@@ -1746,6 +1832,7 @@ extern "C" int gsn_edge_split_sum_hip(int64_t n_nodes, int64_t n_edges, const in
                                       const int32_t *perm, const float *p_i, const float *p_j, int64_t pitch, const float *z0,
                                       int64_t w0, const float *z1, int64_t w1, const float *wz_t, int64_t d, int act, float *out,
                                       void *stream) {
+    route_clear();
     if (n_nodes < 0 || n_edges < 0 || !seg_ptr || !p_i || !p_j || !out || (n_edges > 0 && !sorted_src))
         return set_error(GSN_E_INVALID, "gsn_edge_split_sum_hip: bad argument");
     if (d < 4 || (d & 3) || d > 256 || pitch < d || (pitch & 3)) return set_error(GSN_E_UNSUPPORTED, "gsn_edge_split_sum_hip: d must be a multiple of 4 up to 256 (pitch a multiple of 4)");

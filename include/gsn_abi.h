@@ -49,6 +49,10 @@ enum {
 };
 
 const char *gsn_last_error(void);
+/* what the last propagate / segment-sum / CSR entry point called on this thread launched: "kernel<template arguments> grid=G" per launch,
+ * joined by ';' (empty: nothing was launched).  Thread-local, valid until the next call on this thread; never fails.  The dispatch rules
+ * of csrc/propagate.hip report from their launch sites, so a test can state which kernel a shape takes. */
+const char *gsn_propagate_last_route(void);
 int gsn_version(void);
 /* number of visible gfx950 devices (0 if none / no driver); never fails */
 int gsn_device_count(void);
