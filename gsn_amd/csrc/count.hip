@@ -43,7 +43,7 @@ struct SideArgs {
 #ifndef GSN_SIDE_EVERY
 #define GSN_SIDE_EVERY 4
 #endif
-constexpr int SIDE_EVERY = GSN_SIDE_EVERY;  // counting workgroups per side workgroup (A/B: 2: +0.0xx, 8: see profiles/r06_count_side_ab.txt)
+constexpr int SIDE_EVERY = GSN_SIDE_EVERY;  // counting workgroups per side workgroup (A/B: 2: +0.0xx, 8: see profiles/r06_count_side_ab.txt; at 8 waves per SIMD 8 loses 0.017 ms: profiles/count_cycle_occupancy.txt)
 
 struct CountArgs {
     const uint32_t *plan;      // device
@@ -102,6 +102,15 @@ __device__ __forceinline__ side_ptr_t side_late() {
     kptr_t k = (kptr_t)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(k));
     return (side_ptr_t)(k + offsetof(CountArgs, side));
+}
+// The same for the whole argument block: the cycle instantiation's body reads every field where it uses it (a scalar load from the
+// kernel-argument segment) -- held from the kernel's entry, the ~110 argument words were most of its scalar spills.
+typedef const CountArgs __attribute__((address_space(4))) *args_ptr_t;
+__device__ __forceinline__ args_ptr_t args_late() {
+    typedef const unsigned char __attribute__((address_space(4))) *kptr_t;
+    kptr_t k = (kptr_t)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return (args_ptr_t)k;
 }
 __device__ __forceinline__ int side_byte(const unsigned w0, const unsigned w1, const int c) { return (int)(((c < 4 ? w0 : w1) >> (8 * (c & 3))) & 0xffu); }
 
@@ -379,8 +388,8 @@ __device__ unsigned long long *g_count_prof2;  // [12] wave-level sums over the 
 // through the whole kernel (106 of them + spills before).  The launcher selects it when all of that holds (launch<>()).
 // CYC = L > 0 (with MOL): every column is a non-induced cycle of length <= L -- no plan table, candidate stack or distance tables in LDS,
 // and the task pool is one bitset path walk per searching row (count_core.h: cycle_walk) that yields the row's four cells at once.
-template <int W, int T, bool DIR, bool TAIL, bool MOL, int CYC = 0>
-__device__ __forceinline__ int count_body(const CountArgs &a, unsigned char *smem, const int item, const int part, const int g, const int ng, const bool report) {
+template <int W, int T, bool DIR, bool TAIL, bool MOL, int CYC = 0, class Args = CountArgs>
+__device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, const int item, const int part, const int g, const int ng, const bool report) {
 #ifdef COUNT_PROF
     unsigned long long t_prev = __builtin_amdgcn_s_memtime();
 #endif
@@ -408,7 +417,11 @@ __device__ __forceinline__ int count_body(const CountArgs &a, unsigned char *sme
     uint64_t *A_in = DIR ? reinterpret_cast<uint64_t *>(smem + a.off_ain) : nullptr;
     const int *enc = reinterpret_cast<const int *>(smem + a.off_enc);   // [2 * n_cols] (encoded output only)
 
-    const int tid = threadIdx.x;
+    int tid_v = threadIdx.x;
+    // (CYC: the lane id is opaque per pass, so that 64-bit lane offsets of the output loops are made where they are used and not held
+    //  -- hoisted out of the kernel's pass loop -- across the whole body: the last two registers above the bound)
+    if constexpr (CYC > 0) asm volatile("" : "+v"(tid_v));
+    const int tid = tid_v;
     (void)item;
     const int64_t n0 = a.node_ptr[g], e0 = a.edge_ptr[g];
     const int64_t n64 = a.node_ptr[g + ng] - n0, E64 = a.edge_ptr[g + ng] - e0;
@@ -421,13 +434,26 @@ __device__ __forceinline__ int count_body(const CountArgs &a, unsigned char *sme
     const bool a_enc_from_counts = a.enc_from_counts != 0;
     const int a_split = MOL ? 1 : a.split;
 
+    // CYC: the zeros of an error path (a graph beyond the declared sizes, a bad index), a row per thread and trip: the same bytes as the
+    // flat loops of the other instantiations without their 64-bit quotients, whose expansion was this instantiation's register peak
+    auto zero_rows_cyc = [&](const int64_t nrows, const bool pack_always) {
+        const bool z32 = a.enc_out && !a.enc_no32, z16 = a.enc16 && (pack_always || a.enc_no32);
+        for (int64_t r = tid; r < nrows; r += T) {
+            if (a.out) for (int c = 0; c < 4; ++c) a.out[(row0 + r) * 4 + c] = 0;
+            if (z32) for (int k = 0; k < a.enc_width; ++k) a.enc_out[(row0 + r) * a.enc_width + k] = 0.f;
+            if (z16) for (int k = 0; k < a.enc_width; ++k) a.enc16[(row0 + r) * a.enc16_stride + a.enc16_col0 + k] = 0;
+        }
+    };
     if (ng > 1 && (n64 > a.n_cap || E64 > a.e_cap || n64 > W * 64)) return 1;
     if (ng == 1 && (n64 > a.n_decl || E64 > a.e_decl || n64 > W * 64)) {
         // caller under-declared max_nodes / max_edges: report, leave zeros
         if (part == 0) {
+            if constexpr (CYC > 0) zero_rows_cyc(rows64, true);
+            else {
             if (a.out) for (int64_t i = tid; i < rows64 * n_cols; i += T) a.out[row0 * n_cols + i] = 0;
             if (a.enc_out && !a.enc_no32) for (int64_t i = tid; i < rows64 * a.enc_width; i += T) a.enc_out[row0 * a.enc_width + i] = 0.f;
             if (a.enc16) for (int64_t i = tid; i < rows64 * a.enc_width; i += T) a.enc16[(row0 + i / a.enc_width) * a.enc16_stride + a.enc16_col0 + i % a.enc_width] = 0;
+            }
             if (tid == 0) atomicMax(&a.status[g], (int)GSN_ST_TOO_LARGE);
         }
         return 0;
@@ -458,12 +484,46 @@ __device__ __forceinline__ int count_body(const CountArgs &a, unsigned char *sme
         }
     };
 
+    // CYC: the four cells of one row at once -- the staged 16-bit counts as ONE 8-byte LDS store, the class bytes (only without staged
+    // counts) as one word.  The path is the molecule one (staged cells, staged class indices, no direct float rows), so none of emit_cell's
+    // other arms exist here; the class counts are read from the kernel arguments, wave-uniform, not from the LDS table.  32-bit counts (count_core.h:
+    // CycleAcc) are widened at the int64 store only.
+    auto emit_row = [&](const int row, const uint32_t c0, const uint32_t c1, const uint32_t c2, const uint32_t c3) {
+        if (a_stage_out) {
+            auto lo16 = [](const uint32_t c) { return c < 0xffffu ? c : 0xffffu; };
+            *reinterpret_cast<uint2 *>(out_lds + 4 * row) = uint2{lo16(c0) | (lo16(c1) << 16), lo16(c2) | (lo16(c3) << 16)};
+            if (((c0 | c1 | c2 | c3) >> 16) || c0 == 0xffffu || c1 == 0xffffu || c2 == 0xffffu || c3 == 0xffffu) {      // (rare: a count that does not fit goes out directly)
+                int64_t *d = a.out + (row0 + row) * 4;
+                if (c0 >= 0xffffu) d[0] = (int64_t)c0;
+                if (c1 >= 0xffffu) d[1] = (int64_t)c1;
+                if (c2 >= 0xffffu) d[2] = (int64_t)c2;
+                if (c3 >= 0xffffu) d[3] = (int64_t)c3;
+            }
+        } else if (a.out) {
+            int64_t *d = a.out + (row0 + row) * 4;
+            d[0] = (int64_t)c0; d[1] = (int64_t)c1; d[2] = (int64_t)c2; d[3] = (int64_t)c3;
+        }
+        if (!a_enc_from_counts) {
+            const bool clamp = a.enc_clamp != 0;
+            auto cls = [&](const uint32_t c, const uint32_t ncls) { return c < ncls ? c : (clamp ? ncls - 1u : 0xffu); };
+            *reinterpret_cast<uint32_t *>(smem + a.off_encst + 4 * row) =
+                cls(c0, a.enc_n[0]) | (cls(c1, a.enc_n[1]) << 8) | (cls(c2, a.enc_n[2]) << 16) | (cls(c3, a.enc_n[3]) << 24);
+        }
+    };
+
     // ---- phase 0: clear LDS state, copy the plan table ------------------------------------------------------------
     for (int i = tid; i < n * W; i += T) A[i] = 0ull;
     if (DIR)
         for (int i = tid; i < n * W; i += T) A_in[i] = 0ull;
     if (!CYC)
         for (int i = tid; i < a.plan_words; i += T) plan[i] = a.plan[i];
+    if constexpr (CYC > 0) {                            // (the same table from four wave-uniform reads: no per-lane index into the arguments)
+        const int e0 = a.enc_n[0], e1 = a.enc_n[1], e2 = a.enc_n[2], e3 = a.enc_n[3];
+        if (tid < 4) {
+            reinterpret_cast<int *>(smem + a.off_enc)[2 * tid] = (tid > 0 ? e0 : 0) + (tid > 1 ? e1 : 0) + (tid > 2 ? e2 : 0);
+            reinterpret_cast<int *>(smem + a.off_enc)[2 * tid + 1] = tid == 0 ? e0 : (tid == 1 ? e1 : (tid == 2 ? e2 : e3));
+        }
+    } else
     if (a_enc)                                          // (first float, n_classes) per column
         for (int c = tid; c < n_cols; c += T) {
             int o = 0;
@@ -507,6 +567,17 @@ __device__ __forceinline__ int count_body(const CountArgs &a, unsigned char *sme
     }
     __syncthreads();
     COUNT_T(1);
+    uint64_t core2 = 0;                                  // CYC: the 2-core, the only core its plans name -- a wave-uniform register, never in LDS
+    if constexpr (CYC > 0) {
+        const uint64_t arow = tid < n ? A[tid] : 0ull;
+        uint64_t cur = below_word(misc[1], 0) | (below_word(misc[5], 0) & ~below_word(nA, 0));      // the vertices that exist (as `valid` below)
+        for (;;) {                                       // (the ballot peeling below, d = 2)
+            const uint64_t nxt = __ballot(((cur >> tid) & 1ull) && popc64(arow & cur) >= 2);
+            if (nxt == cur) break;
+            cur = nxt;
+        }
+        core2 = cur;
+    } else {
     // the vertices that exist: 0 .. largest id of the first graph, nA .. largest id of the second
     if (tid < W) valid[tid] = below_word(misc[1], tid) | (below_word(misc[5], tid) & ~below_word(nA, tid));
     // d-cores: every image of a pattern with minimum degree d lies in the d-core of the graph (its >= d pattern neighbours
@@ -562,6 +633,7 @@ __device__ __forceinline__ int count_body(const CountArgs &a, unsigned char *sme
                                      [](uint64_t *wp, uint64_t bit) { atomicOr(reinterpret_cast<unsigned long long *>(wp), (unsigned long long)bit); });
         }
         __syncthreads();
+    }
     }
     COUNT_T(2);
     // distance pruning tables: vertices within 2 / 3 hops (count_core.h, candidates())
@@ -630,22 +702,35 @@ __device__ __forceinline__ int count_body(const CountArgs &a, unsigned char *sme
                     }
                     revof[c] = rev < 0 ? (uint16_t)0xffffu : (uint16_t)rev;
                     primary = live && !(a_sym && rev >= 0 && u > v);
-                    if (!live && part == 0 && !bulk_zero)
+                    if (!live && part == 0 && !bulk_zero) {
+                        if constexpr (CYC > 0) emit_row(c, 0u, 0u, 0u, 0u);
+                        else
                         for (int col = 0; col < n_cols; ++col) emit_cell(c, col, 0ull);
+                    }
 #ifndef COUNT_NO_CORE_FILTER
                     if (primary) {
                         // A root outside the WEAKEST core any plan of the launch lives in is the image of nothing (cores are nested: it is outside
                         // every plan's core; lane_begin would find that out one task at a time -- a pull, a begin and a finish per cell).  Its
                         // cells, and those of the reverse row it would have written, are zero here and the row never enters the pool: on
                         // molecules (cycle plans: the 2-core = ring systems and what connects them) more than half of the rows.
-                        const uint64_t *cm = cores + (__ffs(a.core_mask | (1 << CORE_MAX)) - 1) * W;
-                        if (!(((cm[u >> 6] >> (u & 63)) & (cm[v >> 6] >> (v & 63))) & 1ull)) {
+                        bool in_core;
+                        if constexpr (CYC > 0) in_core = ((core2 >> u) & (core2 >> v) & 1ull) != 0;
+                        else {
+                            const uint64_t *cm = cores + (__ffs(a.core_mask | (1 << CORE_MAX)) - 1) * W;
+                            in_core = (((cm[u >> 6] >> (u & 63)) & (cm[v >> 6] >> (v & 63))) & 1ull) != 0;
+                        }
+                        if (!in_core) {
                             primary = false;
-                            if (part == 0 && !bulk_zero)
+                            if (part == 0 && !bulk_zero) {
+                                if constexpr (CYC > 0) {
+                                    emit_row(c, 0u, 0u, 0u, 0u);
+                                    if (rev >= 0) emit_row(rev, 0u, 0u, 0u, 0u);
+                                } else
                                 for (int col = 0; col < n_cols; ++col) {
                                     emit_cell(c, col, 0ull);
                                     if (a_sym && rev >= 0) emit_cell(rev, col, 0ull);
                                 }
+                            }
                         }
                     }
 #endif
@@ -661,9 +746,12 @@ __device__ __forceinline__ int count_body(const CountArgs &a, unsigned char *sme
     if (misc[2] != 0) {  // bad index: zeros + status
         if (!report) return 1;
         if (part == 0) {
+            if constexpr (CYC > 0) zero_rows_cyc(rows, false);
+            else {
             if (a.out) for (int i = tid; i < rows * n_cols; i += T) a.out[row0 * n_cols + i] = 0;
             if (a.enc_out && !a.enc_no32) for (int i = tid; i < rows * a.enc_width; i += T) a.enc_out[row0 * a.enc_width + i] = 0.f;
             if (a.enc16 && a.enc_no32) for (int i = tid; i < rows * a.enc_width; i += T) a.enc16[(row0 + i / a.enc_width) * a.enc16_stride + a.enc16_col0 + i % a.enc_width] = 0;
+            }
             if (tid == 0) atomicMax(&a.status[g], misc[2]);
         }
         return 0;
@@ -684,8 +772,11 @@ __device__ __forceinline__ int count_body(const CountArgs &a, unsigned char *sme
         // those of its mirror row.  Inner vertices are pruned with the 2-core, the core the cycle plans name (and the one phase 2
         // filtered the roots with).
         static_assert(W == 1 && MOL, "the cycle walk is the molecule instantiation's: one-word adjacency rows, four columns");
-        const uint64_t core2 = cores[2 * W];
         const int n_div = misc[3];                         // rows that run walks
+        // the four columns' lengths are wave-uniform: decoded once, each cell is one select chain on 32-bit counters (count_core.h: CycleAcc)
+        typedef typename CycleAcc<CYC>::type acc_t;
+        static_assert(sizeof(acc_t) == 4, "emit_row takes 32-bit counts");
+        const int j0 = (int)(a.cyc_len & 0xffu) - 3, j1 = (int)((a.cyc_len >> 8) & 0xffu) - 3, j2 = (int)((a.cyc_len >> 16) & 0xffu) - 3, j3 = (int)(a.cyc_len >> 24) - 3;
         for (int i = tid; i < n_div; i += T) {
 #ifdef COUNT_PROF
             prof_iters += 1; prof_lanes += (unsigned)__popcll(__ballot(1));      // passes of the wave, rows walked per pass
@@ -693,24 +784,22 @@ __device__ __forceinline__ int count_body(const CountArgs &a, unsigned char *sme
             const unsigned long long t0 = COUNT_ARM_T0();
             (void)t0;
             const int row = prim[i];
-            uint64_t cnt[CYC - 2];
+            acc_t cnt[CYC - 2];
             cycle_walk<CYC>(A, eu[row], ev[row], core2, cnt);
             COUNT_ARM(2, t0);
             const unsigned long long t0f = COUNT_ARM_T0();
             (void)t0f;
             const int rev = revof[row] == 0xffffu ? -1 : (int)revof[row];
-            bool any = false;
-#pragma unroll
-            for (int col = 0; col < 4; ++col) {
-                const int j = (int)((a.cyc_len >> (8 * col)) & 0xffu) - 3;
-                uint64_t c = 0;
+            auto pick = [&](const int j) {
+                acc_t c = 0;
 #pragma unroll
                 for (int q = 0; q < CYC - 2; ++q) c = j == q ? cnt[q] : c;
-                emit_cell(row, col, c);
-                if (rev >= 0) emit_cell(rev, col, c);
-                any = any || c != 0;
-            }
-            if (rev < 0 && any) atomicMax(&misc[2], (int)GSN_ST_KEYERROR);
+                return c;
+            };
+            const acc_t c0 = pick(j0), c1 = pick(j1), c2 = pick(j2), c3 = pick(j3);
+            emit_row(row, c0, c1, c2, c3);
+            if (rev >= 0) emit_row(rev, c0, c1, c2, c3);
+            else if ((c0 | c1 | c2 | c3) != 0) atomicMax(&misc[2], (int)GSN_ST_KEYERROR);
             COUNT_ARM(3, t0f);
         }
     } else {
@@ -938,8 +1027,16 @@ __device__ __forceinline__ int count_body(const CountArgs &a, unsigned char *sme
 #ifndef COUNT_W4_WAVES
 #define COUNT_W4_WAVES 1
 #endif
+// Register bound of the cycle instantiation (CYC > 0): one-wave workgroups of dependent LDS round trips, a ZINC pair in ~4 KiB of LDS -- 32
+// workgroups fit a CU, so the register file decides how many are resident.  8 waves per SIMD = 64 registers: it takes 55, no spill, no
+// scratch (profiles/count_resources_after.txt; 95 registers = 5 waves before).  What brought it there is marked "CYC:" in count_body
+// -- error-path zeros without 64-bit quotients, arguments read where they are used, whole-row staging from 32-bit counters,
+// the 2-core in a register, the lane id opaque per pass; side_block, which shares the kernel, fits the bound as it is.
+#ifndef COUNT_CYC_WAVES
+#define COUNT_CYC_WAVES 8
+#endif
 template <int W, int T, bool DIR, bool TAIL, bool MOL = false, int CYC = 0>
-__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(DIR ? 1 : (W == 1 ? COUNT_W1_WAVES : (W == 2 ? COUNT_W2_WAVES : (W == 4 ? COUNT_W4_WAVES : 1))))))
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(CYC > 0 ? COUNT_CYC_WAVES : DIR ? 1 : (W == 1 ? COUNT_W1_WAVES : (W == 2 ? COUNT_W2_WAVES : (W == 4 ? COUNT_W4_WAVES : 1))))))
 void count_kernel(CountArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int bid = (int)blockIdx.x;
@@ -966,7 +1063,9 @@ void count_kernel(CountArgs a) {
     for (int pass = 0; pass < 3; ++pass) {
         const int g = pass == 2 ? g0 + 1 : g0;
         const int ng = (pass == 0 && two) ? 2 : 1;
-        const int rc = count_body<W, T, DIR, TAIL, MOL, CYC>(a, smem, item, (MOL || a.pair) ? 0 : part, g, ng, ng == 1);
+        int rc;
+        if constexpr (CYC > 0) rc = count_body<W, T, DIR, TAIL, MOL, CYC>(*args_late(), smem, item, 0, g, ng, ng == 1);      // (the body reads every field where it uses it)
+        else rc = count_body<W, T, DIR, TAIL, MOL, CYC>(a, smem, item, (MOL || a.pair) ? 0 : part, g, ng, ng == 1);
         if (!two || (pass == 0 && rc == 0)) break;
     }
 }

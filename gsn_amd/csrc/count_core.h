@@ -516,22 +516,26 @@ GSN_HD void cycle_walk_level(const uint64_t *A, const uint64_t au, const uint64_
         }
     }
 }
-// (a path of <= 5 inner steps on 62 free vertices: 62 * 61 * 60 * 59 < 2^32 for L <= 6; 64-bit counters above)
+// (counter width: a cell for length k is at most the number of ordered choices of the k - 2 inner vertices among the 62 others, K64's value;
+//  k = 6: 62 * 61 * 60 * 59 = 13 388 280 < 2^32, so 32 bits hold every count of a one-word graph for L <= 6 -- no launch condition is
+//  needed (tests/test_cycle_counter_width_cpu.py); k = 8: 62 * ... * 57 = 4.4e10 does not fit: 64-bit counters above 6)
 template <int L>
 struct CycleAcc { typedef uint64_t type; };
 template <> struct CycleAcc<3> { typedef uint32_t type; };
 template <> struct CycleAcc<4> { typedef uint32_t type; };
 template <> struct CycleAcc<5> { typedef uint32_t type; };
 template <> struct CycleAcc<6> { typedef uint32_t type; };
-template <int L>
-GSN_HD void cycle_walk(const uint64_t *A, const int u, const int v, const uint64_t mask, uint64_t *cnt /* [L - 2] */) {
+// Out: the caller's counter type -- uint64_t, or CycleAcc<L>::type itself (the kernel: no 64-bit copies of counters that fit 32 bits)
+template <int L, class Out>
+GSN_HD void cycle_walk(const uint64_t *A, const int u, const int v, const uint64_t mask, Out *cnt /* [L - 2] */) {
     static_assert(L >= 3 && L <= GSN_KMAX, "cycle lengths 3 .. GSN_KMAX");
+    static_assert(sizeof(Out) >= sizeof(typename CycleAcc<L>::type), "the caller's counters hold what the walk's do");
     typename CycleAcc<L>::type c[L - 2];
 #pragma unroll
     for (int i = 0; i < L - 2; ++i) c[i] = 0;
     cycle_walk_level<L, 0, typename CycleAcc<L>::type>(A, A[u] & mask, mask, v, (1ull << u) | (1ull << v), c);
 #pragma unroll
-    for (int i = 0; i < L - 2; ++i) cnt[i] = (uint64_t)c[i];
+    for (int i = 0; i < L - 2; ++i) cnt[i] = (Out)c[i];
 }
 
 // Is this plan table a set of such columns?  Judged from the plans' structure, not from pattern names: edge mode, non-induced, undirected
