@@ -175,6 +175,9 @@ SIGNATURES = {
                                           ctypes.POINTER(gsn_dgn_agg), c_int, c_vp, c_int, ctypes.c_double, c_vp, c_vp]),
     "gsn_dgn_aggregate_bwd_hip": (c_int, [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
                                           c_i64, ctypes.POINTER(gsn_dgn_agg), c_int, c_vp, c_int, ctypes.c_double, c_vp, c_vp, c_vp, c_vp]),
+    "gsn_laplacian_eig_hip": (c_int, [c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                      c_i64, c_vp]),
+    "gsn_laplacian_eig_scratch_floats": (c_i64, [c_int, c_i64]),
 }
 
 

@@ -10,6 +10,9 @@ The classes keep the reference's constructor signatures, defaults and state-dict
                               (``'eig'``: the node / edge vector fields, ``'pos_enc'``), the graph of each node and ``snorm_n``.
 * :class:`DGNLayerSimple`, :class:`DGNLayer` (``type_net='simple'`` only), :class:`MLPReadout`, :class:`DGNNet`.
 * :func:`dgn_aggregate`    -- the differentiable aggregation on its own; :func:`avg_degree_log` -- ``avg_d['log']`` (main_HIV.py:359-363).
+* :func:`laplacian_eigenvectors`, :func:`positional_encoding` -- the Laplacian eigenvector fields of data/HIV.py:21-51 (``--directions
+                              eig``, ``pos_enc_dim``) for a whole batch: one launch per size class of csrc/eig.hip instead of one ARPACK
+                              call per graph.
 
 CUDA tensors only: there is no CPU fallback.
 """
@@ -78,8 +81,10 @@ class DGNGraph:
     ``edge_index`` column order (the last Ce columns); ``ndata['pos_enc']`` the optional positional encoding.  ``batch`` int64 [N] is the
     graph of each node (the readout's partition) and ``snorm_n`` [N, 1] = sqrt(1 / |V(graph)|) (data/HIV.py:178-179)."""
 
-    def __init__(self, edge_index, num_nodes, ndata=None, edata=None, batch=None, num_graphs=None, snorm_n=None):
+    def __init__(self, edge_index, num_nodes, ndata=None, edata=None, batch=None, num_graphs=None, snorm_n=None, node_ptr=None,
+                 edge_ptr=None):
         self.edge_index = edge_index
+        self.node_ptr, self.edge_ptr = node_ptr, edge_ptr      # the graphs' vertex / edge ranges (positional_encoding reads them)
         self.num_nodes = int(num_nodes)
         self.ndata = dict(ndata or {})
         self.edata = dict(edata or {})
@@ -101,20 +106,56 @@ class DGNGraph:
         return int(self.edge_index.shape[1])
 
     @classmethod
-    def from_batch(cls, batch, node_field=None, edge_field=None, device="cuda"):
-        """From a collated batch (``gsn_amd.synth.Batch``: node-offset ``edge_index``, ``node_ptr``): the counts a
-        ``counts2ids_batch`` call made for it (or any other field) become ``ndata['eig']`` / ``edata['eig']`` as float32."""
+    def from_batch(cls, batch, node_field=None, edge_field=None, device="cuda", directions=None, norm="none", pos_enc_dim=0, edge_feat=None):
+        """From a collated batch (``gsn_amd.synth.Batch``: node-offset ``edge_index``, ``node_ptr``, ``edge_ptr``).
+
+        ``directions=None``: the counts a ``counts2ids_batch`` call made for the batch (or any other field) become ``ndata['eig']`` /
+        ``edata['eig']`` as float32.  ``directions`` a list: the fields are assembled in the list's order as HIVDGL.__init__ does
+        (data/HIV.py:70-88) -- ``'eig'``: ``positional_encoding(g, 4, norm)``, and ``ndata['pos_enc'] = ndata['eig'][:, 1:pos_enc_dim+1]``
+        when ``pos_enc_dim > 0``; ``'subgraphs'``: ``node_field`` joins ``ndata['eig']`` and ``edge_field`` joins ``edata['eig']`` (the
+        reference's id_scope 'global' / 'local'; both may be given); ``'edge_feat'``: ``edge_feat`` joins ``edata['eig']``."""
+        if directions is not None:
+            if isinstance(directions, str):
+                directions = [directions]
+            for direction in directions:
+                if direction not in ("eig", "subgraphs", "edge_feat"):
+                    raise NotImplementedError("direction {} is not currently supported.".format(direction))     # HIV.py:82
+            if "eig" in directions:
+                _eig_checked_args(4, norm, 16)
+                if pos_enc_dim < 0:
+                    raise ValueError("pos_enc_dim = %r is negative" % (pos_enc_dim,))
+            if "subgraphs" in directions and node_field is None and edge_field is None:
+                raise ValueError("directions has 'subgraphs' but neither node_field nor edge_field is given")
+            if "edge_feat" in directions and edge_feat is None:
+                raise ValueError("directions has 'edge_feat' but edge_feat is None")
         dv = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(device)
         ei = dv(batch.edge_index).to(torch.int64)
-        node_ptr = np.asarray(batch.node_ptr, dtype=np.int64)
+        node_ptr = _host_i64(batch.node_ptr)
         sizes = np.diff(node_ptr)
         gid = np.repeat(np.arange(len(sizes), dtype=np.int64), sizes)
         snorm = np.repeat(np.sqrt(1.0 / np.maximum(sizes, 1).astype(np.float32)), sizes).astype(np.float32)
-        g = cls(ei, int(node_ptr[-1]), batch=dv(gid), num_graphs=len(sizes), snorm_n=dv(snorm).unsqueeze(1))
-        if node_field is not None:
-            g.ndata["eig"] = _as_rows(dv(node_field))
-        if edge_field is not None:
-            g.edata["eig"] = _as_rows(dv(edge_field))
+        edge_ptr = getattr(batch, "edge_ptr", None)
+        g = cls(ei, int(node_ptr[-1]), batch=dv(gid), num_graphs=len(sizes), snorm_n=dv(snorm).unsqueeze(1), node_ptr=node_ptr,
+                edge_ptr=None if edge_ptr is None else _host_i64(edge_ptr))
+        join = lambda d, f: f if "eig" not in d else torch.cat((d["eig"], f), dim=1)
+        if directions is None:
+            if node_field is not None:
+                g.ndata["eig"] = _as_rows(dv(node_field))
+            if edge_field is not None:
+                g.edata["eig"] = _as_rows(dv(edge_field))
+            return g
+        for direction in directions:
+            if direction == "eig":
+                positional_encoding(g, 4, norm)
+                if pos_enc_dim > 0:
+                    g.ndata["pos_enc"] = g.ndata["eig"][:, 1:pos_enc_dim + 1]
+            elif direction == "subgraphs":
+                if node_field is not None:
+                    g.ndata["eig"] = join(g.ndata, _as_rows(dv(node_field)))
+                if edge_field is not None:
+                    g.edata["eig"] = join(g.edata, _as_rows(dv(edge_field)))
+            else:
+                g.edata["eig"] = join(g.edata, _as_rows(dv(edge_feat)))
         return g
 
 
@@ -130,6 +171,124 @@ def avg_degree_log(graphs):
         D = torch.bincount(ei[1].cpu().to(torch.int64), minlength=n).to(torch.float32)
         logs.append(torch.log(D + 1))
     return torch.mean(torch.cat(logs)) if logs else torch.tensor(float("nan"))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Laplacian eigenvector fields (data/HIV.py:21-51)
+# ------------------------------------------------------------------------------------------------------------------
+EIG_NORMS = {"none": 0, "sym": 1, "walk": 2}                     # GSN_EIG_NORM_* (gsn_abi.h)
+EIG_KMAX = 8                                                      # GSN_EIG_KMAX
+EIG_CLASSES = (32, 64, 128, 256)                                  # most vertices per graph of a launch (csrc/eig.hip)
+EIG_MAX_SWEEPS = 64
+ST_OK, ST_KEYERROR, ST_TOO_LARGE, ST_BAD_INDEX, ST_ASYMMETRIC, ST_NO_CONVERGENCE = range(6)    # GSN_ST_*
+
+
+def _host_i64(a):
+    """A graph-pointer array on the host (a device tensor is copied back: pass host arrays to stay asynchronous)."""
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def _eig_checked_args(k, norm, max_sweeps):
+    if norm not in EIG_NORMS:
+        raise ValueError("norm = %r: the Laplacians of data/HIV.py:28-36 are 'none', 'sym' and 'walk'" % (norm,))
+    if not isinstance(k, (int, np.integer)) or isinstance(k, bool) or not 1 <= k <= EIG_KMAX:
+        raise ValueError("k = %r: 1 .. %d eigenvectors" % (k, EIG_KMAX))
+    if not isinstance(max_sweeps, (int, np.integer)) or isinstance(max_sweeps, bool) or not 1 <= max_sweeps <= EIG_MAX_SWEEPS:
+        raise ValueError("max_sweeps = %r: 1 .. %d" % (max_sweeps, EIG_MAX_SWEEPS))
+    return int(k), EIG_NORMS[norm], int(max_sweeps)
+
+
+def _raise_eig_status(status, sizes):
+    st = status.cpu().numpy()
+    bad = np.flatnonzero(st)
+    if bad.size == 0:
+        return
+    g, code = int(bad[0]), int(st[bad[0]])
+    if code == ST_ASYMMETRIC:
+        raise ValueError("laplacian_eigenvectors: graph %d has an arc without its reverse (only symmetric arc sets are solved)" % g)
+    if code == ST_TOO_LARGE:
+        raise ValueError("laplacian_eigenvectors: graph %d has %d vertices (at most %d)" % (g, int(sizes[g]), EIG_CLASSES[-1]))
+    if code == ST_BAD_INDEX:
+        raise IndexError("laplacian_eigenvectors: graph %d has an edge end outside its own vertices" % g)
+    raise RuntimeError("laplacian_eigenvectors: graph %d did not converge within max_sweeps (status %d)" % (g, code))
+
+
+def laplacian_eigenvectors(batch, k=4, norm="none", max_sweeps=16, check=True, return_values=False, device="cuda", return_sweeps=False):
+    """The ``k`` eigenvectors of smallest eigenvalue of every graph's Laplacian (data/HIV.py:21-51: 'none' D - A, 'sym'
+    I - D^-1/2 A D^-1/2, 'walk' I - D^-1 A with D the in-degree clipped at 1), increasing eigenvalue: float32 [N, k] on the device.
+
+    ``batch``: a collated batch (``node_ptr``, ``edge_ptr``, node-offset ``edge_index``; host arrays keep the call asynchronous) or a
+    :class:`DGNGraph` made by ``from_batch`` (``device`` is then the graph's).  Each vector has unit 2-norm and its component of largest
+    magnitude is positive (lowest vertex on ties); inside an eigenspace the choice of basis is the solver's (deterministic: two calls
+    give the same bits), so compare subspaces, never elements, with another solver's output.  A graph with fewer than ``k`` vertices has
+    zero vectors (NaN eigenvalues) in the missing columns.  Arc sets must be symmetric and graphs have at most 256 vertices.
+
+    Returns ``vec`` [, ``val`` float32 [G, k] if ``return_values``] [, ``status`` int32 [G] if not ``check``] [, ``sweeps`` int32 [G] if
+    ``return_sweeps``].  ``check=True`` reads the status words back once and raises ValueError (asymmetric, too large), IndexError (an
+    edge end outside its graph) or RuntimeError (no convergence within ``max_sweeps`` Jacobi sweeps), naming the first such graph;
+    ``check=False`` never synchronises: the graphs with a status have zero rows (no convergence: the last iterate)."""
+    k, norm_code, max_sweeps = _eig_checked_args(k, norm, max_sweeps)
+    if isinstance(batch, DGNGraph):
+        device = batch.edge_index.device
+    if batch.node_ptr is None or getattr(batch, "edge_ptr", None) is None:
+        raise ValueError("laplacian_eigenvectors: the graph carries no node_ptr / edge_ptr (build it with DGNGraph.from_batch)")
+    node_ptr, edge_ptr = _host_i64(batch.node_ptr), _host_i64(batch.edge_ptr)
+    G = len(node_ptr) - 1
+    if G < 0 or len(edge_ptr) != G + 1 or (G >= 0 and node_ptr[0] != 0) or np.any(np.diff(node_ptr) < 0) or np.any(np.diff(edge_ptr) < 0):
+        raise ValueError("laplacian_eigenvectors: node_ptr / edge_ptr must be non-decreasing [G + 1] arrays starting at 0")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("laplacian_eigenvectors: device %s -- the solver is a HIP kernel and there is no CPU fallback" % (device,))
+    _abi.require_gpu()
+    N = int(node_ptr[-1])
+    sizes = np.diff(node_ptr)
+    ei = batch.edge_index if isinstance(batch.edge_index, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(batch.edge_index))
+    if ei.dim() != 2 or ei.shape[0] != 2 or ei.shape[1] != int(edge_ptr[-1]):
+        raise ValueError("laplacian_eigenvectors: edge_index must be [2, %d] (edge_ptr[-1]), got %s" % (int(edge_ptr[-1]), list(ei.shape)))
+    vec = torch.empty(N, k, dtype=torch.float32, device=device)
+    val = torch.full((max(G, 0), k), float("nan"), dtype=torch.float32, device=device)
+    status = torch.zeros(max(G, 0), dtype=torch.int32, device=device)
+    sweeps = torch.zeros(max(G, 0), dtype=torch.int32, device=device)
+    if G > 0 and N > 0:
+        ei = ei.to(device=device, dtype=torch.int64).contiguous()
+        E = ei.shape[1]
+        npt, ept = torch.from_numpy(node_ptr).to(device), torch.from_numpy(edge_ptr).to(device)
+        # one launch per size class; a graph beyond the largest class rides in the first launch, whose kernel refuses it (zero rows)
+        cls_of = np.searchsorted(np.asarray(EIG_CLASSES), sizes, side="left")
+        used = sorted(set(int(c) for c in cls_of if c < len(EIG_CLASSES))) or [0]
+        cls_of = np.where(cls_of >= len(EIG_CLASSES), used[0], cls_of)
+        with _abi.device_guard(device):
+            for c in used:
+                ids_h = np.flatnonzero(cls_of == c).astype(np.int32)
+                ids = None if len(ids_h) == G else torch.from_numpy(ids_h).to(device)
+                n_scr = int(_abi.lib().gsn_laplacian_eig_scratch_floats(EIG_CLASSES[c], len(ids_h)))
+                scratch = torch.empty(n_scr, dtype=torch.float32, device=device) if n_scr else None
+                with _timed("laplacian_eig_%d" % EIG_CLASSES[c], 0.0):
+                    rc = _abi.lib().gsn_laplacian_eig_hip(G, _abi.ptr(npt), _abi.ptr(ept), _abi.ptr(ei) if E else None, E, _abi.ptr(ids),
+                                                          len(ids_h), EIG_CLASSES[c], norm_code, k, max_sweeps, _abi.ptr(vec), _abi.ptr(val),
+                                                          _abi.ptr(status), _abi.ptr(sweeps), _abi.ptr(scratch), n_scr,
+                                                          _abi.current_stream())
+                _abi.check(rc, "gsn_laplacian_eig_hip")
+        if check:
+            _raise_eig_status(status, sizes)
+    out = [vec]
+    if return_values:
+        out.append(val)
+    if not check:
+        out.append(status)
+    if return_sweeps:
+        out.append(sweeps)
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def positional_encoding(g, pos_enc_dim, norm):
+    """data/HIV.py:21-51 on a :class:`DGNGraph`: the ``pos_enc_dim`` Laplacian eigenvectors of smallest eigenvalue of every graph become
+    (or are concatenated behind) ``g.ndata['eig']``; returns ``g``."""
+    scalar_field = laplacian_eigenvectors(g, k=pos_enc_dim, norm=norm)
+    g.ndata["eig"] = scalar_field if "eig" not in g.ndata else torch.cat((g.ndata["eig"], scalar_field), dim=1)
+    return g
 
 
 # ------------------------------------------------------------------------------------------------------------------

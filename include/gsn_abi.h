@@ -45,7 +45,9 @@ enum {
     GSN_ST_KEYERROR = 1, /* a match uses an edge direction that is not a column of edge_index: the reference raises
                             KeyError at utils_graph_processing.py:173 */
     GSN_ST_TOO_LARGE = 2, /* graph exceeds max_nodes / max_edges given to the call */
-    GSN_ST_BAD_INDEX = 3  /* a vertex id outside [0, num_nodes) */
+    GSN_ST_BAD_INDEX = 3, /* a vertex id outside [0, num_nodes) */
+    GSN_ST_ASYMMETRIC = 4,     /* gsn_laplacian_eig_hip: the graph's arc set is not symmetric (A != A^T) */
+    GSN_ST_NO_CONVERGENCE = 5  /* gsn_laplacian_eig_hip: not converged after max_sweeps sweeps (the rows hold the last iterate) */
 };
 
 const char *gsn_last_error(void);
@@ -827,6 +829,34 @@ int gsn_dgn_aggregate_bwd_hip(int64_t n_nodes, int64_t n_edges, int64_t d, const
                               int64_t node_stride, int64_t node_width, const float *edge_field, int64_t edge_stride, int64_t edge_width,
                               const gsn_dgn_agg *aggs, int n_aggs, const int32_t *scalers, int n_scalers, double avg_d_log,
                               const float *grad_out, float *grad_msg, float *grad_h, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Laplacian eigenvector fields of the directional GSN (directional_gsn/data/HIV.py:21-51, positional_encoding: scipy's ARPACK once per
+ * graph).  For every graph of the launch, with A[u, v] = number of arcs u -> v (duplicates add, self loops count) and
+ * d = max(in-degree, 1):   norm NONE: L = diag(d) - A    SYM: L = I - D^-1/2 A D^-1/2    WALK: L = I - D^-1 A,
+ * the k (1 .. GSN_EIG_KMAX) eigenpairs of smallest eigenvalue in increasing order (equal eigenvalues in the solver's own, deterministic
+ * order):  vec fp32 [N, k] row-major (row node_ptr[g] + i: vertex i of graph g), val fp32 [G, k].  Every vector has unit 2-norm and its
+ * component of largest magnitude is positive (lowest vertex on exact ties).  A graph with n < k vertices gets zero vectors and NaN values
+ * in columns j >= n.  Two runs give the same bits.
+ *   node_ptr / edge_ptr   int64 device [G + 1] (G = n_graphs_total), edge_index int64 device [2, n_edges] with batch-global vertex ids: the
+ *                         arrays gsn_count_layer_step_hip takes
+ *   graph_ids, n_ids      the graphs of this launch (int32 device, no id twice), or NULL: all G graphs
+ *   n_class               32, 64, 128 or 256: the most vertices a graph of this launch may have.  32 .. 128 solve in LDS; 256 solves in
+ *                         `scratch`, gsn_laplacian_eig_scratch_floats(256, n_ids) floats of device memory (0 for the other classes)
+ *   max_sweeps            1 .. 64: the bound of the Jacobi iteration
+ *   status                int32 device [G], written for every graph of the launch: GSN_ST_OK; GSN_ST_TOO_LARGE (more than n_class
+ *                         vertices), GSN_ST_BAD_INDEX (an arc end outside the graph's vertices, or node_ptr outside the batch) and
+ *                         GSN_ST_ASYMMETRIC (A != A^T) with zero rows and NaN values; GSN_ST_NO_CONVERGENCE with the last iterate's rows
+ *   sweeps_used           int32 device [G] or NULL: the sweeps each graph ran
+ * One workgroup per graph, one launch per call, asynchronous on `stream`; graphs outside the launch keep their rows.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define GSN_EIG_KMAX 8
+enum { GSN_EIG_NORM_NONE = 0, GSN_EIG_NORM_SYM = 1, GSN_EIG_NORM_WALK = 2 };
+int gsn_laplacian_eig_hip(int64_t n_graphs_total, const int64_t *node_ptr, const int64_t *edge_ptr, const int64_t *edge_index,
+                          int64_t n_edges, const int32_t *graph_ids, int64_t n_ids, int n_class, int norm, int k, int max_sweeps,
+                          float *vec, float *val, int32_t *status, int32_t *sweeps_used, float *scratch, int64_t scratch_floats,
+                          void *stream);
+int64_t gsn_laplacian_eig_scratch_floats(int n_class, int64_t n_ids);
 
 #ifdef __cplusplus
 }
