@@ -21,24 +21,34 @@
 
 namespace gsn {
 
+// Both forms keep the RELATIVE accuracy of a small derivative (a saturated unit): the column sums of gZ are held to a few 2^-24 of
+// sum_r |gZ| (tests/test_bn_kernels_gpu.py), and 1 - y * y rounds y * y against 1 -- an absolute 2^-24 whatever is left of the difference.
 __device__ __forceinline__ float act_grad_from_y(float y, int act) {
     switch (act) {
         case 1: return y > 0.f ? 1.f : 0.f;
-        case 2: return y > 0.f ? 1.f : y + 1.f;          // elu: d/dz (e^z - 1) = y + 1 for z <= 0
-        case 3: return 1.f - y * y;                      // tanh
+        case 2: return y > 0.f ? 1.f : y + 1.f;          // elu: d/dz (e^z - 1) = y + 1 for z <= 0  (exact for y <= -0.5)
+        case 3: return (1.f - y) * (1.f + y);            // tanh: 1 - y^2, factored (1 - y is exact for y >= 0.5, 1 + y for y <= -0.5)
         default: return 1.f;
     }
 }
 
-// the same derivative from the pre-activation value z (the stage output is not read: z is recomputed from the pre-BatchNorm rows with the
-// forward pass's own expression, bn_act_kernel in encode.hip)
-__device__ __forceinline__ float act_grad_from_z(float z, int act) {
-    switch (act) {
-        case 1: return z > 0.f ? 1.f : 0.f;
-        case 2: return z > 0.f ? 1.f : expm1f(z) + 1.f;
-        case 3: { const float t = tanhf(z); return 1.f - t * t; }
-        default: return 1.f;
-    }
+// the same derivative from the pre-BatchNorm value h (the stage output is not read): z = (h - mean) * scale + shift is recomputed in fp32 as the
+// forward pass does (bn_act_kernel in encode.hip), which also decides the side of relu / elu.  A saturated unit answers the rounding of z
+// itself -- 2^-24 (|(h - mean) scale| + |z|) -- with a RELATIVE error 2 |tanh z| dz of sech^2 z (dz of e^z), so what the three roundings of z
+// dropped (zl: each error exact in fp32 -- two two-sums and the residual of the product -- hence no contraction in here) is put back to first
+// order, d/dz sech^2 z = -2 tanh z sech^2 z.  fp32 only: the plane kernel below has no register to spare for fp64 temporaries.
+__device__ __forceinline__ float act_grad_from_h(float hv, float mu, float sc, float sh, int act) {
+#pragma clang fp contract(off)
+    const float p = hv - mu, pr = p * sc, z = pr + sh;
+    if (act < 2) return (act == 1 && !(z > 0.f)) ? 0.f : 1.f;
+    const float b1 = p - hv, e1 = (hv - (p - b1)) + (-mu - b1);                      // (h - mean) - p
+    const float e2 = fmaf(p, sc, -pr);                                               // p * scale - pr
+    const float b3 = z - pr, e3 = (pr - (z - b3)) + (sh - b3);                       // (pr + shift) - z
+    const float zl = e3 + e2 + e1 * sc;
+    if (act == 2) return z > 0.f ? 1.f : expf(z) * (1.f + zl);                       // (not expm1f(z) + 1: that sum rounds against 1)
+    const float u = expf(-2.f * fabsf(z)), d = 1.f + u;                              // sech^2 z = 4 u / (1 + u)^2, u = e^(-2 |z|)  (not 1 - tanhf(z)^2)
+    const float t = copysignf((1.f - u) / d, z);
+    return 4.f * u / (d * d) * (1.f - 2.f * t * zl);
 }
 
 // pass 1: column sums of gZ and gZ * xh (fp64 [2][C], caller zero-fills).  grid (blocks_x, ceil(C/64)); a wave covers 64
@@ -66,14 +76,14 @@ __global__ __launch_bounds__(256) void bn_act_bwd_reduce_kernel(int64_t m_rows, 
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const float gz = g4[u] * (y ? act_grad_from_y(y4[u], act) : act_grad_from_z((h4[u] - mu) * zs + zb, act));
+                const float gz = g4[u] * (y ? act_grad_from_y(y4[u], act) : act_grad_from_h(h4[u], mu, zs, zb, act));
                 s1 += (double)gz;
                 s2 += (double)gz * (double)((h4[u] - mu) * is);
             }
         }
         for (; r < m_rows; r += step) {
             const int64_t i = r * n_cols + c;
-            const float gz = gy[i] * (y ? act_grad_from_y(y[i], act) : act_grad_from_z((h[i] - mu) * zs + zb, act));
+            const float gz = gy[i] * (y ? act_grad_from_y(y[i], act) : act_grad_from_h(h[i], mu, zs, zb, act));
             s1 += (double)gz;
             s2 += (double)gz * (double)((h[i] - mu) * is);
         }
@@ -110,7 +120,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(int64_t m_rows, i
         int64_t r = (int64_t)blockIdx.x * 4 + wave;
         const bool need_h = !y || sums;
         auto one = [&](int64_t i, float gyv, float yv, float hv) {
-            const float gz = gyv * (y ? act_grad_from_y(yv, act) : act_grad_from_z((hv - mu) * cf + zb, act));
+            const float gz = gyv * (y ? act_grad_from_y(yv, act) : act_grad_from_h(hv, mu, cf, zb, act));
             float g = gz;
             if (sums) g = gz - m1 - (hv - mu) * is * m2;
             g *= cf;
@@ -241,7 +251,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BP_WAVES, B
                 const float4 cf = *reinterpret_cast<const float4 *>(bp_tab + 2 * kp + 4 * c), zb = *reinterpret_cast<const float4 *>(bp_tab + 3 * kp + 4 * c);
                 const float4 m1 = *reinterpret_cast<const float4 *>(bp_tab + 4 * kp + 4 * c), m2 = *reinterpret_cast<const float4 *>(bp_tab + 5 * kp + 4 * c);
                 auto one = [&](float gyv, float hv, float mu_, float is_, float cf_, float zb_, float m1_, float m2_) {
-                    const float gz = gyv * act_grad_from_z((hv - mu_) * cf_ + zb_, act);
+                    const float gz = gyv * act_grad_from_h(hv, mu_, cf_, zb_, act);
                     float g_ = gz;
                     if (train) g_ = gz - m1_ - (hv - mu_) * is_ * m2_;
                     return g_ * cf_;
