@@ -57,6 +57,55 @@ int current_device() {
     if (hipGetDevice(&dev) != hipSuccess) return -1;
     return dev;
 }
+
+int lds_limit(DeviceOnce *once, std::initializer_list<const void *> kernels, const char *label, int bytes) {
+    const int dev = once ? current_device() : -1;
+    if (once && once->done(dev)) return GSN_OK;
+    char sized[32];
+    if (!label) { snprintf(sized, sizeof(sized), "%d B LDS", bytes); label = sized; }
+    for (const void *k : kernels) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(%s): %s", label, hipGetErrorString(e));
+    }
+    if (once) once->mark(dev);
+    return GSN_OK;
+}
+
+int launch_check(const char *label_fmt, ...) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return GSN_OK;
+    char label[256];
+    va_list ap;
+    va_start(ap, label_fmt);
+    vsnprintf(label, sizeof(label), label_fmt, ap);
+    va_end(ap);
+    return set_error(GSN_E_HIP, "%s: %s", label, hipGetErrorString(e));
+}
+
+void trace(const char *fmt, ...) {
+    if (!sw_present(SW_CHAIN_TRACE)) return;
+    va_list ap;
+    va_start(ap, fmt);
+    vfprintf(stderr, fmt, ap);
+    va_end(ap);
+}
+
+ProfCounters::ProfCounters(size_t n, void *stream) {
+    n_ = n;
+    if (n == 0 || hipMalloc(&dev_, n * sizeof(unsigned long long)) != hipSuccess) { dev_ = nullptr; return; }
+    (void)hipMemsetAsync(dev_, 0, n * sizeof(unsigned long long), reinterpret_cast<hipStream_t>(stream));
+}
+ProfCounters::~ProfCounters() { if (dev_) (void)hipFree(dev_); }
+std::vector<unsigned long long> ProfCounters::fetch(void *stream) {
+    std::vector<unsigned long long> h(n_, 0ull);
+    (void)hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream));
+    if (dev_) {
+        (void)hipMemcpy(h.data(), dev_, n_ * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+        (void)hipFree(dev_);
+        dev_ = nullptr;
+    }
+    return h;
+}
 }  // namespace gsn
 
 // HP-1 + HP-2 in one host call (include/gsn_abi.h: gsn_count_layer_step_hip): the counting launch with its side outputs, then layer 0 on the packs

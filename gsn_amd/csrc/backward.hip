@@ -800,9 +800,7 @@ static int bn_act_bwd_launch(int64_t m_rows, int64_t n_cols, const float *grad_y
     // (y == null: both train_bn modes read the pre-BatchNorm rows for the activation derivative)
     hipLaunchKernelGGL(bn_act_bwd_apply_kernel, grid, dim3(256), 0, s, m_rows, (int)n_cols, grad_y, y, (train_bn == 1 || !y) ? h : y, mean,
                        invstd, coef, train_bn == 1 ? sums : nullptr, act, grad_h, grad_bias, shift);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "bn_act_bwd kernels: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("bn_act_bwd kernels");
 }
 
 extern "C" int gsn_bn_act_bwd_hip(int64_t m_rows, int64_t n_cols, const float *grad_y, const float *y, const float *h,
@@ -841,12 +839,10 @@ extern "C" int gsn_bn_act_bwd_planes_hip(int64_t m_rows, int64_t n_cols, const f
     a.gy = grad_y; a.h = h; a.mean = mean; a.invstd = invstd; a.coef = coef; a.shift = shift; a.sums = sums;
     a.rowinv = row_scratch; a.planes = reinterpret_cast<unsigned char *>(row_scratch + a.m_pad); a.gbias = grad_bias;
     int64_t gx = a.m_pad / 32;
-    static const int64_t wgs = [] { const char *e = getenv("GSN_BWD_PLANES_WGS"); const int64_t v = e ? atoll(e) : 0; return v > 0 ? v : (int64_t)2048; }();
+    const int64_t wgs_env = sw_int64(SW_BWD_PLANES_WGS, 0), wgs = wgs_env > 0 ? wgs_env : 2048;
     if (gx > wgs) gx = wgs;
     hipLaunchKernelGGL(bn_act_bwd_planes_kernel, dim3((unsigned)gx), dim3(256), (size_t)6 * a.k_pad * 4, s, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "bn_act_bwd_planes kernels: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("bn_act_bwd_planes kernels");
 }
 
 // gsn_bn_act_hip for a stage output that is read as fp16 planes: row_scratch = the row scratch of Y (gsn_linear_f16x3_scratch_bytes(m_rows, n_cols)),
@@ -864,12 +860,10 @@ extern "C" int gsn_bn_act_planes_hip(int64_t m_rows, int64_t n_cols, const float
     a.h = h; a.mean = mean; a.scale = scale; a.shift = shift; a.out = out;
     a.rowinv = row_scratch; a.planes = reinterpret_cast<unsigned char *>(row_scratch + a.m_pad);
     int64_t gx = a.m_pad / 32;
-    static const int64_t wgs = [] { const char *e = getenv("GSN_FWD_PLANES_WGS"); const int64_t v = e ? atoll(e) : 0; return v > 0 ? v : (int64_t)2048; }();
+    const int64_t wgs_env = sw_int64(SW_FWD_PLANES_WGS, 0), wgs = wgs_env > 0 ? wgs_env : 2048;
     if (gx > wgs) gx = wgs;
     hipLaunchKernelGGL(bn_act_planes_kernel, dim3((unsigned)gx), dim3(256), (size_t)3 * a.k_pad * 4, reinterpret_cast<hipStream_t>(stream), a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "bn_act_planes_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("bn_act_planes_kernel");
 }
 
 // rows per slab of a weight-gradient call (both kernels): see gsn_wgrad_hip.  wg_target > 0: the r05 rule with that many workgroups asked for
@@ -916,16 +910,15 @@ extern "C" int gsn_wgrad_hip(int64_t m_rows, int64_t n_out, const float *grad_h,
     // slabs up to 65 536 rows: 1 410 workgroups in three rounds at M = 6 000 x 300 x 600, 82 us; one round of 360: 41 us (M = 4 096: 61 -> 33 us,
     // profiles/r06_wgrad16_phase.txt).  Large calls: 2 048 workgroups for balance, their slabs are longer than 512 rows by themselves.
     // GSN_WGRAD_WGS=n: n workgroups per call asked for, as in r05 (A/B)
-    static const int64_t wg_target = [] { const char *e = getenv("GSN_WGRAD_WGS"); const int64_t v = e ? atoll(e) : 0; return v > 0 ? v : (int64_t)0; }();
+    const int64_t wg_target_env = sw_int64(SW_WGRAD_WGS, 0), wg_target = wg_target_env > 0 ? wg_target_env : 0;
     int64_t rows_per = gsn_wgrad_slab_rows(m_rows, (int64_t)tn * tk, wg_target);
     rows_per = (rows_per + WG_RB - 1) / WG_RB * WG_RB;
     a.rows_per_wg = rows_per;
     int64_t slabs = (m_rows + rows_per - 1) / rows_per;
-    if (getenv("GSN_CHAIN_TRACE"))
-        fprintf(stderr, "gsn wgrad: M %lld N %d K %d blocks %d%s slabs %lld x %lld rows\n", (long long)m_rows, (int)n_out, k, n_blocks, gathered ? " gathered" : "",
+    trace("gsn wgrad: M %lld N %d K %d blocks %d%s slabs %lld x %lld rows\n", (long long)m_rows, (int)n_out, k, n_blocks, gathered ? " gathered" : "",
                 (long long)slabs, (long long)rows_per);
     // GSN_WGRAD_FP32=1: the fp32-MFMA kernel (v_mfma_f32_32x32x2_f32), for A/B runs
-    static const bool fp32_kernel = [] { const char *e = getenv("GSN_WGRAD_FP32"); return e && e[0] == '1'; }();
+    const bool fp32_kernel = sw_on(SW_WGRAD_FP32, false);
     if (fp32_kernel && !gathered)      // (gathered blocks: the bf16 kernel only)
         hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)slabs, (unsigned)tn, (unsigned)tk), dim3(256), 0,
                            reinterpret_cast<hipStream_t>(stream), a);
@@ -933,7 +926,7 @@ extern "C" int gsn_wgrad_hip(int64_t m_rows, int64_t n_out, const float *grad_h,
         a.tn = tn; a.tk = tk;
         const int64_t slab_groups = (slabs + 7) / 8;
         // GSN_WGRAD_PIPE: 0 = the kernel above for plain rows too; 4 / 5 / 6 = vector instructions asked for behind each MFMA (default 6; config-4 step on one box: off 19.71, 4: 19.43, 5: 19.22, 6: 19.06-19.21 ms)
-        static const int pipe = [] { const char *e = getenv("GSN_WGRAD_PIPE"); const int v = e ? atoi(e) : 6; return v == 1 ? 6 : v; }();
+        const int pipe_env = sw_int(SW_WGRAD_PIPE, 6), pipe = pipe_env == 1 ? 6 : pipe_env;
         const dim3 grid((unsigned)(slab_groups * tn * tk * 8));
         hipStream_t st = reinterpret_cast<hipStream_t>(stream);
         if (gathered && pipe) hipLaunchKernelGGL((wgrad_bf16_pipe_kernel<false, 6, true>), grid, dim3(256), 0, st, a);
@@ -946,7 +939,5 @@ extern "C" int gsn_wgrad_hip(int64_t m_rows, int64_t n_out, const float *grad_h,
         else if (pipe) hipLaunchKernelGGL((wgrad_bf16_pipe_kernel<false, 6>), grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL(wgrad_bf16_kernel<false>, dim3((unsigned)(slab_groups * tn * tk * 8)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "wgrad_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("wgrad_kernel");
 }

@@ -384,8 +384,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, WP
 }
 
 void chain_trace(const char *kernel, const ChainArgs &a) {
-    static const bool on = [] { const char *d = getenv("GSN_CHAIN_TRACE"); return d && atoi(d) != 0; }();
-    if (on) fprintf(stderr, "gsn_chain_launch %s m_rows=%lld k0=%d n_out=%d stages=%d\n", kernel, (long long)a.m_rows, a.st[0].k_total, a.st[a.n_stages - 1].n_out, a.n_stages);
+    trace("gsn_chain_launch %s m_rows=%lld k0=%d n_out=%d stages=%d\n", kernel, (long long)a.m_rows, a.st[0].k_total, a.st[a.n_stages - 1].n_out, a.n_stages);
 }
 
 template <int NST, int CH0, int CH1, bool STATS, bool SEG>
@@ -396,22 +395,14 @@ static int launch_chain_impl(const ChainArgs &a, hipStream_t st) {
     const void *fn = reinterpret_cast<const void *>(&mlp_chain_kernel<NST, CH0, CH1, STATS, WPE, SEG, NW>);
     const size_t lds = (size_t)2 * CBM * a.pitch * 4 + 3 * RS_STRIDE * 4;
     static DeviceOnce attr_set;
-    const int attr_dev = current_device();
-    if (!attr_set.done(attr_dev)) {
-        hipError_t e0 = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e0 != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(mlp_chain_kernel): %s", hipGetErrorString(e0));
-        attr_set.mark(attr_dev);
-    }
+    if (int rc = lds_limit(&attr_set, {fn}, "mlp_chain_kernel")) return rc;
     const int64_t n_tiles = (a.m_rows + CBM - 1) / CBM;
-    int per_cu = (SMALL && lds <= 76 * 1024) ? 2 : 1;
-    { const char *d = getenv("GSN_CHAIN_PERCU"); if (d) per_cu = atoi(d); }
+    const int per_cu = sw_int(SW_CHAIN_PERCU, (SMALL && lds <= 76 * 1024) ? 2 : 1);
     int64_t gx = 256 * per_cu;
     if (gx > n_tiles) gx = n_tiles;
     chain_trace(STATS ? "mlp_chain_kernel(stats)" : (SEG ? "mlp_chain_kernel(seg)" : "mlp_chain_kernel"), a);
     hipLaunchKernelGGL((mlp_chain_kernel<NST, CH0, CH1, STATS, WPE, SEG, NW>), dim3((unsigned)gx), dim3(64 * NW), lds, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "mlp_chain_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("mlp_chain_kernel");
 }
 
 template <int NST, int CH0, int CH1>
@@ -453,7 +444,7 @@ extern "C" int gsn_mlp_chain_fwd_hip(int64_t m_rows, int n_stages, const gsn_cha
     ChainArgs a{};
     a.m_rows = m_rows; a.n_stages = n_stages; a.row_perm = row_perm; a.out = out; a.stats = stats;
     a.seg_target = stats ? nullptr : seg_target;
-    { const char *d = getenv("GSN_CHAIN_DBG"); a.dbg = d ? atoi(d) : 0; }
+    a.dbg = sw_int(SW_CHAIN_DBG, 0);
     int nb = 0, kmax = 0;
     for (int s = 0; s < n_stages; ++s) {
         const gsn_chain_stage &g = stages[s];

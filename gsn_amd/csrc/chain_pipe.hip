@@ -226,27 +226,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 template <int CH0, int CH1>
 static int launch_pipe_impl(const ChainArgs &a, int pin, int pmid, size_t lds, hipStream_t st) {
     static DeviceOnce attr_set;
-    const int attr_dev = current_device();
-    if (!attr_set.done(attr_dev)) {
-        hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(&mlp_chain2_pipe_kernel<CH0, CH1>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e0 != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(mlp_chain2_pipe_kernel): %s", hipGetErrorString(e0));
-        attr_set.mark(attr_dev);
-    }
+    if (int rc = lds_limit(&attr_set, {kernel_ptr(&mlp_chain2_pipe_kernel<CH0, CH1>)}, "mlp_chain2_pipe_kernel")) return rc;
     const int64_t n_tiles = (a.m_rows + CBM - 1) / CBM;
     int64_t gx = 256;
     if (gx > n_tiles) gx = n_tiles;
     chain_trace("mlp_chain2_pipe_kernel", a);
     hipLaunchKernelGGL((mlp_chain2_pipe_kernel<CH0, CH1>), dim3((unsigned)gx), dim3(512), lds, st, a, pin, pmid);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "mlp_chain2_pipe_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("mlp_chain2_pipe_kernel");
 }
 
 // Returns GSN_OK after launching, or 1 if this shape is not covered (the caller then uses chain.hip's kernel).
 int launch_chain2_pipe(const ChainArgs &a, int maxch, hipStream_t st) {
     if (a.n_stages != 2 || a.stats || a.seg_target) return 1;
-    { const char *d = getenv("GSN_CHAIN_PIPE"); if (d && atoi(d) == 0) return 1; }
+    if (!sw_on(SW_CHAIN_PIPE, true)) return 1;
     const int pin = ((maxch * CHK + 31) / 32 * 32) | 1;
     // (the matrix loop reads whole CHK-column chunks: a pitch below the padded width lets the last row of a tile read past the
     //  tile -- into the row-source table behind the second MID tile, whose -1 entries are NaNs as floats: NaN x 0 weights)

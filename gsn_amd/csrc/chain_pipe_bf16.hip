@@ -390,29 +390,19 @@ static int launch_pipe_bf_impl(const ChainArgs &a, hipStream_t st) {
     constexpr size_t lds = ((size_t)6 * (32 * (NK0 * 16 + 8) / 2) + (size_t)6 * (32 * (NK1 * 16 + 8) / 2)) * 4;
     static_assert(lds <= 160 * 1024, "LDS budget");
     static DeviceOnce attr_set;
-    const int attr_dev = current_device();
-    if (!attr_set.done(attr_dev)) {
-        hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(&mlp_chain2_pipe_bf16_kernel<NK0, NK1, VEC4, PROF>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e0 != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(mlp_chain2_pipe_bf16_kernel): %s", hipGetErrorString(e0));
-        attr_set.mark(attr_dev);
-    }
-    unsigned long long *prof = nullptr;
-    if (PROF) { (void)hipMalloc(&prof, 8 * 6 * 8); (void)hipMemset(prof, 0, 8 * 6 * 8); }
+    if (int rc = lds_limit(&attr_set, {kernel_ptr(&mlp_chain2_pipe_bf16_kernel<NK0, NK1, VEC4, PROF>)}, "mlp_chain2_pipe_bf16_kernel")) return rc;
+    ProfCounters prof(PROF ? 8 * 6 : 0, st);
     const int64_t n_tiles = (a.m_rows + 31) / 32;
     int64_t gx = 256;
     if (gx > n_tiles) gx = n_tiles;
     chain_trace("mlp_chain2_pipe_bf16_kernel", a);
-    hipLaunchKernelGGL((mlp_chain2_pipe_bf16_kernel<NK0, NK1, VEC4, PROF>), dim3((unsigned)gx), dim3(512), lds, st, a, prof);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "mlp_chain2_pipe_bf16_kernel: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL((mlp_chain2_pipe_bf16_kernel<NK0, NK1, VEC4, PROF>), dim3((unsigned)gx), dim3(512), lds, st, a, prof.ptr());
+    if (int rc = launch_check("mlp_chain2_pipe_bf16_kernel")) return rc;
     if (PROF) {
-        unsigned long long h[8 * 6];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpy(h, prof, sizeof(h), hipMemcpyDeviceToHost);
-        (void)hipFree(prof);
-        static int shown = 0;
-        if (shown++ % 8 == 7)
+        const std::vector<unsigned long long> hv = prof.fetch(st);
+        const unsigned long long *h = hv.data();
+        static EveryNth show{8};
+        if (show())
             for (int w = 0; w < 4; ++w) {
                 const unsigned long long *o = h + w * 6, *q = h + (4 + w) * 6;
                 if (o[5] && q[5])
@@ -428,14 +418,14 @@ int launch_chain2_pipe_bf16(const ChainArgs &a, int maxch, hipStream_t st) {
     if (a.n_stages != 2 || a.stats || a.seg_target || a.row_perm) return 1;
     for (int b = 0; b < a.n_blocks; ++b)
         if (a.bidx[b] || a.bidx32[b]) return 1;                         // direct rows only
-    { const char *d = getenv("GSN_CHAIN_BF16X6"); if (d && atoi(d) == 0) return 1; }
+    if (!sw_on(SW_CHAIN_BF16X6, true)) return 1;
     if (a.m_rows > (int64_t)2000000000) return 1;                       // 32-bit row arithmetic
     const int k1 = a.st[1].k_total;
     bool vec4 = true;                                                   // float4 gathers: stage-0 widths and bases 16-byte aligned
     for (int b = a.st[0].first_block; b < a.st[0].first_block + a.st[0].n_blocks; ++b)
         if ((a.bwidth[b] & 3) || (reinterpret_cast<uintptr_t>(a.bdata[b]) & 15)) vec4 = false;
-    { const char *d = getenv("GSN_PIPE_VEC4"); if (d && atoi(d) == 0) vec4 = false; }
-    { const char *d = getenv("GSN_PIPE_PROF"); if (d && atoi(d) && vec4 && maxch != 5 && k1 > 64) return launch_pipe_bf_impl<10, 8, true, true>(a, st); }
+    if (!sw_on(SW_PIPE_VEC4, true)) vec4 = false;
+    if (sw_on(SW_PIPE_PROF, false) && vec4 && maxch != 5 && k1 > 64) return launch_pipe_bf_impl<10, 8, true, true>(a, st);
     if (vec4) {
         if (maxch == 5) return k1 <= 64 ? launch_pipe_bf_impl<5, 4, true>(a, st) : launch_pipe_bf_impl<5, 8, true>(a, st);
         return k1 <= 64 ? launch_pipe_bf_impl<10, 4, true>(a, st) : launch_pipe_bf_impl<10, 8, true>(a, st);

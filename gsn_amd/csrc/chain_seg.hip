@@ -307,35 +307,25 @@ template <int NKS, int TBM, bool PROF, bool VEC4>
 static int launch_seg_impl(const ChainArgs &a, hipStream_t st) {
     const void *fn = reinterpret_cast<const void *>(&mlp_chain1_seg_kernel<NKS, TBM, PROF, VEC4>);
     static DeviceOnce attr_set;
-    const int attr_dev = current_device();
-    if (!attr_set.done(attr_dev)) {
-        hipError_t e0 = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e0 != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(mlp_chain1_seg_kernel): %s", hipGetErrorString(e0));
-        attr_set.mark(attr_dev);
-    }
+    if (int rc = lds_limit(&attr_set, {fn}, "mlp_chain1_seg_kernel")) return rc;
     const int pin = (((NKS * 2 + 31) / 32) * 32) | 1;
     int py = a.st[0].n_out | 1;
     if (py == a.st[0].n_out) py += 2;
     const size_t lds = ((size_t)2 * TBM * pin + (size_t)2 * TBM * py + (size_t)4 * CMAX_BLOCKS * TBM) * 4;
     if (lds > 160 * 1024) return 1;
-    unsigned long long *prof = nullptr;
-    int prio = 3;
-    { const char *d = getenv("GSN_SEG_PRIO"); if (d) prio = atoi(d); }
-    if (PROF) { (void)hipMalloc(&prof, 2 * 8 * 6 * 8); (void)hipMemset(prof, 0, 2 * 8 * 6 * 8); }
+    const int prio = sw_int(SW_SEG_PRIO, 3);
+    ProfCounters prof(PROF ? 2 * 8 * 6 : 0, st);
     const int64_t n_tiles = (a.m_rows + TBM - 1) / TBM;
     int64_t gx = 256 * (lds <= 78 * 1024 ? 2 : 1);
     if (gx > n_tiles) gx = n_tiles;
     chain_trace("mlp_chain1_seg_kernel", a);
-    hipLaunchKernelGGL((mlp_chain1_seg_kernel<NKS, TBM, PROF, VEC4>), dim3((unsigned)gx), dim3(TBM * 16), lds, st, a, pin, py, prof, prio);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "mlp_chain1_seg_kernel: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL((mlp_chain1_seg_kernel<NKS, TBM, PROF, VEC4>), dim3((unsigned)gx), dim3(TBM * 16), lds, st, a, pin, py, prof.ptr(), prio);
+    if (int rc = launch_check("mlp_chain1_seg_kernel")) return rc;
     if (PROF) {
-        unsigned long long h[2 * 8 * 6];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpy(h, prof, sizeof(h), hipMemcpyDeviceToHost);
-        (void)hipFree(prof);
-        static int shown = 0;
-        if (shown++ % 8 == 7)
+        const std::vector<unsigned long long> hv = prof.fetch(st);
+        const unsigned long long *h = hv.data();
+        static EveryNth show{8};
+        if (show())
             for (int w = 0; w < TBM / 8; ++w) {
                 const unsigned long long *o = h + w * 6, *q = h + (8 + w) * 6;
                 if (o[5]) fprintf(stderr, "segprof A%d tiles %llu: top %llu mfma %llu ywrite %llu stage %llu barrier %llu | B%d: lds %llu walk %llu barrier %llu (cycles per tile)\n", w, o[5],
@@ -348,7 +338,7 @@ static int launch_seg_impl(const ChainArgs &a, hipStream_t st) {
 template <int TBM, bool VEC4>
 static int launch_seg_k(const ChainArgs &a, hipStream_t st) {
     const int nks = (a.st[0].k_total + 1) / 2;
-    { const char *d = getenv("GSN_SEG_PROF"); if (d && atoi(d) && nks == 36) return launch_seg_impl<36, TBM, true, VEC4>(a, st); }
+    if (sw_on(SW_SEG_PROF, false) && nks == 36) return launch_seg_impl<36, TBM, true, VEC4>(a, st);
     if (nks <= 24) return launch_seg_impl<24, TBM, false, VEC4>(a, st);
     if (nks <= 32) return launch_seg_impl<32, TBM, false, VEC4>(a, st);
     if (nks <= 36) return launch_seg_impl<36, TBM, false, VEC4>(a, st);
@@ -361,12 +351,11 @@ int launch_chain1_seg(const ChainArgs &a, int maxch, hipStream_t st) {
     if (a.m_rows > (int64_t)2000000000) return 1;                       // 32-bit row arithmetic
     for (int b = 0; b < a.n_blocks; ++b)
         if (a.bidx[b] && !a.bidx32[b]) return 1;                        // int64 row indices: chain.hip's kernel
-    int tbm = 32;
-    { const char *d = getenv("GSN_CHAIN_SEGPIPE"); if (d) tbm = atoi(d); }
+    const int tbm = sw_int(SW_CHAIN_SEGPIPE, 32);
     bool vec4 = true;                                                   // float4 gathers: widths and bases 16-byte aligned
     for (int b = 0; b < a.n_blocks; ++b)
         if ((a.bwidth[b] & 3) || (reinterpret_cast<uintptr_t>(a.bdata[b]) & 15)) vec4 = false;
-    { const char *d = getenv("GSN_SEG_VEC4"); if (d && atoi(d) == 0) vec4 = false; }
+    if (!sw_on(SW_SEG_VEC4, true)) vec4 = false;
     if (tbm == 64) return vec4 ? launch_seg_k<64, true>(a, st) : launch_seg_k<64, false>(a, st);
     if (tbm == 32) return vec4 ? launch_seg_k<32, true>(a, st) : launch_seg_k<32, false>(a, st);
     return 1;

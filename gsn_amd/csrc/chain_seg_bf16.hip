@@ -410,34 +410,24 @@ template <int NK16, int TBM, bool PROF>
 static int launch_bf_impl(const ChainArgs &a, hipStream_t st) {
     const void *fn = reinterpret_cast<const void *>(&mlp_chain1_seg_bf16_kernel<NK16, TBM, PROF>);
     static DeviceOnce attr_set;
-    const int attr_dev = current_device();
-    if (!attr_set.done(attr_dev)) {
-        hipError_t e0 = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e0 != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(mlp_chain1_seg_bf16_kernel): %s", hipGetErrorString(e0));
-        attr_set.mark(attr_dev);
-    }
+    if (int rc = lds_limit(&attr_set, {fn}, "mlp_chain1_seg_bf16_kernel")) return rc;
     int py = a.st[0].n_out | 1;
     if (py == a.st[0].n_out) py += 2;
     const size_t lds = ((size_t)2 * 3 * (TBM * (NK16 * 16 + 8) / 2) + (size_t)2 * TBM * py + (size_t)4 * CMAX_BLOCKS * TBM + 2) * 4;
     if (lds > 160 * 1024) return 1;
-    unsigned long long *prof = nullptr;
-    int prio = 0;
-    { const char *d = getenv("GSN_SEG_PRIO"); if (d) prio = atoi(d); }
-    if (PROF) { (void)hipMalloc(&prof, 2 * 8 * 6 * 8); (void)hipMemset(prof, 0, 2 * 8 * 6 * 8); }
+    const int prio = sw_int(SW_SEG_PRIO, 0);
+    ProfCounters prof(PROF ? 2 * 8 * 6 : 0, st);
     const int64_t n_tiles = (a.m_rows + TBM - 1) / TBM;
     int64_t gx = 256 * (lds <= 78 * 1024 ? 2 : 1);
     if (gx > n_tiles) gx = n_tiles;
     chain_trace("mlp_chain1_seg_bf16_kernel", a);
-    hipLaunchKernelGGL((mlp_chain1_seg_bf16_kernel<NK16, TBM, PROF>), dim3((unsigned)gx), dim3(TBM * 12), lds, st, a, py, prof, prio);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "mlp_chain1_seg_bf16_kernel: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL((mlp_chain1_seg_bf16_kernel<NK16, TBM, PROF>), dim3((unsigned)gx), dim3(TBM * 12), lds, st, a, py, prof.ptr(), prio);
+    if (int rc = launch_check("mlp_chain1_seg_bf16_kernel")) return rc;
     if (PROF) {
-        unsigned long long h[2 * 8 * 6];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpy(h, prof, sizeof(h), hipMemcpyDeviceToHost);
-        (void)hipFree(prof);
-        static int shown = 0;
-        if (shown++ % 8 == 7)
+        const std::vector<unsigned long long> hv = prof.fetch(st);
+        const unsigned long long *h = hv.data();
+        static EveryNth show{8};
+        if (show())
             for (int w = 0; w < TBM / 8; ++w) {
                 const unsigned long long *o = h + w * 6, *q = h + (8 + w) * 6;
                 if (o[5]) fprintf(stderr, "segprof(bf16x6) A%d tiles %llu: top %llu mfma %llu ywrite %llu stage %llu barrier %llu | B%d: lds %llu walk %llu barrier %llu (cycles per tile)\n", w, o[5],
@@ -450,7 +440,7 @@ static int launch_bf_impl(const ChainArgs &a, hipStream_t st) {
 template <int TBM>
 static int launch_bf_k(const ChainArgs &a, hipStream_t st) {
     const int k = a.st[0].k_total;
-    { const char *d = getenv("GSN_SEG_PROF"); if (d && atoi(d) && k > 64) return launch_bf_impl<5, TBM, true>(a, st); }
+    if (sw_on(SW_SEG_PROF, false) && k > 64) return launch_bf_impl<5, TBM, true>(a, st);
     if (k <= 48) return launch_bf_impl<3, TBM, false>(a, st);
     if (k <= 64) return launch_bf_impl<4, TBM, false>(a, st);
     return launch_bf_impl<5, TBM, false>(a, st);
@@ -464,8 +454,7 @@ int launch_chain1_seg_bf16(const ChainArgs &a, int maxch, hipStream_t st) {
         if (a.bidx[b] && !a.bidx32[b]) return 1;                        // int64 row indices: chain.hip's kernel
         if ((a.bwidth[b] & 3) || (reinterpret_cast<uintptr_t>(a.bdata[b]) & 15)) return 1;   // float4 gathers only
     }
-    int tbm = 64;   // measured at 65 536 ZINC graphs: 0.40 ms (TBM 64, one workgroup per CU) vs 0.56 ms (TBM 32, two)
-    { const char *d = getenv("GSN_CHAIN_BF16X6"); if (d) tbm = atoi(d); }
+    const int tbm = sw_int(SW_CHAIN_BF16X6, 64);   // measured at 65 536 ZINC graphs: 0.40 ms (TBM 64, one workgroup per CU) vs 0.56 ms (TBM 32, two)
     if (tbm == 64) return launch_bf_k<64>(a, st);
     if (tbm == 32) return launch_bf_k<32>(a, st);
     return 1;

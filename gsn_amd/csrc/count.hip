@@ -1110,17 +1110,15 @@ static inline int align_up(int x, int a) { return (x + a - 1) / a * a; }
 
 template <int W, int T, bool DIR, bool TAIL, bool MOL = false, int CYC = 0>
 static int launch_d(CountArgs &a, int n_items, size_t lds, hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&count_kernel<W, T, DIR, TAIL, MOL, CYC>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
+    // (the size varies per call: no once-per-device flag; no label: the error names the byte count)
+    if (int rc = lds_limit(nullptr, {kernel_ptr(&count_kernel<W, T, DIR, TAIL, MOL, CYC>)}, nullptr, (int)lds)) return rc;
     hipLaunchKernelGGL((count_kernel<W, T, DIR, TAIL, MOL, CYC>), dim3((unsigned)n_items), dim3(T), lds, stream, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "count_kernel launch: %s", hipGetErrorString(e));
+    if (int rc = launch_check("count_kernel launch")) return rc;
 #ifdef COUNT_PROF
     {
         (void)hipStreamSynchronize(stream);
-        static int shown = 0;
-        if (shown++ % 16 == 15) {
+        static EveryNth show{16};
+        if (show()) {
             unsigned long long *buf = nullptr;
             (void)hipMalloc(&buf, (size_t)n_items * 128);
             (void)hipMemset(buf, 0, (size_t)n_items * 128);
@@ -1176,22 +1174,18 @@ static int launch(CountArgs &a, int n_items, size_t lds, hipStream_t stream) {
 #ifdef COUNT_PROF
             static const bool mol_on = false;           // (the phase profile is read from the generic instantiation, or from the cycle one)
 #else
-            static const bool mol_on = [] { const char *d = getenv("GSN_COUNT_MOL"); return !d || atoi(d) != 0; }();
+            const bool mol_on = sw_on(SW_COUNT_MOL, true);
 #endif
             const bool mol = mol_on && !tail && a.mode == GSN_MODE_EDGE && a.sym && a.n_cols == 4 && a.pair && a.split == 1 && a.enc_out &&
                              a.enc_stage && !a.graph_ids;
-            if (getenv("GSN_CHAIN_TRACE"))
-                fprintf(stderr, "gsn count: molecule instantiation %d cycle walk %d (tail %d mode %d sym %d cols %d pair %d split %d stage %d out %d enc %d enc_stage %d ids %d)\n", (int)mol,
+            trace("gsn count: molecule instantiation %d cycle walk %d (tail %d mode %d sym %d cols %d pair %d split %d stage %d out %d enc %d enc_stage %d ids %d)\n", (int)mol,
                         (int)(a.cyc_len != 0), (int)tail, a.mode, a.sym, a.n_cols, a.pair, a.split, a.stage_out, a.out != nullptr, a.enc_out != nullptr, a.enc_stage, a.graph_ids != nullptr);
             // every column a cycle of length <= 6 (count_launch: the launch's LDS was laid out for it, under these very conditions): the walk
             if (a.cyc_len) return launch_d<1, 64, false, false, true, 6>(a, n_items, lds, stream);
             if (mol) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&count_kernel_mol), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
+                if (int rc = lds_limit(nullptr, {kernel_ptr(&count_kernel_mol)}, nullptr, (int)lds)) return rc;
                 hipLaunchKernelGGL(count_kernel_mol, dim3((unsigned)n_items), dim3(64), lds, stream, a);
-                e = hipGetLastError();
-                if (e != hipSuccess) return set_error(GSN_E_HIP, "count_kernel_mol launch: %s", hipGetErrorString(e));
-                return GSN_OK;
+                return launch_check("count_kernel_mol launch");
             }
         }
         return tail ? launch_d<W, T, false, true>(a, n_items, lds, stream) : launch_d<W, T, false, false>(a, n_items, lds, stream);
@@ -1227,7 +1221,7 @@ static int count_launch(const uint32_t *plan_host, const uint32_t *plan_dev, int
     const bool directed = (plan_host[6] & 2u) != 0;
     a.stride = plan_stride(plan_host[6]);
     {
-        static const int pull_batch = [] { const char *d = getenv("GSN_PULL_BATCH"); const int v = d ? atoi(d) : 8; return v < 1 ? 1 : (v > 64 ? 64 : v); }();
+        const int pull_env = sw_int(SW_PULL_BATCH, 8), pull_batch = pull_env < 1 ? 1 : (pull_env > 64 ? 64 : pull_env);
         a.pull_batch = pull_batch;
     }
     if (directed && a.mode != GSN_MODE_VERTEX) return set_error(GSN_E_UNSUPPORTED, "gsn_count_hip: directed plans are vertex-mode plans");
@@ -1306,7 +1300,7 @@ static int count_launch(const uint32_t *plan_host, const uint32_t *plan_dev, int
     // only (every enumerated level of every plan has an adjacency constraint); GSN_COUNT_PAIR=0 switches it off.
     const int64_t tasks_cap1 = rows_cap * a.n_cols;
     bool pair = !graph_ids && n_graphs >= 2 && W == 1 && T == 64 && !(n_items < 2048 && tasks_cap1 >= 1024);
-    if (pair) { const char *d = getenv("GSN_COUNT_PAIR"); if (d && atoi(d) == 0) pair = false; }
+    if (pair && !sw_on(SW_COUNT_PAIR, true)) pair = false;
     for (int p = 0; pair && p < a.n_plans; ++p) {
         const uint32_t *w = plan_host + a.plans_off + (int64_t)p * a.stride;
         const int k = (int)(w[0] & 0xffu), nfix = (int)((w[0] >> 8) & 0xffu);
@@ -1335,7 +1329,7 @@ static int count_launch(const uint32_t *plan_host, const uint32_t *plan_dev, int
     // 0.082 ms with it).  GSN_COUNT_TAIL_LOOP=0 / 1 forces it off / on.
     a.tail_loop = 0;
     if (W == 1) {
-        static const int forced = [] { const char *e = getenv("GSN_COUNT_TAIL_LOOP"); return e ? atoi(e) : -1; }();
+        const int forced = sw_int(SW_COUNT_TAIL_LOOP, -1);
         a.tail_loop = forced >= 0 ? (forced != 0) : ((int64_t)a.e_decl >= 8 * (int64_t)a.n_decl);     // (the caller's capacities, before pairing)
     }
     // Cycle columns (count_core.h: cycle_plan_lengths / cycle_walk): a launch that meets the molecule instantiation's conditions (launch<>())
@@ -1343,11 +1337,11 @@ static int count_launch(const uint32_t *plan_host, const uint32_t *plan_dev, int
     // tables in its LDS.  Longer cycles (7, 8) keep the interpreter.  GSN_COUNT_CYCLE=0 sends such a launch down the interpreter.
     a.cyc_len = 0;
     if (W == 1 && T == 64 && pair && edge_mode && a.sym && !directed && a.n_cols == 4 && enc_out && enc_bytes && !a.any_tail && !a.tail_loop) {
-        static const bool cyc_on = [] { const char *d = getenv("GSN_COUNT_CYCLE"); return !d || atoi(d) != 0; }();
+        const bool cyc_on = sw_on(SW_COUNT_CYCLE, true);
 #ifdef COUNT_PROF
         static const bool mol_on = true;
 #else
-        static const bool mol_on = [] { const char *d = getenv("GSN_COUNT_MOL"); return !d || atoi(d) != 0; }();
+        const bool mol_on = sw_on(SW_COUNT_MOL, true);
 #endif
         uint8_t len[4];
         const int lmax = (cyc_on && mol_on) ? cycle_plan_lengths(plan_host, plan_words, len, 4) : 0;
@@ -1398,7 +1392,7 @@ static int count_launch(const uint32_t *plan_host, const uint32_t *plan_dev, int
     // few heavy graphs: several workgroups per graph so that every CU gets >= 8 of them
     a.split = 1;
     const int64_t tasks_cap = rows_cap * a.n_cols;
-    static const int64_t split_target = [] { const char *e = getenv("GSN_COUNT_SPLIT_TARGET"); const int64_t v = e ? atoll(e) : 0; return v > 0 ? v : (int64_t)2048; }();
+    const int64_t split_target_env = sw_int64(SW_COUNT_SPLIT_TARGET, 0), split_target = split_target_env > 0 ? split_target_env : 2048;
     if (!pair && n_items < split_target && tasks_cap >= 1024) {
         int64_t sp = (split_target + n_items - 1) / n_items;
         if (sp > 32) sp = 32;
@@ -1413,7 +1407,7 @@ static int count_launch(const uint32_t *plan_host, const uint32_t *plan_dev, int
     a.enc_no32 = (enc16 && enc_no32) ? 1 : 0;
     if (enc_out && a.split == 1 && enc_bytes && rows_cap_u * enc_width < (int64_t)1 << 24 && o + rows_cap_u * a.n_cols <= 150 * 1024) {
         a.enc_stage = 1;
-        static const bool bytes_forced = getenv("GSN_COUNT_ENC_BYTES") != nullptr;      // (A/B: keep the byte array beside staged counts)
+        const bool bytes_forced = sw_present(SW_COUNT_ENC_BYTES);     // (A/B: keep the byte array beside staged counts)
         if (a.stage_out && !bytes_forced) a.enc_from_counts = 1;      // the staged 16-bit counts hold what the class indices need: no second array
         else o += align_up((int)(rows_cap_u * a.n_cols), 16);         // (16-byte aligned: with four columns a row's indices are read as one word)
     }
@@ -1446,7 +1440,7 @@ static int count_launch(const uint32_t *plan_host, const uint32_t *plan_dev, int
     int items = pair ? (int)((n_graphs + 1) / 2) : (int)n_items * a.split;
     a.n_items = items; a.lds_bytes = o;
     if (a.side_mask) items = (items + SIDE_EVERY - 1) / SIDE_EVERY * (SIDE_EVERY + 1);      // every (SIDE_EVERY + 1)-th workgroup is a side workgroup
-    if (getenv("GSN_CHAIN_TRACE")) fprintf(stderr, "gsn count: count_kernel<%d,%d> workgroups %d pair %d split %d lds %d\n", W, T, items, a.pair, a.split, o);
+    trace("gsn count: count_kernel<%d,%d> workgroups %d pair %d split %d lds %d\n", W, T, items, a.pair, a.split, o);
     if (W == 1 && T == 64) return launch<1, 64>(a, items, (size_t)o, st);
     if (W == 1) return launch<1, 256>(a, items, (size_t)o, st);
     if (W == 2 && T == 64) return launch<2, 64>(a, items, (size_t)o, st);

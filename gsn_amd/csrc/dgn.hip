@@ -510,8 +510,7 @@ extern "C" int gsn_dgn_aggregate_fwd_hip(int64_t n_nodes, int64_t n_edges, int64
     for (int j0 = 0; j0 < n_aggs; j0 += DGN_MAXA) {
         dgn_slice(a, aggs, j0, n_aggs - j0 < DGN_MAXA ? n_aggs - j0 : DGN_MAXA);
         dgn_launch<FwdK>(a, vec, s);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return set_error(GSN_E_HIP, "dgn_aggregate_fwd_kernel: %s", hipGetErrorString(e));
+        if (int rc = launch_check("dgn_aggregate_fwd_kernel")) return rc;
     }
     return GSN_OK;
 }
@@ -538,11 +537,8 @@ extern "C" int gsn_dgn_aggregate_bwd_hip(int64_t n_nodes, int64_t n_edges, int64
         dgn_slice(a, aggs, j0, n_aggs - j0 < DGN_MAXA ? n_aggs - j0 : DGN_MAXA);
         a.first = j0 == 0;
         dgn_launch<BwdTK>(a, vec, s);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return set_error(GSN_E_HIP, "dgn_aggregate_bwd_target_kernel: %s", hipGetErrorString(e));
+        if (int rc = launch_check("dgn_aggregate_bwd_target_kernel")) return rc;
     }
     dgn_launch<BwdSK>(a, vec, s);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "dgn_aggregate_bwd_source_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("dgn_aggregate_bwd_source_kernel");
 }

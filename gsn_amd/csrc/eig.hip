@@ -437,20 +437,12 @@ __global__ void __launch_bounds__(THREADS) laplacian_eig_kernel(EigArgs a) {
 template <int NMAX, int THREADS, bool IN_LDS>
 int eig_launch(const EigArgs &a, hipStream_t stream) {
     const size_t lds = IN_LDS ? sizeof(float) * 2 * NMAX * (NMAX + 1) : 0;
-    if (lds > 48 * 1024) {
+    if (lds > 48 * 1024) {      // (a constant of the instantiation: once per device)
         static DeviceOnce once;
-        const int dev = current_device();
-        if (!once.done(dev)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&laplacian_eig_kernel<NMAX, THREADS, IN_LDS>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
-            once.mark(dev);
-        }
+        if (int rc = lds_limit(&once, {kernel_ptr(&laplacian_eig_kernel<NMAX, THREADS, IN_LDS>)}, nullptr, (int)lds)) return rc;
     }
     hipLaunchKernelGGL((laplacian_eig_kernel<NMAX, THREADS, IN_LDS>), dim3((unsigned)a.n_ids), dim3(THREADS), lds, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "laplacian_eig_kernel<%d> launch: %s", NMAX, hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("laplacian_eig_kernel<%d> launch", NMAX);
 }
 
 }  // namespace

@@ -148,16 +148,12 @@ extern "C" int gsn_one_hot_hip(int64_t m_rows, int n_cols, const int64_t *values
         else if (n_cols == 2) hipLaunchKernelGGL(one_hot_rows_kernel<2>, grid, block, 0, st, a);
         else if (n_cols == 3) hipLaunchKernelGGL(one_hot_rows_kernel<3>, grid, block, 0, st, a);
         else hipLaunchKernelGGL(one_hot_rows_kernel<4>, grid, block, 0, st, a);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return set_error(GSN_E_HIP, "one_hot_rows_kernel: %s", hipGetErrorString(e));
-        return GSN_OK;
+        return launch_check("one_hot_rows_kernel");
     }
     int64_t blocks = (m_rows * a.width + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     hipLaunchKernelGGL(one_hot_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "one_hot_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("one_hot_kernel");
 }
 
 extern "C" int gsn_one_hot_pack16_hip(int64_t m_rows, int n_cols, const int64_t *values, const int32_t *n_classes, int clamp,
@@ -186,9 +182,7 @@ extern "C" int gsn_one_hot_pack16_hip(int64_t m_rows, int n_cols, const int64_t 
         a.q_first = lo >> 3; a.q_count = (hi >> 3) - a.q_first + 1;
     }
     hipLaunchKernelGGL(one_hot_pack16_kernel, dim3((unsigned)((m_rows * a.q_count + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "one_hot_pack16_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("one_hot_pack16_kernel");
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -637,13 +631,7 @@ static int launch_embed_lds_n(EmbArgs &a, int nwv, hipStream_t s) {
     constexpr int DCH = EMB_DCH * NSUB;
     const size_t lds = (size_t)(BWD ? nwv : 1) * a.row_off[a.n_cols] * DCH * sizeof(float);
     static DeviceOnce attr_set;
-    const int attr_dev = current_device();
-    if (!attr_set.done(attr_dev)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&embed_lds_kernel<BWD, NSUB>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                EMB_LDS_SUM_ROWS * EMB_DCH * (int)sizeof(float)) != hipSuccess)
-            return set_error(GSN_E_HIP, "embed_lds_kernel: cannot raise the LDS limit");
-        attr_set.mark(attr_dev);
-    }
+    if (int rc = lds_limit(&attr_set, {kernel_ptr(&embed_lds_kernel<BWD, NSUB>)}, "embed_lds_kernel", EMB_LDS_SUM_ROWS * EMB_DCH * (int)sizeof(float))) return rc;
     // rows per workgroup: 2048 at most (the table slices are copied to / flushed from LDS once per workgroup), fewer until there are ~8
     // workgroups per CU -- at 2048 a molhiv-sized batch (214 k edge rows, d = 300) gave every CU two workgroups and 0.9 TB/s
     const int64_t n_slices = (a.d + DCH - 1) / DCH;
@@ -652,14 +640,12 @@ static int launch_embed_lds_n(EmbArgs &a, int nwv, hipStream_t s) {
     rpw = rpw < 128 ? 128 : (rpw > EMB_ROWS ? EMB_ROWS : rpw);
     a.rows_per_wg = (int)rpw;
     const dim3 grid((unsigned)((a.m_rows + rpw - 1) / rpw), (unsigned)n_slices);
-    static const bool no_vec4 = getenv("GSN_EMBED_NOVEC4") != nullptr;        // (A/B)
+    const bool no_vec4 = sw_present(SW_EMBED_NOVEC4);        // (A/B)
     a.vec4 = (!BWD && NSUB > 1 && !a.concat && a.d % 4 == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0 && !no_vec4) ? 1 : 0;
-    static const bool no_pipe = [] { const char *e = getenv("GSN_EMBED_PIPE"); return e && atoi(e) == 0; }();
+    const bool no_pipe = !sw_on(SW_EMBED_PIPE, true);
     a.pipe = (a.vec4 && a.n_cols <= 16 && !no_pipe) ? 1 : 0;
     hipLaunchKernelGGL((embed_lds_kernel<BWD, NSUB>), grid, dim3(64 * nwv), lds, s, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "embed_lds_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("embed_lds_kernel");
 }
 
 template <bool BWD>
@@ -701,12 +687,6 @@ static int grid_for(int64_t items) {
 
 }  // namespace gsn
 
-#define GSN_LAUNCH_CHECK(name)                                                                  \
-    do {                                                                                        \
-        hipError_t e_ = hipGetLastError();                                                      \
-        if (e_ != hipSuccess) return set_error(GSN_E_HIP, name ": %s", hipGetErrorString(e_)); \
-    } while (0)
-
 extern "C" int gsn_column_range_hip(int64_t m_rows, int n_cols, const int64_t *values, int64_t *col_min, int64_t *col_max,
                                     void *stream) {
     if (n_cols < 1 || n_cols > 65535 || !col_min || !col_max || (m_rows > 0 && !values))
@@ -718,8 +698,7 @@ extern "C" int gsn_column_range_hip(int64_t m_rows, int n_cols, const int64_t *v
         if (bx > 1024) bx = 1024;
         hipLaunchKernelGGL(column_range_kernel, dim3(bx, n_cols), dim3(256), 0, s, m_rows, n_cols, values, col_min, col_max);
     }
-    GSN_LAUNCH_CHECK("column_range_kernel");
-    return GSN_OK;
+    return launch_check("column_range_kernel");
 }
 
 extern "C" int gsn_column_ranks_hip(int64_t m_rows, int n_cols, const int64_t *values, const int64_t *col_min,
@@ -738,8 +717,7 @@ extern "C" int gsn_column_ranks_hip(int64_t m_rows, int n_cols, const int64_t *v
     if (m_rows > 0)
         hipLaunchKernelGGL(rank_gather_kernel, dim3(grid_for(m_rows * n_cols)), dim3(256), 0, s, m_rows, n_cols, values,
                            col_min, col_base, table, codes);
-    GSN_LAUNCH_CHECK("rank kernels");
-    return GSN_OK;
+    return launch_check("rank kernels");
 }
 
 extern "C" int gsn_embed_fwd_hip(int64_t m_rows, int n_cols, int d, int concat, const int64_t *codes, const int64_t *meta,
@@ -749,7 +727,7 @@ extern "C" int gsn_embed_fwd_hip(int64_t m_rows, int n_cols, int d, int concat, 
     if (m_rows <= 0) return GSN_OK;
     // (few rows -- the reference's batch sizes: 800 .. 6 000 rows -- gather straight from the L2-resident tables: the LDS kernel first copies
     //  every table slice into every workgroup, ~40 us per call whatever the row count)
-    static const int64_t lds_min_rows = [] { const char *e = getenv("GSN_EMBED_LDS_MIN_ROWS"); return e ? atoll(e) : (int64_t)8192; }();
+    const int64_t lds_min_rows = sw_int64(SW_EMBED_LDS_MIN_ROWS, 8192);
     if (m_rows > lds_min_rows && embed_lds_fits(n_cols, table_rows)) {
         EmbArgs a{};
         a.m_rows = m_rows; a.n_cols = n_cols; a.d = d; a.concat = concat; a.codes = codes; a.meta = meta; a.out = out; a.status = status;
@@ -758,8 +736,7 @@ extern "C" int gsn_embed_fwd_hip(int64_t m_rows, int n_cols, int d, int concat, 
     const int64_t total = m_rows * (concat ? (int64_t)n_cols * d : d);
     hipLaunchKernelGGL(embed_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), m_rows,
                        n_cols, d, concat, codes, meta, out, status);
-    GSN_LAUNCH_CHECK("embed_fwd_kernel");
-    return GSN_OK;
+    return launch_check("embed_fwd_kernel");
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -934,7 +911,7 @@ __global__ __launch_bounds__(256) void embed_bwd_mfma_kernel(EmbMArgs a) {
 
 namespace gsn {
 static bool embed_bwd_mfma_fits(int64_t m_rows, int n_cols, int concat, const int64_t *table_rows, int64_t *rtot_out) {
-    static const bool lds_only = [] { const char *e = getenv("GSN_EMBED_BWD_LDS"); return e && e[0] == '1'; }();
+    const bool lds_only = sw_on(SW_EMBED_BWD_LDS, false);
     int64_t rtot = 0;
     bool small_tables = n_cols <= EMB_MAXC;
     for (int c = 0; small_tables && c < n_cols; ++c) { rtot += table_rows[c]; small_tables = table_rows[c] > 0 && table_rows[c] < 0xfffe; }
@@ -997,8 +974,7 @@ static int embed_bwd_impl(int64_t m_rows, int n_cols, int d, int concat, const i
             slabs = (m_rows + rows_per - 1) / rows_per;
             const int64_t groups = (slabs + 7) / 8;
             hipLaunchKernelGGL(embed_bwd_mfma_kernel, dim3((unsigned)(groups * nt * 8)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-            GSN_LAUNCH_CHECK("embed_bwd_mfma_kernel");
-            return GSN_OK;
+            return launch_check("embed_bwd_mfma_kernel");
         }
     }
     if (embed_lds_fits(n_cols, table_rows)) {
@@ -1013,8 +989,7 @@ static int embed_bwd_impl(int64_t m_rows, int n_cols, int d, int concat, const i
     for (int c = 0; c < n_cols; ++c)
         hipLaunchKernelGGL(embed_bwd_kernel, dim3(grid_for(m_rows * d)), dim3(256), 0, s, m_rows, n_cols, d, concat, codes, grad_meta,
                            grad_out, c);
-    GSN_LAUNCH_CHECK("embed_bwd kernels");
-    return GSN_OK;
+    return launch_check("embed_bwd kernels");
 }
 
 namespace gsn {
@@ -1058,13 +1033,11 @@ extern "C" int gsn_bn_act_hip(int64_t m_rows, int64_t n_cols, const float *h, co
         bx = bx > 2048 ? 2048 : bx;
         hipLaunchKernelGGL(bn_act_cols_kernel, dim3((unsigned)bx, (unsigned)((n_cols + 63) / 64)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                            m_rows, (int)n_cols, h, mean, scale, shift, act, out);
-        GSN_LAUNCH_CHECK("bn_act_cols_kernel");
-        return GSN_OK;
+        return launch_check("bn_act_cols_kernel");
     }
     hipLaunchKernelGGL(bn_act_kernel, dim3(grid_for(m_rows * n_cols)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        m_rows * n_cols, (int)n_cols, h, mean, scale, shift, act, out);
-    GSN_LAUNCH_CHECK("bn_act_kernel");
-    return GSN_OK;
+    return launch_check("bn_act_kernel");
 }
 
 // per-column sum and sum of squares of materialised rows, added to stats[2][n_cols] (fp64): a workgroup takes a band of rows, a thread
@@ -1093,8 +1066,7 @@ extern "C" int gsn_column_stats_hip(int64_t m_rows, int64_t n_cols, const float 
     const int64_t blocks = (m_rows + gsn::CS_ROWS - 1) / gsn::CS_ROWS;
     if (blocks > 0x7fffffff) return set_error(GSN_E_UNSUPPORTED, "gsn_column_stats_hip: too many rows");
     hipLaunchKernelGGL(gsn::column_stats_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), m_rows, (int)n_cols, h, stats);
-    GSN_LAUNCH_CHECK("column_stats_kernel");
-    return GSN_OK;
+    return launch_check("column_stats_kernel");
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1165,9 +1137,7 @@ extern "C" int gsn_add_gathered_hip(int64_t n_rows, int64_t d, const float *x, c
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (v4) hipLaunchKernelGGL((gsn::add_gathered_kernel<4>), dim3((unsigned)blocks), dim3(256), 0, s, n_rows, (int)d, x, table, idx, n_table, out);
     else hipLaunchKernelGGL((gsn::add_gathered_kernel<1>), dim3((unsigned)blocks), dim3(256), 0, s, n_rows, (int)d, x, table, idx, n_table, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "add_gathered_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("add_gathered_kernel");
 }
 
 extern "C" int gsn_gather_cat_hip(int64_t m_rows, int n_blocks, const gsn_block *blocks, float *out, void *stream) {
@@ -1183,8 +1153,7 @@ extern "C" int gsn_gather_cat_hip(int64_t m_rows, int n_blocks, const gsn_block 
     a.k_total = a.off[n_blocks];
     if (m_rows <= 0) return GSN_OK;
     hipLaunchKernelGGL(gather_cat_kernel, dim3(grid_for(m_rows * a.k_total)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-    GSN_LAUNCH_CHECK("gather_cat_kernel");
-    return GSN_OK;
+    return launch_check("gather_cat_kernel");
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1268,8 +1237,7 @@ extern "C" int gsn_bn_finalize_act_hip(int64_t n_cols, int64_t m_rows, double ep
     hipLaunchKernelGGL(bn_finalize_act_kernel, dim3((unsigned)bx, (unsigned)((n_cols + 63) / 64)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        (int)n_cols, m_rows, eps, momentum, stats, gamma, beta, running_mean, running_var, mean, invstd, scale, shift,
                        num_batches_tracked, h, act, out);
-    GSN_LAUNCH_CHECK("bn_finalize_act_kernel");
-    return GSN_OK;
+    return launch_check("bn_finalize_act_kernel");
 }
 
 extern "C" int gsn_bn_finalize_hip(int64_t n_cols, int64_t m_rows, double eps, double momentum, const double *stats,
@@ -1287,6 +1255,5 @@ extern "C" int gsn_bn_finalize_count_hip(int64_t n_cols, int64_t m_rows, double 
     hipLaunchKernelGGL(bn_finalize_kernel, dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        (int)n_cols, (double)m_rows, eps, momentum, stats, gamma, beta, running_mean, running_var, mean, invstd, scale, shift,
                        num_batches_tracked);
-    GSN_LAUNCH_CHECK("bn_finalize_kernel");
-    return GSN_OK;
+    return launch_check("bn_finalize_kernel");
 }

@@ -38,10 +38,9 @@ extern "C" int gsn_fingerprint_hip(int n_tensors, const int64_t *meta, int64_t m
     int64_t bx = (max_words + 2047) / 2048;      // ~8 words per thread
     bx = bx < 1 ? 1 : (bx > 64 ? 64 : bx);
     hipLaunchKernelGGL(fingerprint_kernel, dim3((unsigned)bx, (unsigned)n_tensors), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), n_tensors, meta, acc);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "fingerprint_kernel: %s", hipGetErrorString(e));
+    if (int rc = launch_check("fingerprint_kernel")) return rc;
     if (host_out) {      // pinned host memory: the copy is asynchronous, ordered behind the kernel on the stream
-        e = hipMemcpyAsync(host_out, acc, sizeof(unsigned long long), hipMemcpyDeviceToHost, reinterpret_cast<hipStream_t>(stream));
+        const hipError_t e = hipMemcpyAsync(host_out, acc, sizeof(unsigned long long), hipMemcpyDeviceToHost, reinterpret_cast<hipStream_t>(stream));
         if (e != hipSuccess) return set_error(GSN_E_HIP, "gsn_fingerprint_hip: copy to the host: %s", hipGetErrorString(e));
     }
     return GSN_OK;

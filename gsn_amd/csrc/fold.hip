@@ -111,8 +111,7 @@ extern "C" int gsn_fold_weights_fwd_hip(int64_t rows, int64_t d_x, int64_t a_col
         return set_error(GSN_E_INVALID, "gsn_fold_weights_fwd_hip: bad arguments");
     hipLaunchKernelGGL(fold_fwd_kernel, dim3((unsigned)rows), dim3(256), (size_t)a_cols * sizeof(float), reinterpret_cast<hipStream_t>(stream), (int)d_x,
                        (int)a_cols, (int)h_cols, (int)pad_cols, w3, ld3, w2, ld2, b2, out);
-    if (hipGetLastError() != hipSuccess) return set_error(GSN_E_HIP, "gsn_fold_weights_fwd_hip: launch failed");
-    return GSN_OK;
+    return launch_check("gsn_fold_weights_fwd_hip");
 }
 
 extern "C" int gsn_fold_weights_bwd_hip(int64_t rows, int64_t d_x, int64_t a_cols, int64_t h_cols, const float *g, int64_t ldg, const float *w3, int64_t ld3,
@@ -123,6 +122,5 @@ extern "C" int gsn_fold_weights_bwd_hip(int64_t rows, int64_t d_x, int64_t a_col
     const size_t lds = (size_t)((h_cols + 1 > rows ? h_cols + 1 : rows)) * sizeof(float);
     hipLaunchKernelGGL(fold_bwd_kernel, dim3((unsigned)(rows + a_cols)), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), (int)rows, (int)d_x,
                        (int)a_cols, (int)h_cols, g, ldg, w3, ld3, w2, ld2, b2, g_w3, g_w2, g_b2);
-    if (hipGetLastError() != hipSuccess) return set_error(GSN_E_HIP, "gsn_fold_weights_bwd_hip: launch failed");
-    return GSN_OK;
+    return launch_check("gsn_fold_weights_bwd_hip");
 }

@@ -256,7 +256,5 @@ extern "C" int gsn_code_stage_fwd_hip(int64_t m_rows, int n_slots, const gsn_cod
     if (cpl == 1) launch_code_stage<1>(a, stats != nullptr, grid, lds, s);
     else if (cpl == 2) launch_code_stage<2>(a, stats != nullptr, grid, lds, s);
     else launch_code_stage<4>(a, stats != nullptr, grid, lds, s);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "code_stage_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("code_stage_kernel");
 }

@@ -5,8 +5,11 @@
 #include <cstdint>
 #include <cstdio>
 #include <atomic>
+#include <initializer_list>
+#include <vector>
 
 #include "../../include/gsn_abi.h"
+#include "switches.h"
 
 namespace gsn {
 
@@ -41,6 +44,37 @@ struct DeviceOnce {
     void mark(int dev) { if (dev >= 0 && dev < 64) mask.fetch_or(1ull << dev, std::memory_order_release); }
 };
 int current_device();   // hipGetDevice, -1 on error (abi.cpp)
+
+// ---- launch plumbing (abi.cpp); streams travel as void * so that this header needs no HIP include ----
+constexpr int LDS_LIMIT_BYTES = 160 * 1024;
+template <class... A> const void *kernel_ptr(void (*kernel)(A...)) { return reinterpret_cast<const void *>(kernel); }
+// raises the dynamic-LDS limit of `kernels` to `bytes` on the current device, once per device under the caller's static flag
+// (`once` null: at every call, for count.hip, whose size varies per call).  The error names the attribute call, (<label>) and the
+// HIP error string; a null label stands for "<bytes> B LDS".  After a failure nothing is marked done.
+int lds_limit(DeviceOnce *once, std::initializer_list<const void *> kernels, const char *label, int bytes = LDS_LIMIT_BYTES);
+// hipGetLastError after a launch: GSN_OK, or GSN_E_HIP with "<label>: <hip string>" (the label is a printf format)
+int launch_check(const char *label_fmt, ...) __attribute__((format(printf, 1, 2)));
+// a line on stderr when GSN_CHAIN_TRACE is present (read at every call)
+void trace(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+
+// device counters of a profiling build: n zeroed unsigned long long on `stream` (n == 0: none, ptr() is null; so it is when the
+// allocation fails, and fetch() then returns n zeros)
+struct ProfCounters {
+    ProfCounters(size_t n, void *stream);
+    ~ProfCounters();
+    ProfCounters(const ProfCounters &) = delete;
+    ProfCounters &operator=(const ProfCounters &) = delete;
+    unsigned long long *ptr() const { return dev_; }
+    std::vector<unsigned long long> fetch(void *stream);   // waits for the stream, copies the counters out, frees them
+private:
+    unsigned long long *dev_ = nullptr;
+    size_t n_ = 0;
+};
+// true at every n-th call: the profiling builds print one launch in n
+struct EveryNth {
+    int n, calls = 0;
+    bool operator()() { return calls++ % n == n - 1; }
+};
 int64_t gsn_wgrad_slab_rows(int64_t m_rows, int64_t tiles, int64_t wg_target);   // backward.hip: rows per slab of a weight-gradient call
 
 }  // namespace gsn

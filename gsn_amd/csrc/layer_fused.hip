@@ -945,32 +945,24 @@ static int lf_launch(const LfArgs &a, hipStream_t st) {
     static_assert(lds <= 160 * 1024, "LDS budget");
     const void *fn = reinterpret_cast<const void *>(&layer_fused_kernel<NKE, NK0, NK1, WG, PROF>);
     static DeviceOnce attr_set;                                        // (the attribute is per device)
-    const int attr_dev = current_device();
-    if (!attr_set.done(attr_dev)) {
-        hipError_t e0 = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e0 != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(layer_fused_kernel): %s", hipGetErrorString(e0));
-        attr_set.mark(attr_dev);
-    }
+    if (int rc = lds_limit(&attr_set, {fn}, "layer_fused_kernel")) return rc;
     int64_t gx = 256;
-    { const char *d = getenv("GSN_FUSED_GRID"); if (d && atoi(d) > 0) gx = atoi(d); }
+    if (const int g = sw_int(SW_FUSED_GRID, 0); g > 0) gx = g;
     const int64_t n_tiles = ((int64_t)a.n_nodes + LF_TN - 1) / LF_TN;
     if (gx > n_tiles) gx = n_tiles;
-    if (getenv("GSN_CHAIN_TRACE")) fprintf(stderr, "gsn chain: layer_fused_kernel<%d,%d,%d,%d> nodes %d edges %d grid %lld\n", NKE, NK0, NK1, WG, a.n_nodes, a.n_edges, (long long)gx);
-    unsigned long long *prof = nullptr;
-    if (PROF) { (void)hipMalloc(&prof, (24 * 6 + 512) * 8); (void)hipMemset(prof, 0, (24 * 6 + 512) * 8); }
-    static const int prio_env = [] { const char *d = getenv("GSN_FUSED_PRIO"); return d ? atoi(d) : 1; }();   // matrix phases at raised wave priority (~1 %)
+    trace("gsn chain: layer_fused_kernel<%d,%d,%d,%d> nodes %d edges %d grid %lld\n", NKE, NK0, NK1, WG, a.n_nodes, a.n_edges, (long long)gx);
+    ProfCounters prof(PROF ? 24 * 6 + 512 : 0, st);
+    const int prio_env = sw_int(SW_FUSED_PRIO, 1);   // matrix phases at raised wave priority (~1 %)
     int prio = prio_env & 0xff;
-    if (PROF) { const char *d = getenv("GSN_FUSED_ABLATE"); if (d) prio |= atoi(d) << 8; }
-    hipLaunchKernelGGL((layer_fused_kernel<NKE, NK0, NK1, WG, PROF>), dim3((unsigned)gx), dim3(768), lds, st, a, prof, prio);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "layer_fused_kernel: %s", hipGetErrorString(e));
+    if (PROF) prio |= sw_int(SW_FUSED_ABLATE, 0) << 8;
+    hipLaunchKernelGGL((layer_fused_kernel<NKE, NK0, NK1, WG, PROF>), dim3((unsigned)gx), dim3(768), lds, st, a, prof.ptr(), prio);
+    if (int rc = launch_check("layer_fused_kernel")) return rc;
     if (PROF) {
-        unsigned long long h[24 * 6 + 512];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpy(h, prof, sizeof(h), hipMemcpyDeviceToHost);
-        (void)hipFree(prof);
-        static int shown = 0;
-        if (shown % 8 == 7 && gx == 256) {           // when did the workgroups enter and leave (relative to the first entry)?
+        const std::vector<unsigned long long> hv = prof.fetch(st);
+        const unsigned long long *h = hv.data();
+        static EveryNth show_nth{8};
+        const bool show = show_nth();
+        if (show && gx == 256) {           // when did the workgroups enter and leave (relative to the first entry)?
             unsigned long long t0 = ~0ull;
             // (s_memtime counters are per XCD: only the workgroups of one XCD, blockIdx % 8 == 0, are comparable)
             for (int b = 0; b < 256; b += 8) if (h[144 + 2 * b] && h[144 + 2 * b] < t0) t0 = h[144 + 2 * b];
@@ -983,7 +975,7 @@ static int lf_launch(const LfArgs &a, hipStream_t st) {
             }
             fprintf(stderr, "\nfusedprof last entry %lld, first exit %lld, last exit %lld\n", emax, xmin, xmax);
         }
-        if (shown++ % 8 == 7)
+        if (show)
             for (int w = 0; w < 12; ++w) {
                 const unsigned long long *o = h + w * 6;
                 if (o[5]) fprintf(stderr, "fusedprof %s%d steps %llu: phase1 %llu barrier %llu phase2 %llu barrier %llu bookkeeping %llu (cycles per step)\n",
@@ -1084,8 +1076,7 @@ extern "C" int gsn_layer_fused_prepare_hip(const gsn_chain_stage *edge, int64_t 
     else if (nk0 == 6) hipLaunchKernelGGL((layer_fused_prepare_kernel<5, 6, 8>), dim3(1), dim3(768), 0, st, a, pp);
     else if (nk1 == 4) hipLaunchKernelGGL((layer_fused_prepare_kernel<5, 10, 4>), dim3(1), dim3(768), 0, st, a, pp);
     else hipLaunchKernelGGL((layer_fused_prepare_kernel<5, 10, 8>), dim3(1), dim3(768), 0, st, a, pp);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "layer_fused_prepare_kernel: %s", hipGetErrorString(e));
+    if (int rc = launch_check("layer_fused_prepare_kernel")) return rc;
     if (rr_supported(edge, d_x, node0, node1))
         return rr_prepare(edge, d_x, node0, node1, reinterpret_cast<unsigned char *>(prepared) + lf_prep_bytes_own(a), st);
     return GSN_OK;
@@ -1148,10 +1139,10 @@ static int lf_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, 
     }
     const int k0 = a.s0.k_total, k1 = a.s1.k_total;
     // every width 128 (or 64): the reference's d = 128 / 64 layers -- widths as compile-time constants
-    const bool generic = getenv("GSN_FUSED_GENERIC") != nullptr;
+    const bool generic = sw_present(SW_FUSED_GENERIC);
     const bool w128 = !generic && a.e.n_out == 128 && a.s0.n_out == 128 && a.s1.n_out == 128 && k0 <= 160 && k0 > 96 && k1 > 64;
     const bool w64 = !generic && a.e.n_out == 64 && a.s0.n_out == 64 && a.s1.n_out == 64 && k0 <= 96;
-    { const char *d = getenv("GSN_FUSED_PROF"); if (d && atoi(d) && w128) return lf_launch<5, 10, 8, 4, true>(a, st); }
+    if (sw_on(SW_FUSED_PROF, false) && w128) return lf_launch<5, 10, 8, 4, true>(a, st);
     if (w128) return lf_launch<5, 10, 8, 4>(a, st);
     if (w64) return lf_launch<5, 6, 4, 2>(a, st);
     if (k0 <= 96) return k1 <= 64 ? lf_launch<5, 6, 4>(a, st) : lf_launch<5, 6, 8>(a, st);

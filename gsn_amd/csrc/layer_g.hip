@@ -850,8 +850,7 @@ __global__ __launch_bounds__(256) void layer_fused_kernel_g(GArgs a, unsigned lo
 
 // ------------------------------------------------------------------------------------------------------------------------------
 static bool g_enabled() {
-    static const int on = [] { const char *d = getenv("GSN_FUSED_G"); return d ? atoi(d) : 1; }();
-    return on != 0;
+    return sw_int(SW_FUSED_G, 1) != 0;
 }
 
 int g_supported(const gsn_chain_stage *edge, int64_t d_x, const gsn_chain_stage *node0, const gsn_chain_stage *node1) {
@@ -897,30 +896,21 @@ int g_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const gs
         for (int q = 0; q < 4; ++q) { a.zq[q].base = reinterpret_cast<unsigned long long>(x); a.zq[q].stride = 0; a.zq[q].role = 0; }
     }
     int64_t gx = 256;
-    { const char *d = getenv("GSN_FUSED_GRID"); if (d && atoi(d) > 0) gx = atoi(d); }
+    if (const int g = sw_int(SW_FUSED_GRID, 0); g > 0) gx = g;
     if (gx > n_graphs) gx = n_graphs;
     a.n_wg = (int)gx;
-    static const bool prof_on = [] { const char *d = getenv("GSN_FUSED_PROF"); return d && atoi(d) != 0; }();
+    static const bool prof_on = sw_on(SW_FUSED_PROF, false);
     static DeviceOnce attr_set;
-    const int attr_dev = current_device();
-    if (!attr_set.done(attr_dev)) {
-        hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(&layer_fused_kernel_g<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e0 == hipSuccess) e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(&layer_fused_kernel_g<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e0 == hipSuccess) e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(&layer_fused_kernel_g<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e0 != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(layer_fused_kernel_g): %s", hipGetErrorString(e0));
-        attr_set.mark(attr_dev);
-    }
-    if (getenv("GSN_CHAIN_TRACE")) fprintf(stderr, "gsn chain: layer_fused_kernel_g nodes %d edges %d graphs %d grid %lld\n", a.n_nodes, a.n_edges, a.n_graphs, (long long)gx);
+    if (int rc = lds_limit(&attr_set, {kernel_ptr(&layer_fused_kernel_g<false, false>), kernel_ptr(&layer_fused_kernel_g<false, true>),
+                                       kernel_ptr(&layer_fused_kernel_g<true, true>)}, "layer_fused_kernel_g")) return rc;
+    trace("gsn chain: layer_fused_kernel_g nodes %d edges %d graphs %d grid %lld\n", a.n_nodes, a.n_edges, a.n_graphs, (long long)gx);
     if (prof_on && has_z) {
-        unsigned long long *prof = nullptr;
-        (void)hipMalloc(&prof, 64 * 8); (void)hipMemsetAsync(prof, 0, 64 * 8, st);
-        hipLaunchKernelGGL((layer_fused_kernel_g<true, true>), dim3((unsigned)gx), dim3(256), GL_TOTAL, st, a, prof);
-        unsigned long long h[64];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(h, prof, sizeof(h), hipMemcpyDeviceToHost);
-        (void)hipFree(prof);
-        static int shown = 0;
-        if (shown++ % 8 == 7)
+        ProfCounters prof(64, st);
+        hipLaunchKernelGGL((layer_fused_kernel_g<true, true>), dim3((unsigned)gx), dim3(256), GL_TOTAL, st, a, prof.ptr());
+        const std::vector<unsigned long long> hv = prof.fetch(st);
+        const unsigned long long *h = hv.data();
+        static EveryNth show{8};
+        if (show())
             for (int w = 0; w < 4; ++w) {
                 const unsigned long long *o = h + 16 * w;
                 const double nt = o[9] ? (double)o[9] : 1.0;
@@ -934,9 +924,7 @@ int g_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const gs
     } else {
         hipLaunchKernelGGL((layer_fused_kernel_g<false, false>), dim3((unsigned)gx), dim3(256), GL_TOTAL, st, a, (unsigned long long *)nullptr);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "layer_fused_kernel_g: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("layer_fused_kernel_g");
 }
 
 }  // namespace gsn

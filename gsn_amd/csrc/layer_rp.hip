@@ -795,37 +795,29 @@ int rp_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const g
     a.d_x = (int)d_x; a.out = out; a.prep = reinterpret_cast<const unsigned *>(prepared);
     const int64_t n_tiles = (n_nodes + RR_TN - 1) / RR_TN;
     int64_t gx = 256;
-    { const char *d = getenv("GSN_FUSED_GRID"); if (d && atoi(d) > 0) gx = atoi(d); }
+    if (const int g = sw_int(SW_FUSED_GRID, 0); g > 0) gx = g;
     int64_t ranges = gx * RR_NW;
     if (ranges > n_tiles) ranges = n_tiles;
     if (gx > ranges) gx = ranges;
     a.n_ranges = (int)ranges;
     {
-        static const double share = [] { const char *d = getenv("GSN_RP_OLD_SHARE"); return d ? atof(d) : 0.6; }();
+        const char *d = sw_str(SW_RP_OLD_SHARE);
+        const double share = d ? atof(d) : 0.6;
         a.n_split = (ranges == gx * RR_NW && share > 0.0 && share < 1.0) ? (int)((double)n_nodes * share) : 0;
     }
-    static const bool prof_on = [] { const char *d = getenv("GSN_FUSED_PROF"); return d && atoi(d) != 0; }();
+    static const bool prof_on = sw_on(SW_FUSED_PROF, false);
     const void *fn = prof_on ? reinterpret_cast<const void *>(&layer_fused_kernel_rp<4, 2, true>) : reinterpret_cast<const void *>(&layer_fused_kernel_rp<4, 2, false>);
     static DeviceOnce attr_set;
-    const int attr_dev = current_device();
-    if (!attr_set.done(attr_dev)) {
-        hipError_t e0 = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e0 != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(layer_fused_kernel_rp): %s", hipGetErrorString(e0));
-        attr_set.mark(attr_dev);
-    }
-    if (getenv("GSN_CHAIN_TRACE")) fprintf(stderr, "gsn chain: layer_fused_kernel_rp<4,2> nodes %d edges %d grid %lld ranges %d\n", a.n_nodes, a.n_edges, (long long)gx, a.n_ranges);
+    if (int rc = lds_limit(&attr_set, {fn}, "layer_fused_kernel_rp")) return rc;
+    trace("gsn chain: layer_fused_kernel_rp<4,2> nodes %d edges %d grid %lld ranges %d\n", a.n_nodes, a.n_edges, (long long)gx, a.n_ranges);
     if (prof_on) {
-        unsigned long long *prof = nullptr;
-        const size_t pn = 32 + 2 * (size_t)a.n_ranges;
-        (void)hipMalloc(&prof, pn * 8); (void)hipMemsetAsync(prof, 0, pn * 8, st);
-        hipLaunchKernelGGL((layer_fused_kernel_rp<4, 2, true>), dim3((unsigned)gx), dim3(64 * RR_NW), SH::LDS_BYTES, st, a, prof);
-        std::vector<unsigned long long> hv(pn);
-        unsigned long long *h = hv.data();
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(h, prof, pn * 8, hipMemcpyDeviceToHost);
-        (void)hipFree(prof);
-        static int shown = 0;
-        if (shown % 8 == 7) {
+        ProfCounters prof(32 + 2 * (size_t)a.n_ranges, st);
+        hipLaunchKernelGGL((layer_fused_kernel_rp<4, 2, true>), dim3((unsigned)gx), dim3(64 * RR_NW), SH::LDS_BYTES, st, a, prof.ptr());
+        const std::vector<unsigned long long> hv = prof.fetch(st);
+        const unsigned long long *h = hv.data();
+        static EveryNth show_nth{8};
+        const bool show = show_nth();
+        if (show) {
             unsigned long long t_lo = ~0ull, t_hi = 0, e_lo = ~0ull;
             double life = 0.0, lmin = 1e30, lmax = 0.0;
             for (int r = 0; r < a.n_ranges; ++r) {
@@ -838,7 +830,7 @@ int rp_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const g
                     a.n_ranges, (t_hi - t_lo) / 100.0, life / a.n_ranges / 100.0, lmin / 100.0, lmax / 100.0, (e_lo - t_lo) / 100.0,
                     life / a.n_ranges / (double)(t_hi - t_lo));
         }
-        if (shown++ % 8 == 7)
+        if (show)
             for (int w = 0; w < 2; ++w) {
                 const unsigned long long *o = h + 16 * w;
                 const double nb = o[6] ? (double)o[6] : 1.0, nt = o[7] ? (double)o[7] : 1.0;
@@ -848,9 +840,7 @@ int rp_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const g
     } else {
         hipLaunchKernelGGL((layer_fused_kernel_rp<4, 2, false>), dim3((unsigned)gx), dim3(64 * RR_NW), SH::LDS_BYTES, st, a, (unsigned long long *)nullptr);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "layer_fused_kernel_rp: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("layer_fused_kernel_rp");
 }
 
 }  // namespace gsn
@@ -868,7 +858,5 @@ extern "C" int gsn_pack16_rows_hip(const float *src, int64_t rows, int64_t width
     const int64_t total = rows * wq;
     hipLaunchKernelGGL(pack16_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, rows, (int)width, dst,
                        (int)dst_stride, (int)col0, (int)(one_col < 0 ? -1 : one_col), status);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "pack16_rows_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("pack16_rows_kernel");
 }

@@ -763,8 +763,7 @@ __global__ __launch_bounds__(1024) void layer_rr_prepare_kernel(RrPrepArgs p, un
 
 // ------------------------------------------------------------------------------------------------------------------------------
 static bool rr_enabled() {
-    static const int on = [] { const char *d = getenv("GSN_FUSED_RR"); return d ? atoi(d) : 1; }();
-    return on != 0;
+    return sw_int(SW_FUSED_RR, 1) != 0;
 }
 
 static bool rr_stage_ok(const gsn_chain_stage &g, int width) {
@@ -820,9 +819,7 @@ int rr_prepare(const gsn_chain_stage *edge, int64_t d_x, const gsn_chain_stage *
     }
     p.d_x = (int)d_x; p.pack16 = pack16 ? 1 : 0;
     hipLaunchKernelGGL((layer_rr_prepare_kernel<4, 2>), dim3(1), dim3(1024), 0, st, p, reinterpret_cast<unsigned *>(prepared));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "layer_rr_prepare_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("layer_rr_prepare_kernel");
 }
 
 int rr_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const gsn_chain_stage *edge, const float *x, int64_t d_x,
@@ -860,32 +857,24 @@ int rr_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const g
             }
     const int64_t n_tiles = (n_nodes + RR_TN - 1) / RR_TN;
     int64_t gx = 256;
-    { const char *d = getenv("GSN_FUSED_GRID"); if (d && atoi(d) > 0) gx = atoi(d); }
+    if (const int g = sw_int(SW_FUSED_GRID, 0); g > 0) gx = g;
     int64_t ranges = gx * RR_NW;
     if (ranges > n_tiles) ranges = n_tiles;
     if (gx > ranges) gx = ranges;
     a.n_ranges = (int)ranges;
-    static const bool prof_on = [] { const char *d = getenv("GSN_FUSED_PROF"); return d && atoi(d) != 0; }();
+    static const bool prof_on = sw_on(SW_FUSED_PROF, false);
     const void *fn = prof_on ? reinterpret_cast<const void *>(&layer_fused_kernel_rr<4, 2, true>) : reinterpret_cast<const void *>(&layer_fused_kernel_rr<4, 2, false>);
     static DeviceOnce attr_set;
-    const int attr_dev = current_device();
-    if (!attr_set.done(attr_dev)) {
-        hipError_t e0 = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e0 != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(layer_fused_kernel_rr): %s", hipGetErrorString(e0));
-        attr_set.mark(attr_dev);
-    }
+    if (int rc = lds_limit(&attr_set, {fn}, "layer_fused_kernel_rr")) return rc;
     static_assert(SH::LDS_BYTES <= 160 * 1024, "LDS budget");
-    if (getenv("GSN_CHAIN_TRACE")) fprintf(stderr, "gsn chain: layer_fused_kernel_rr<4,2> nodes %d edges %d grid %lld ranges %d\n", a.n_nodes, a.n_edges, (long long)gx, a.n_ranges);
+    trace("gsn chain: layer_fused_kernel_rr<4,2> nodes %d edges %d grid %lld ranges %d\n", a.n_nodes, a.n_edges, (long long)gx, a.n_ranges);
     if (prof_on) {
-        unsigned long long *prof = nullptr;
-        (void)hipMalloc(&prof, 32 * 8); (void)hipMemsetAsync(prof, 0, 32 * 8, st);
-        hipLaunchKernelGGL((layer_fused_kernel_rr<4, 2, true>), dim3((unsigned)gx), dim3(64 * RR_NW), SH::LDS_BYTES, st, a, prof);
-        unsigned long long h[32];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(h, prof, sizeof(h), hipMemcpyDeviceToHost);
-        (void)hipFree(prof);
-        static int shown = 0;
-        if (shown++ % 8 == 7)
+        ProfCounters prof(32, st);
+        hipLaunchKernelGGL((layer_fused_kernel_rr<4, 2, true>), dim3((unsigned)gx), dim3(64 * RR_NW), SH::LDS_BYTES, st, a, prof.ptr());
+        const std::vector<unsigned long long> hv = prof.fetch(st);
+        const unsigned long long *h = hv.data();
+        static EveryNth show{8};
+        if (show())
             for (int w = 0; w < 2; ++w) {
                 const unsigned long long *o = h + 16 * w;
                 const double nb = o[6] ? (double)o[6] : 1.0, nt = o[7] ? (double)o[7] : 1.0;
@@ -895,9 +884,7 @@ int rr_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const g
     } else {
         hipLaunchKernelGGL((layer_fused_kernel_rr<4, 2, false>), dim3((unsigned)gx), dim3(64 * RR_NW), SH::LDS_BYTES, st, a, (unsigned long long *)nullptr);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "layer_fused_kernel_rr: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("layer_fused_kernel_rr");
 }
 
 }  // namespace gsn

@@ -840,8 +840,7 @@ __global__ __launch_bounds__(1024) void layer_w_prepare_kernel(WPrepArgs p, unsi
 
 // ------------------------------------------------------------------------------------------------------------------------------
 static bool w_enabled() {
-    static const int on = [] { const char *d = getenv("GSN_FUSED_W"); return d ? atoi(d) : 1; }();
-    return on != 0;
+    return sw_int(SW_FUSED_W, 1) != 0;
 }
 
 static bool w_stage_ok(const gsn_chain_stage &g, int width) {
@@ -896,20 +895,16 @@ int w_prepare(const gsn_chain_stage *edge, int64_t d_x, const gsn_chain_stage *n
         p.k_total[s] = kt[s]; p.act[s] = gs[s]->act;
     }
     hipLaunchKernelGGL(layer_w_prepare_kernel, dim3(1), dim3(1024), 0, st, p, reinterpret_cast<unsigned *>(prepared));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "layer_w_prepare_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("layer_w_prepare_kernel");
 }
 
 int w_row_exponents(int64_t n_nodes, const float *x, int32_t *row_exp, hipStream_t st) {
     if (n_nodes <= 0) return GSN_OK;
     int64_t gb = (n_nodes + 31) / 32;
     gb = gb < 1 ? 1 : (gb > 2048 ? 2048 : gb);
-    if (getenv("GSN_CHAIN_TRACE")) fprintf(stderr, "gsn chain: layer_w_row_exp_kernel nodes %lld\n", (long long)n_nodes);
+    trace("gsn chain: layer_w_row_exp_kernel nodes %lld\n", (long long)n_nodes);
     hipLaunchKernelGGL(layer_w_row_exp_kernel, dim3((unsigned)gb), dim3(256), 0, st, x, (int)n_nodes, row_exp);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "layer_w_row_exp_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("layer_w_row_exp_kernel");
 }
 
 int w_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const gsn_chain_stage *edge, const float *x, int64_t d_x,
@@ -950,20 +945,14 @@ int w_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const gs
         for (int q = 0; q < 4; ++q) { a.zq[q].base = reinterpret_cast<unsigned long long>(x); a.zq[q].stride = 0; a.zq[q].role = 0; }
     const int64_t n_tiles = (n_nodes + W_TN - 1) / W_TN;
     int64_t gx = 256;
-    { const char *d = getenv("GSN_FUSED_GRID"); if (d && atoi(d) > 0) gx = atoi(d); }
+    if (const int g = sw_int(SW_FUSED_GRID, 0); g > 0) gx = g;
     int64_t ranges = gx * 4;
     if (ranges > n_tiles) ranges = n_tiles;
     if (gx > ranges) gx = ranges;
     a.n_ranges = (int)ranges;
-    static const bool prof_on = [] { const char *d = getenv("GSN_FUSED_PROF"); return d && atoi(d) != 0; }();
+    static const bool prof_on = sw_on(SW_FUSED_PROF, false);
     static DeviceOnce attr_set;
-    const int attr_dev = current_device();
-    if (!attr_set.done(attr_dev)) {
-        hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(&layer_fused_kernel_w<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e0 == hipSuccess) e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(&layer_fused_kernel_w<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e0 != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(layer_fused_kernel_w): %s", hipGetErrorString(e0));
-        attr_set.mark(attr_dev);
-    }
+    if (int rc = lds_limit(&attr_set, {kernel_ptr(&layer_fused_kernel_w<false>), kernel_ptr(&layer_fused_kernel_w<true>)}, "layer_fused_kernel_w")) return rc;
     static_assert(SH::LDS_BYTES <= 160 * 1024, "LDS budget");
     // the row exponents of x: one int per node, stream-ordered scratch
     int32_t *xe = row_exp;
@@ -973,24 +962,20 @@ int w_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const gs
     }
     a.xe = x_row_exp ? x_row_exp : xe;
     a.xe_out = out_row_exp;
-    const bool trace = getenv("GSN_CHAIN_TRACE") != nullptr;
     if (!x_row_exp) {
         int64_t gb = (n_nodes + 31) / 32;
         gb = gb < 1 ? 1 : (gb > 2048 ? 2048 : gb);
-        if (trace) fprintf(stderr, "gsn chain: layer_w_row_exp_kernel nodes %d\n", a.n_nodes);
+        trace("gsn chain: layer_w_row_exp_kernel nodes %d\n", a.n_nodes);
         hipLaunchKernelGGL(layer_w_row_exp_kernel, dim3((unsigned)gb), dim3(256), 0, st, x, a.n_nodes, xe);
     }
-    if (trace) fprintf(stderr, "gsn chain: layer_fused_kernel_w nodes %d edges %d grid %lld ranges %d\n", a.n_nodes, a.n_edges, (long long)gx, a.n_ranges);
+    trace("gsn chain: layer_fused_kernel_w nodes %d edges %d grid %lld ranges %d\n", a.n_nodes, a.n_edges, (long long)gx, a.n_ranges);
     if (prof_on) {
-        unsigned long long *prof = nullptr;
-        (void)hipMalloc(&prof, 32 * 8); (void)hipMemsetAsync(prof, 0, 32 * 8, st);
-        hipLaunchKernelGGL((layer_fused_kernel_w<true>), dim3((unsigned)gx), dim3(256), SH::LDS_BYTES, st, a, prof);
-        unsigned long long h[32];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(h, prof, sizeof(h), hipMemcpyDeviceToHost);
-        (void)hipFree(prof);
-        static int shown = 0;
-        if (shown++ % 8 == 7)
+        ProfCounters prof(32, st);
+        hipLaunchKernelGGL((layer_fused_kernel_w<true>), dim3((unsigned)gx), dim3(256), SH::LDS_BYTES, st, a, prof.ptr());
+        const std::vector<unsigned long long> hv = prof.fetch(st);
+        const unsigned long long *h = hv.data();
+        static EveryNth show{8};
+        if (show())
             for (int w = 0; w < 2; ++w) {
                 const unsigned long long *o = h + 16 * w;
                 const double nu = o[6] ? (double)o[6] : 1.0, nt = o[7] ? (double)o[7] : 1.0;
@@ -1000,10 +985,9 @@ int w_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const gs
     } else {
         hipLaunchKernelGGL((layer_fused_kernel_w<false>), dim3((unsigned)gx), dim3(256), SH::LDS_BYTES, st, a, (unsigned long long *)nullptr);
     }
-    hipError_t e = hipGetLastError();
+    const int rc = launch_check("layer_fused_kernel_w");
     if (!row_exp && !x_row_exp) (void)hipFreeAsync(xe, st);
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "layer_fused_kernel_w: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return rc;
 }
 
 }  // namespace gsn

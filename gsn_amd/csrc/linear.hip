@@ -552,20 +552,12 @@ template <bool STATS, bool VEC4, int D>
 static int launch_linear_bf16_impl(const LinArgs &a, int k_pad, int64_t n_tiles, int col_tiles, hipStream_t st) {
     const size_t lds = ((size_t)12 * BPLANE + (size_t)2 * MAX_BLOCKS * BM) * 4;
     static DeviceOnce attr_set;
-    const int attr_dev = current_device();
-    if (!attr_set.done(attr_dev)) {
-        hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_fwd_bf16_kernel<STATS, VEC4, D>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e0 != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(linear_fwd_bf16_kernel): %s", hipGetErrorString(e0));
-        attr_set.mark(attr_dev);
-    }
+    if (int rc = lds_limit(&attr_set, {kernel_ptr(&linear_fwd_bf16_kernel<STATS, VEC4, D>)}, "linear_fwd_bf16_kernel")) return rc;
     int64_t gx = 256 / col_tiles;   // persistent: one workgroup per CU in total
     if (gx < 1) gx = 1;
     if (gx > n_tiles) gx = n_tiles;
     hipLaunchKernelGGL((linear_fwd_bf16_kernel<STATS, VEC4, D>), dim3((unsigned)gx, (unsigned)col_tiles), dim3(512), lds, st, a, k_pad);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "linear_fwd_bf16_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("linear_fwd_bf16_kernel");
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -815,36 +807,20 @@ template <bool STATS, bool VEC4, bool WT = false>
 static int launch_linear_bf16_small(const LinArgs &a, int k_pad, int col_tiles, hipStream_t st) {
     const size_t lds = ((size_t)2 * SBUF + (size_t)MAX_BLOCKS * SBM) * 4;
     static DeviceOnce attr_set;
-    const int attr_dev = current_device();
-    if (!attr_set.done(attr_dev)) {
-        hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_fwd_bf16_small_kernel<STATS, VEC4, WT>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e0 != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(linear_fwd_bf16_small_kernel): %s", hipGetErrorString(e0));
-        attr_set.mark(attr_dev);
-    }
+    if (int rc = lds_limit(&attr_set, {kernel_ptr(&linear_fwd_bf16_small_kernel<STATS, VEC4, WT>)}, "linear_fwd_bf16_small_kernel")) return rc;
     const int64_t gx = (a.m_rows + SBM - 1) / SBM;
     hipLaunchKernelGGL((linear_fwd_bf16_small_kernel<STATS, VEC4, WT>), dim3((unsigned)gx, (unsigned)col_tiles), dim3(256), lds, st, a, k_pad);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "linear_fwd_bf16_small_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("linear_fwd_bf16_small_kernel");
 }
 
 template <bool VEC4, bool WT>
 static int launch_linear_bf16_splitk(const LinArgs &a, int k_pad, int col_tiles, int splits, hipStream_t st) {
     const size_t lds = ((size_t)2 * SBUF + (size_t)MAX_BLOCKS * SBM) * 4;
     static DeviceOnce attr_set;
-    const int attr_dev = current_device();
-    if (!attr_set.done(attr_dev)) {
-        hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_fwd_bf16_small_kernel<false, VEC4, WT, true>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e0 != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(linear_fwd_bf16_small_kernel): %s", hipGetErrorString(e0));
-        attr_set.mark(attr_dev);
-    }
+    if (int rc = lds_limit(&attr_set, {kernel_ptr(&linear_fwd_bf16_small_kernel<false, VEC4, WT, true>)}, "linear_fwd_bf16_small_kernel")) return rc;
     const int64_t gx = (a.m_rows + SBM - 1) / SBM;
     hipLaunchKernelGGL((linear_fwd_bf16_small_kernel<false, VEC4, WT, true>), dim3((unsigned)gx, (unsigned)col_tiles, (unsigned)splits), dim3(256), lds, st, a, k_pad);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "linear_fwd_bf16_small_kernel (split K): %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("linear_fwd_bf16_small_kernel (split K)");
 }
 
 template <bool STATS, bool VEC4>
@@ -857,17 +833,9 @@ static int launch_linear_bf16(const LinArgs &a, int k_pad, int64_t n_tiles, int 
 template <bool STATS, bool WRES>
 static int launch_linear(const LinArgs &a, int k_pad, size_t lds, int64_t gx, int col_tiles, hipStream_t st) {
     static DeviceOnce attr_set;
-    const int attr_dev = current_device();
-    if (!attr_set.done(attr_dev)) {
-        hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_fwd_kernel<STATS, WRES>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e0 != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(linear_fwd_kernel): %s", hipGetErrorString(e0));
-        attr_set.mark(attr_dev);
-    }
+    if (int rc = lds_limit(&attr_set, {kernel_ptr(&linear_fwd_kernel<STATS, WRES>)}, "linear_fwd_kernel")) return rc;
     hipLaunchKernelGGL((linear_fwd_kernel<STATS, WRES>), dim3((unsigned)gx, (unsigned)col_tiles), dim3(256), lds, st, a, k_pad);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "linear_fwd_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("linear_fwd_kernel");
 }
 
 }  // namespace gsn
@@ -897,9 +865,9 @@ extern "C" int gsn_linear_fwd_strided_hip(int64_t m_rows, int n_blocks, const gs
 // Ranges of K slices per output tile (1: no split).  Taken where the 32-row tiles leave most CUs idle and the chain is long: at most two
 // workgroups per CU in total, at least three slices per range, at most four ranges.  GSN_LINEAR_SPLITK_RANGES=n forces n ranges (0 or 1: off).
 extern "C" int gsn_linear_splitk_plan(int64_t m_rows, int64_t k_total, int64_t n_out) {
-    static const int forced = [] { const char *d = getenv("GSN_LINEAR_SPLITK_RANGES"); return d ? atoi(d) : -1; }();
-    static const int small_max = [] { const char *d = getenv("GSN_LINEAR_SMALL_MAX"); return d ? atoi(d) : 96; }();
-    static const bool bf16x6 = [] { const char *d = getenv("GSN_LINEAR_BF16X6"); return !(d && atoi(d) == 0); }();
+    const int forced = sw_int(SW_LINEAR_SPLITK_RANGES, -1);
+    const int small_max = sw_int(SW_LINEAR_SMALL_MAX, 96);
+    const bool bf16x6 = sw_on(SW_LINEAR_BF16X6, true);
     if (forced == 0 || !bf16x6 || m_rows <= 0 || k_total <= 0 || n_out <= 0) return 1;
     const int64_t n_tiles = (m_rows + BM - 1) / BM, col_tiles = (n_out + BN - 1) / BN;
     if (n_tiles * col_tiles > small_max) return 1;
@@ -991,13 +959,13 @@ static int linear_fwd_impl(int64_t m_rows, int n_blocks, const gsn_block *blocks
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int k_pad = (k_total + BK - 1) / BK * BK;
     {   // default: the bf16x6 kernel (GSN_LINEAR_BF16X6=0 selects the fp32-MFMA kernel below for A/B measurements)
-        static const bool bf16x6 = [] { const char *d = getenv("GSN_LINEAR_BF16X6"); return !(d && atoi(d) == 0); }();
+        const bool bf16x6 = sw_on(SW_LINEAR_BF16X6, true);
         bool vec4 = !strided && (k_total & 3) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0;   // float4 staging of A and W
         for (int b = 0; b < n_blocks; ++b)
             if ((a.bwidth[b] & 3) || (reinterpret_cast<uintptr_t>(a.bdata[b]) & 15)) vec4 = false;
-        { const char *d = getenv("GSN_LINEAR_VEC4"); if (d && atoi(d) == 0) vec4 = false; }
+        if (!sw_on(SW_LINEAR_VEC4, true)) vec4 = false;
         // few 128-row tiles: 32-row tiles on four times as many CUs (GSN_LINEAR_SMALL_MAX = the largest count of 128-row tiles that takes them, 0 = never)
-        static const int small_max = [] { const char *d = getenv("GSN_LINEAR_SMALL_MAX"); return d ? atoi(d) : 96; }();
+        const int small_max = sw_int(SW_LINEAR_SMALL_MAX, 96);
         if (bf16x6 && n_tiles * col_tiles <= small_max) {
             if (vec4) return stats ? launch_linear_bf16_small<true, true>(a, k_pad, col_tiles, st) : launch_linear_bf16_small<false, true>(a, k_pad, col_tiles, st);
             if (strided && w_rs < w_cs && ((n_out - 1) * w_rs + (int64_t)(k_total - 1) * w_cs) < (int64_t(1) << 30))     // a transposed view: staged along its contiguous direction (32-bit byte offsets)

@@ -847,9 +847,7 @@ static int l16_prepare(const float *W, int64_t n_out, int64_t k_total, int64_t w
         return set_error(GSN_E_UNSUPPORTED, "gsn_linear_f16x3_prepare_hip: weight planes of 2 GiB and more are not supported");
     hipLaunchKernelGGL(lin16_prepare_kernel, dim3((unsigned)n_out), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), W, (int)n_out, (int)k_total,
                        k_pad, reinterpret_cast<_Float16 *>(planes), col_inv, w_rs, w_cs);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "lin16_prepare_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("lin16_prepare_kernel");
 }
 
 extern "C" int gsn_linear_f16x3_prepare_hip(const float *W, int64_t n_out, int64_t k_total, void *planes, float *col_inv, void *stream) {
@@ -891,7 +889,7 @@ static int l16_rows(int64_t m_rows, int n_blocks, const gsn_block *blocks, float
 
 static void l16_split_launch(const L16Args &a, hipStream_t st) {
     // one block of 16-byte aligned rows: the grid-stride kernel (GSN_L16_SPLIT_WGS workgroups, default 1024; 0: the one-tile-per-workgroup kernel)
-    static const int64_t split_wgs = [] { const char *e = getenv("GSN_L16_SPLIT_WGS"); return e ? (int64_t)atoll(e) : (int64_t)1024; }();
+    const int64_t split_wgs = sw_int64(SW_L16_SPLIT_WGS, 1024);
     int64_t gx = a.m_pad / 32;
     if (split_wgs > 0 && a.n_blocks == 1 && (a.w0 & 3) == 0) {
         if (gx > split_wgs) gx = split_wgs;
@@ -929,12 +927,12 @@ static int l16_fwd(int64_t m_rows, int n_blocks, const gsn_block *blocks, const 
     // 300 -> 600 194 vs 188 us, 600 -> 300 178 vs 183 us, 196 608 x 300 -> 600 295 vs 318 us (scripts/gpu/r6_l16_wide.py; config-4 step 16.68 vs
     // 16.45 ms): neither the column waste nor the traffic is what bounds this kernel.
     const int wm = 2;
-    const char *wide_env = getenv("GSN_L16_WIDE");                          // (read per call: a test switches it)
+    const char *wide_env = sw_str(SW_L16_WIDE);
     const bool wide_on = wide_env && wide_env[0] == '1';
     const int64_t cols128 = (n_out + 127) / 128 * 128, cols320 = (n_out + 319) / 320 * 320;
-    const bool vec_ok = n_out % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && !getenv("GSN_L16_NOVEC");
-    const bool wide = wide_on && vec_ok && n_out > 256 && cols320 <= cols128 && (m_rows + 127) / 128 * (cols320 / 320) >= 512 && !getenv("GSN_L16_REGSTAGE") &&
-                      !getenv("GSN_L16_PROF") && !getenv("GSN_L16_DBG");
+    const bool vec_ok = n_out % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && !sw_present(SW_L16_NOVEC);
+    const bool wide = wide_on && vec_ok && n_out > 256 && cols320 <= cols128 && (m_rows + 127) / 128 * (cols320 / 320) >= 512 && !sw_present(SW_L16_REGSTAGE) &&
+                      !sw_present(SW_L16_PROF) && !sw_present(SW_L16_DBG);
     const int nj = wide ? 5 : 2;
     const int bm = 64 * wm, bn = 64 * nj;
     const int64_t n_tiles = (m_rows + bm - 1) / bm;
@@ -945,30 +943,24 @@ static int l16_fwd(int64_t m_rows, int n_blocks, const gsn_block *blocks, const 
     const int64_t need = (n_tiles + 7) / 8;
     if (groups > need) groups = (int)need;
     a.col_tiles = col_tiles; a.groups = groups;
-    a.dbg = getenv("GSN_L16_DBG") ? atoi(getenv("GSN_L16_DBG")) : 0;
-    static const bool want_prof = getenv("GSN_L16_PROF") != nullptr;
-    a.prof = nullptr;
-    if (want_prof && hipMalloc(reinterpret_cast<void **>(&a.prof), 64) != hipSuccess) a.prof = nullptr;
+    a.dbg = sw_int(SW_L16_DBG, 0);
+    static const bool want_prof = sw_present(SW_L16_PROF);
+    ProfCounters prof(want_prof ? 8 : 0, st);
+    a.prof = prof.ptr();
     size_t lds = (size_t)2 * (bm + bn) * P_PITCH + 8 * bn + 4 * (2 * nj * 64 + 2 * nj * 32);   // slice buffers | epilogue tables
-    if (getenv("GSN_CHAIN_TRACE"))
-        fprintf(stderr, "gsn linear: linear_f16x3_kernel (%d x %d tiles) M %lld K %d N %d grid 8 x %d x %d\n", bm, bn, (long long)m_rows, a.k_total, (int)n_out,
+    trace("gsn linear: linear_f16x3_kernel (%d x %d tiles) M %lld K %d N %d grid 8 x %d x %d\n", bm, bn, (long long)m_rows, a.k_total, (int)n_out,
                 groups, col_tiles);
     const dim3 grid((unsigned)(8 * groups * col_tiles));
-    const bool vec = n_out % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && !getenv("GSN_L16_NOVEC");      // 16-byte output stores
+    const bool vec = n_out % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && !sw_present(SW_L16_NOVEC);      // 16-byte output stores
     if (stats && (!vec || act != 0 || bn_scale))
         return set_error(GSN_E_UNSUPPORTED, "gsn_linear_f16x3_fwd_stats_hip: statistics go with plain pre-BN rows (act 0, no bn vectors), n_out a multiple of 4, out 16-byte aligned");
     static DeviceOnce attr_set[9];
-    const int attr_dev = current_device();
-    hipError_t e0 = hipSuccess;
+    int attr_rc = GSN_OK;
     auto launch = [&](auto kern, int which) {
-        if (!attr_set[which].done(attr_dev)) {
-            e0 = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e0 != hipSuccess) return;
-            attr_set[which].mark(attr_dev);
-        }
-        hipLaunchKernelGGL(kern, grid, dim3(128 * wm), lds, st, a);
+        attr_rc = lds_limit(&attr_set[which], {kernel_ptr(kern)}, "linear_f16x3_kernel");
+        if (attr_rc == GSN_OK) hipLaunchKernelGGL(kern, grid, dim3(128 * wm), lds, st, a);
     };
-    static const bool reg_stage = getenv("GSN_L16_REGSTAGE") != nullptr;  // (A/B: slices staged through registers)
+    static const bool reg_stage = sw_present(SW_L16_REGSTAGE);  // (A/B: slices staged through registers)
     const size_t lds_dma = (size_t)2 * (D_BM + bn) * L_LINE + 4 * (2 * D_BM + 2 * bn) + 4 * (2 * nj * 64 + 2 * nj * 32);   // slice buffers | row scales, column tables | store offsets
     if (stats && wide) {
         lds = lds_dma;
@@ -987,19 +979,14 @@ static int l16_fwd(int64_t m_rows, int n_blocks, const gsn_block *blocks, const 
         else if (!vec) launch(linear_f16x3_dma_kernel<2, false, false>, 4);
         else launch(linear_f16x3_dma_kernel<2, false, true>, 5);
     }
-    if (e0 != hipSuccess) return set_error(GSN_E_HIP, "hipFuncSetAttribute(linear_f16x3_kernel): %s", hipGetErrorString(e0));
+    if (attr_rc != GSN_OK) return attr_rc;
     if (a.prof) {
-        unsigned long long h[8];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(h, a.prof, 64, hipMemcpyDeviceToHost);
-        (void)hipFree(a.prof);
+        const std::vector<unsigned long long> h = prof.fetch(st);
         const double n = h[5] ? (double)h[5] : 1.0, nt = h[6] ? (double)h[6] : 1.0;
         fprintf(stderr, "l16prof: per slice: fetch issue %.0f products %.0f stage(+load wait) %.0f barrier %.0f | epilogue %.0f per tile (%llu slices, %llu tiles)\n",
                 h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[4] / nt, h[5], h[6]);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "linear_f16x3_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("linear_f16x3_kernel");
 }
 
 extern "C" int gsn_linear_f16x3_fwd_hip(int64_t m_rows, int n_blocks, const gsn_block *blocks, const void *planes, const float *col_inv,
@@ -1024,9 +1011,7 @@ extern "C" int gsn_linear_f16x3_split_rows_hip(int64_t m_rows, int n_blocks, con
     const int rc = l16_rows(m_rows, n_blocks, blocks, row_scratch, a, "gsn_linear_f16x3_split_rows_hip");
     if (rc != GSN_OK) return rc;
     l16_split_launch(a, reinterpret_cast<hipStream_t>(stream));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "lin16_split_rows_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("lin16_split_rows_kernel");
 }
 
 extern "C" int gsn_linear_f16x3_fwd_presplit_hip(int64_t m_rows, int n_blocks, const gsn_block *blocks, const void *planes, const float *col_inv,

@@ -1107,9 +1107,7 @@ __global__ __launch_bounds__(256) void segment_sum_wg_kernel(PropArgs p) {
 }
 
 static int hip_check(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "%s: %s", what, hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("%s", what);
 }
 
 template <int VEC, int LPR, int MAXC>
@@ -1176,7 +1174,7 @@ static int launch_cat_pipe(const PropArgs &p, hipStream_t st) {
     if (long_segments) l = q <= 8 ? 8 : q <= 16 ? 16 : q <= 32 ? 32 : 64;
     else if (p.da && !p.db && !p.dc && q > 16 && q <= 32) { l = 32; u = 2; }
     if (l && (q + l - 1) / l > 2) u = 2;
-    if (const char *e = getenv("GSN_PROP_CP")) sscanf(e, "%d,%d,%d", &l, &u, &b);
+    if (const char *e = sw_str(SW_PROP_CP)) sscanf(e, "%d,%d,%d", &l, &u, &b);
     if (l == 0) return -1;
     const int m = (q + l - 1) / l;
     const int64_t cap = b;
@@ -1196,7 +1194,7 @@ static int launch_cat_pipe(const PropArgs &p, hipStream_t st) {
 static int launch_relu_sum3(const PropArgs &p, hipStream_t st) {
     const int q = p.d_out / 4;
     int l = q <= 80 ? 16 : 32, u = 0, n = 0, b = 256 * 8 * 4;
-    if (const char *e = getenv("GSN_PROP_RS")) sscanf(e, "%d,%d,%d,%d", &l, &u, &n, &b);
+    if (const char *e = sw_str(SW_PROP_RS)) sscanf(e, "%d,%d,%d,%d", &l, &u, &n, &b);
     if (l == 0) return -1;
     if (u == 0) u = l == 16 ? (p.n_self ? 1 : 2) : (p.n_self ? 2 : 4);
     const bool nt = n != 0;
@@ -1446,14 +1444,8 @@ extern "C" int gsn_csr_build_hip(int64_t n_nodes, int64_t n_edges, const int64_t
         return set_error(GSN_E_UNSUPPORTED, "gsn_csr_build_hip: more than 2^31 edges or vertices");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (n_nodes <= CSR_SMALL_NODES && n_edges <= CSR_SMALL_EDGES) {
-        static DeviceOnce lds_set;
-        const int lds_dev = current_device();
-        if (!lds_set.done(lds_dev)) {   // up to 2 x 48 KiB of dynamic LDS
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(&csr_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    2 * (CSR_SMALL_NODES + 1) * (int)sizeof(int32_t)) != hipSuccess)
-                return set_error(GSN_E_HIP, "gsn_csr_build_hip: cannot raise the LDS limit of csr_small_kernel");
-            lds_set.mark(lds_dev);
-        }
+        static DeviceOnce lds_set;   // up to 2 x 48 KiB of dynamic LDS
+        if (int rc = lds_limit(&lds_set, {kernel_ptr(&csr_small_kernel)}, "csr_small_kernel", 2 * (CSR_SMALL_NODES + 1) * (int)sizeof(int32_t))) return rc;
         route_note("csr_small", 1);
         hipLaunchKernelGGL(csr_small_kernel, dim3(1), dim3(1024), (size_t)(2 * (n_nodes + 1)) * sizeof(int32_t), st, index, n_edges,
                            (int)n_nodes, seg_ptr, perm, sorted_target, other, sorted_other);
@@ -1595,7 +1587,7 @@ static int propagate_fwd_impl(int kind, int64_t n_nodes, int64_t n_edges, const 
         if (q <= 16) return launch_fwd<4, 16, 1>(p, st);
         // lanes per target row: the widths up to 128 floats take 16 (four targets per wave: four rows' loads in flight per wave instead of two
         // -- 0.656 -> 0.463 ms for the 112-wide concatenation, 0.422 -> 0.394 at d = 128, r04); GSN_PROP_LPR=8/16/32/64 forces a mapping
-        static const int forced = [] { const char *e = getenv("GSN_PROP_LPR"); return e ? atoi(e) : 0; }();
+        const int forced = sw_int(SW_PROP_LPR, 0);
         if (forced) {
             const int m = (int)((q + forced - 1) / forced);
             if (forced == 8) { if (m <= 1) return launch_fwd<4, 8, 1>(p, st); if (m <= 2) return launch_fwd<4, 8, 2>(p, st); if (m <= 4) return launch_fwd<4, 8, 4>(p, st); }
@@ -1651,8 +1643,8 @@ extern "C" int gsn_propagate_bwd_fold_self_hip(int64_t n_nodes, int64_t n_edges,
                                                int64_t db, const float *c, int64_t dc, const float *g_out, float *g_a, float *g_b, float *g_c,
                                                const float *eps, double *g_eps, void *stream) {
     route_clear();
-    static const bool pipe = [] { const char *e = getenv("GSN_PROP_BWD_PIPE"); return !e || atoi(e) != 0; }();
-    static const bool fold = [] { const char *e = getenv("GSN_PROP_FOLD_SELF"); return !e || atoi(e) != 0; }();
+    const bool pipe = sw_on(SW_PROP_BWD_PIPE, true);
+    const bool fold = sw_on(SW_PROP_FOLD_SELF, true);
     const bool need_edge = (g_b && db) || (g_c && dc);
     if (!fold || !pipe || !a || !g_a || !g_out || d <= 0 || d > 320 || (d & 3) || n_edges <= 0 || !need_edge || (db && db != d) || (dc && dc != d) ||
         (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)g_out | (uintptr_t)g_a | (uintptr_t)g_b | (uintptr_t)g_c) % 16) != 0)
@@ -1697,7 +1689,7 @@ static int propagate_bwd_impl(int kind, int64_t n_nodes, int64_t n_edges, const 
         if (vec4 || cat4) {
             int64_t blocks = (n_edges + 15) / 16;
             if (blocks > 16384) blocks = 16384;
-            static const bool pipe = [] { const char *e = getenv("GSN_PROP_BWD_PIPE"); return !e || atoi(e) != 0; }();
+            const bool pipe = sw_on(SW_PROP_BWD_PIPE, true);
             if (vec4 && pipe && d_out <= 320) {
                 route_note("propagate_bwd_edge_relu4p", blocks);
                 hipLaunchKernelGGL(propagate_bwd_edge_relu4p_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
@@ -1724,7 +1716,7 @@ static int propagate_bwd_impl(int kind, int64_t n_nodes, int64_t n_edges, const 
         if (edge4) {
             int64_t blocks = (n_nodes + 15) / 16;
             if (blocks > 16384) blocks = 16384;
-            static const bool pipe = [] { const char *e = getenv("GSN_PROP_BWD_PIPE"); return !e || atoi(e) != 0; }();
+            const bool pipe = sw_on(SW_PROP_BWD_PIPE, true);
             if (p.fold_self) {
                 if (!(pipe && d_out <= 320)) return set_error(GSN_E_UNSUPPORTED, "gsn_propagate_bwd_fold_self_hip: the folded self term rides the pipelined node pass (d <= 320)");
                 route_note("propagate_bwd_node_edge4p<fold%d>", blocks, 1);
@@ -1806,12 +1798,7 @@ extern "C" int gsn_csr_build_graphs_hip(int64_t n_graphs, const int64_t *node_pt
                          (long long)max_nodes, (long long)max_edges, (long long)lds);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     static DeviceOnce lds_set;
-    const int lds_dev = current_device();
-    if (!lds_set.done(lds_dev)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&csr_graphs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) != hipSuccess)
-            return set_error(GSN_E_HIP, "gsn_csr_build_graphs_hip: cannot raise the LDS limit of csr_graphs_kernel");
-        lds_set.mark(lds_dev);
-    }
+    if (int rc = lds_limit(&lds_set, {kernel_ptr(&csr_graphs_kernel)}, "csr_graphs_kernel", 64 * 1024)) return rc;
     route_note("csr_graphs", n_graphs);
     hipLaunchKernelGGL(csr_graphs_kernel, dim3((unsigned)n_graphs), dim3(64), (size_t)lds, st, node_ptr, edge_ptr, (int)n_graphs, n_nodes, n_edges,
                        (int)max_nodes, (int)max_edges, index, other, seg_ptr, perm, sorted_target, sorted_other, status);

@@ -465,7 +465,7 @@ extern "C" int gsn_wgrad_f16x3_hip(int64_t m_rows, int64_t n_out, int64_t k_tota
     const int tn = (int)((n_out + WF_T - 1) / WF_T), tk = (int)((k_total + WF_T - 1) / WF_T);
     a.tn = tn; a.tk = tk;
     // slabs as gsn_wgrad_hip takes them (one round of ~256 workgroups for small and mid-size calls, 2 048 workgroups for large ones)
-    static const int64_t wg_target = [] { const char *e = getenv("GSN_WGRAD16_WGS"); const int64_t v = e ? atoll(e) : 0; return v > 0 ? v : (int64_t)0; }();
+    const int64_t wg_target_env = sw_int64(SW_WGRAD16_WGS, 0), wg_target = wg_target_env > 0 ? wg_target_env : 0;
     int64_t rows_per = gsn_wgrad_slab_rows(m_rows, (int64_t)tn * tk, wg_target);
     if (rows_per > WF_MAX_ROWS) rows_per = WF_MAX_ROWS;
     rows_per = (rows_per + 47) / 48 * 48;                                  // (the kernel's loop: three 16-row steps per trip)
@@ -473,39 +473,33 @@ extern "C" int gsn_wgrad_f16x3_hip(int64_t m_rows, int64_t n_out, int64_t k_tota
     const int64_t slabs = (m_rows + rows_per - 1) / rows_per;
     const int64_t slab_groups = (slabs + 7) / 8;
     if (slab_groups * tn * tk * 8 >= ((int64_t)1 << 31)) return set_error(GSN_E_UNSUPPORTED, "gsn_wgrad_f16x3_hip: too many workgroups");
-    if (getenv("GSN_CHAIN_TRACE"))
-        fprintf(stderr, "gsn wgrad: wgrad_f16x3_kernel M %lld N %d K %d slabs %lld x %lld rows\n", (long long)m_rows, (int)n_out, (int)k_total, (long long)slabs,
+    trace("gsn wgrad: wgrad_f16x3_kernel M %lld N %d K %d slabs %lld x %lld rows\n", (long long)m_rows, (int)n_out, (int)k_total, (long long)slabs,
                 (long long)rows_per);
     const dim3 grid((unsigned)(slab_groups * tn * tk * 8));
     const size_t lds = (size_t)4 * 4 * 2 * (64 * 16 + 128) + 16 + (size_t)(rows_per + 16) * 6;      // fragments | emax | the two scale tables, raw exponents
-    static const int valu = [] { const char *e = getenv("GSN_WGRAD16_VALU"); const int v = e ? atoi(e) : 3; return v; }();
+    const int valu = sw_int(SW_WGRAD16_VALU, 3);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    a.dbg = getenv("GSN_WGRAD16_DBG") ? atoi(getenv("GSN_WGRAD16_DBG")) : 0;
+    a.dbg = sw_int(SW_WGRAD16_DBG, 0);
     // GSN_WGRAD16_DMA=1: the LDS-DMA + transposing-read kernel (read per call: tests switch it).  Measured on one box at 105 083 x 300 x 600:
     // 240-248 us against 218-227 us for the register-staged kernel -- fewer vector and LDS instructions (SQ_INSTS_VALU 4.5e7 -> 2.9e7,
     // SQ_LDS_IDX_ACTIVE 2.7e7 -> 1.6e7), three workgroups per CU instead of two, the matrix pipe mostly hidden (no products: -35 us), but 74 us of
     // waiting for lines that the staged kernel hides behind its own vector work; both move the same 1.5 GB from L2 to the CUs, which bounds
     // either at ~150 us.  Not the default.
-    const char *dma_env = getenv("GSN_WGRAD16_DMA");
+    const char *dma_env = sw_str(SW_WGRAD16_DMA);
     const bool dma = dma_env && dma_env[0] == '1';
     if (dma) {
         const size_t lds_dma = (size_t)3 * 16384 + 16 + (size_t)(rows_per + 16) * 4;      // three buffers | emax | the two scale tables
         if (a.dbg) hipLaunchKernelGGL((wgrad_f16x3_dma_kernel<true>), grid, dim3(256), lds_dma, st, a);
         else hipLaunchKernelGGL((wgrad_f16x3_dma_kernel<false>), grid, dim3(256), lds_dma, st, a);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return set_error(GSN_E_HIP, "wgrad_f16x3_dma_kernel: %s", hipGetErrorString(e));
-        return GSN_OK;
+        return launch_check("wgrad_f16x3_dma_kernel");
     }
-    a.dbg = getenv("GSN_WGRAD16_DBG") ? atoi(getenv("GSN_WGRAD16_DBG")) : 0;
-    a.prof = nullptr;
-    if ((a.dbg & 16) && hipMalloc(reinterpret_cast<void **>(&a.prof), 128) != hipSuccess) a.prof = nullptr;
+    a.dbg = sw_int(SW_WGRAD16_DBG, 0);
+    ProfCounters prof((a.dbg & 16) ? 16 : 0, st);
+    a.prof = prof.ptr();
     if (a.dbg) {
         hipLaunchKernelGGL((wgrad_f16x3_kernel<3, true>), grid, dim3(256), lds, st, a);
         if (a.prof) {
-            unsigned long long h[16];
-            (void)hipStreamSynchronize(st);
-            (void)hipMemcpy(h, a.prof, 128, hipMemcpyDeviceToHost);
-            (void)hipFree(a.prof);
+            const std::vector<unsigned long long> h = prof.fetch(st);
             fprintf(stderr, "wgrad16prof: workgroup 0 wave 0: prologue %llu | loop %llu (%llu steps: %.0f per step, of it waiting at the barrier %.0f) | epilogue %llu cycles (100 MHz clock)\n",
                     h[0], h[1], h[4], (double)h[1] / (double)(h[4] ? h[4] : 1), (double)h[2] / (double)(h[4] ? h[4] : 1), h[3]);
             const double n = (double)(h[4] ? h[4] : 1);
@@ -516,7 +510,5 @@ extern "C" int gsn_wgrad_f16x3_hip(int64_t m_rows, int64_t n_out, int64_t k_tota
     else if (valu == 2) hipLaunchKernelGGL((wgrad_f16x3_kernel<2, false>), grid, dim3(256), lds, st, a);
     else if (valu == 4) hipLaunchKernelGGL((wgrad_f16x3_kernel<4, false>), grid, dim3(256), lds, st, a);
     else hipLaunchKernelGGL((wgrad_f16x3_kernel<3, false>), grid, dim3(256), lds, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(GSN_E_HIP, "wgrad_f16x3_kernel: %s", hipGetErrorString(e));
-    return GSN_OK;
+    return launch_check("wgrad_f16x3_kernel");
 }

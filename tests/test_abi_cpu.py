@@ -115,6 +115,18 @@ def harness():
     return ctypes.CDLL(so)
 
 
+def test_switch_table_and_readers_on_host():
+    """The switch table of csrc/ (switches.h) and its readers, by a stand-alone program built from tests/switches_harness.cpp and
+    switches.cpp alone: defaults, every reader kind on "0" / "1" / "" / "7", LIVE against ONCE, unique GSN_ names, a LIVE trace switch."""
+    exe = os.path.join(REPO, "tests", "_build", "switches_harness")
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    srcs = [os.path.join(REPO, "tests", "switches_harness.cpp"), os.path.join(REPO, "gsn_amd", "csrc", "switches.cpp")]
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-pthread", "-o", exe] + srcs)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert r.stdout.startswith("switches ok:")
+
+
 @pytest.mark.parametrize("name", case_names("counts"))
 def test_plans_and_search_core_on_host(lib, harness, name):
     """Plan compiler (product code) + per-lane search core (shared with the HIP kernel), run on the host by the

@@ -589,6 +589,46 @@ def test_chain_shape_cases_reach_every_kernel_variant():
         assert kernel in seen, (kernel, sorted(seen))
 
 
+def test_chain_trace_switch_is_read_at_every_launch(capfd):
+    """GSN_CHAIN_TRACE is a LIVE switch for the chain launchers too (csrc/switches.h): in ONE process a chain launch prints its
+    `gsn_chain_launch` line exactly while the variable is set -- unset, set, unset again -- whatever the first launch of the process
+    saw.  One relu stage that gsn_mlp_chain_fwd_hip takes: 130 rows (three 64-row tiles, the last ragged), one direct 36-column
+    block, 128 outputs.  The three outputs are bit-equal and meet the float64 product within the bound of the shape cases above."""
+    import os
+    from gsn_amd.layers import _Stage, _launch_stages, _chain_fits
+    torch.manual_seed(130)
+    dev = "cuda"
+    M, K, n_out = 130, 36, 128
+    x = torch.randn(M, K, device=dev)
+    W = torch.randn(n_out, K, device=dev) / K ** 0.5
+    b = torch.randn(n_out, device=dev)
+    stages = [_Stage(W, b, None, "relu", [(x, None)])]
+    assert _chain_fits(stages)
+    ref = torch.relu(x.double() @ W.double().T + b.double())
+    old = os.environ.pop("GSN_CHAIN_TRACE", None)
+    outs, errs = [], []
+    try:
+        capfd.readouterr()
+        for value in (None, "1", None):
+            if value is None:
+                os.environ.pop("GSN_CHAIN_TRACE", None)
+            else:
+                os.environ["GSN_CHAIN_TRACE"] = value
+            y = _launch_stages(stages, M)
+            torch.cuda.synchronize()
+            outs.append(y.clone())
+            errs.append(capfd.readouterr().err)
+    finally:
+        os.environ.pop("GSN_CHAIN_TRACE", None)
+        if old is not None:
+            os.environ["GSN_CHAIN_TRACE"] = old
+    traced = [any(line.startswith("gsn_chain_launch ") for line in e.splitlines()) for e in errs]
+    assert traced == [False, True, False], errs
+    assert outs[0].shape == (M, n_out)
+    assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
+    assert rel_err(outs[0].double(), ref) < TOL
+
+
 @pytest.mark.parametrize("mix", ["exact", "mixed"])
 def test_fused_scatter_add_with_bf16_exact_inputs(mix):
     """One-hot / small-integer inputs are exact in bf16: the bf16x6 edge stage then skips the plane products that read the
