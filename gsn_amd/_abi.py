@@ -48,6 +48,10 @@ class gsn_count_side(ctypes.Structure):
                 ("edge_clamp", c_int), ("edge_col0", c_int), ("code_status", c_vp)]
 
 
+class gsn_count_keys(ctypes.Structure):
+    _fields_ = [("nkey", c_vp), ("ekeys", c_vp), ("idmask", c_vp)]
+
+
 class gsn_count_call(ctypes.Structure):
     _fields_ = [("plan_host", c_vp), ("plan_dev", c_vp), ("plan_words", c_i64), ("n_graphs", c_i64), ("node_ptr", c_vp), ("edge_ptr", c_vp),
                 ("edge_index", c_vp), ("edge_row_stride", c_i64), ("ids_are_global", c_int), ("max_nodes", c_i64), ("max_edges", c_i64),
@@ -90,6 +94,11 @@ SIGNATURES = {
     "gsn_count_encode_pack16_side_hip": (c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_int, c_i64, c_i64, c_vp, c_vp, c_vp, c_int,
                                                  c_vp, c_i64, c_i64, ctypes.POINTER(gsn_count_side), c_vp]),
     "gsn_count_layer_step_hip": (c_int, [ctypes.POINTER(gsn_count_call), ctypes.POINTER(gsn_layer_pack16_call), c_vp, c_vp]),
+    "gsn_count_encode_keys_side_hip": (c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_int, c_i64, c_i64, c_vp, c_vp, c_vp, c_int,
+                                               c_i64, ctypes.POINTER(gsn_count_side), ctypes.POINTER(gsn_count_keys), c_vp]),
+    "gsn_count_layer_step_keys_hip": (c_int, [ctypes.POINTER(gsn_count_call), ctypes.POINTER(gsn_layer_pack16_call), ctypes.POINTER(gsn_count_keys),
+                                              c_vp, c_i64, c_vp, c_vp]),
+    "gsn_layer_keys_byte_table": (c_int, [c_vp]),
     "gsn_pack16_rows_hip": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
     "gsn_one_hot_pack16_hip": (c_int, [c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
     "gsn_csr_scratch_elems": (c_i64, [c_i64]),

@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "gsn_internal.h"
+#include "layer_rr.h"
 
 namespace gsn {
 
@@ -119,4 +120,32 @@ extern "C" int gsn_count_layer_step_hip(const gsn_count_call *c, const gsn_layer
         return gsn::set_error(GSN_E_HIP, "gsn_count_layer_step_hip: hipEventRecord(event_between)");
     return gsn_layer_fused_fwd_pack16_hip(l->n_nodes, l->n_edges, l->seg_ptr, l->edge, l->x, l->d_x, l->node0, l->node1, l->prepared, l->pack,
                                           l->edge_rows, l->out, stream);
+}
+
+// The same step on code keys (include/gsn_abi.h: gsn_count_layer_step_keys_hip): the counting launch leaves the CSR and the compact keys, layer 0
+// gathers its operand rows from the node dictionary and the byte table through them -- no row pack is written or read
+extern "C" int gsn_count_layer_step_keys_hip(const gsn_count_call *c, const gsn_layer_pack16_call *l, const gsn_count_keys *keys, const uint16_t *node_dict,
+                                             int64_t dict_rows, void *event_between, void *stream) {
+    if (!c || !l || !keys || !c->side) return gsn::set_error(GSN_E_INVALID, "gsn_count_layer_step_keys_hip: null call struct / keys / side");
+    if (!keys->nkey || !keys->ekeys || !keys->idmask || !node_dict) return gsn::set_error(GSN_E_INVALID, "gsn_count_layer_step_keys_hip: null key array / node dictionary");
+    if (!c->side->node_codes || !c->side->edge_codes) return gsn::set_error(GSN_E_INVALID, "gsn_count_layer_step_keys_hip: node and edge codes are both needed");
+    if (!gsn_layer_fused_pack16_supported(l->edge, l->d_x, l->node0, l->node1))
+        return gsn::set_error(GSN_E_UNSUPPORTED, "gsn_count_layer_step_keys_hip: shape outside the packed-row layer kernel");
+    if (!l->seg_ptr || !l->out || !l->prepared || (reinterpret_cast<uintptr_t>(l->prepared) & 15) || l->n_nodes <= 0 || l->n_nodes > (int64_t)2000000000 ||
+        l->n_edges > (int64_t)2000000000)
+        return gsn::set_error(GSN_E_INVALID, "gsn_count_layer_step_keys_hip: null seg_ptr / out / prepared (16-byte aligned), or sizes outside 32-bit row arithmetic");
+    // the layer reads the key arrays in the order of the CSR this launch writes
+    if (l->edge->n_blocks < 3 || l->edge->blocks[0].idx32 != c->side->sorted_target || l->edge->blocks[1].idx32 != c->side->sorted_other ||
+        l->edge->blocks[2].idx32 != c->side->perm || l->seg_ptr != c->side->seg_ptr || l->n_edges != c->side->n_edges || l->n_nodes != c->side->n_nodes)
+        return gsn::set_error(GSN_E_INVALID, "gsn_count_layer_step_keys_hip: the layer's seg_ptr / block indices must be the counting launch's CSR arrays");
+    int rc = gsn_count_encode_keys_side_hip(c->plan_host, c->plan_dev, c->plan_words, c->n_graphs, c->node_ptr, c->edge_ptr, c->edge_index, c->edge_row_stride,
+                                            c->ids_are_global, c->max_nodes, c->max_edges, c->out, c->status, c->n_classes, c->clamp, c->pack_col0, c->side, keys, stream);
+    if (rc != GSN_OK) return rc;
+    if (event_between && hipEventRecord(reinterpret_cast<hipEvent_t>(event_between), reinterpret_cast<hipStream_t>(stream)) != hipSuccess)
+        return gsn::set_error(GSN_E_HIP, "gsn_count_layer_step_keys_hip: hipEventRecord(event_between)");
+    const gsn::RpKeys k{keys->ekeys, keys->nkey, keys->idmask, node_dict, dict_rows, c->side->edge_col0};
+    rc = gsn::rp_forward(l->n_nodes, l->n_edges, l->seg_ptr, l->edge, l->x, l->d_x, l->node0, l->node1, l->prepared, nullptr, l->edge_rows, l->out,
+                         reinterpret_cast<hipStream_t>(stream), &k);
+    if (rc == 1) return gsn::set_error(GSN_E_UNSUPPORTED, "gsn_count_layer_step_keys_hip: key arrays beyond 2 GiB (32-bit buffer offsets)");
+    return rc;
 }

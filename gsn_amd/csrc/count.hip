@@ -27,6 +27,8 @@ constexpr int GSN_ENC_MAX_COLS = 64;
 // What gsn_count_encode_pack16_side_hip adds to a counting launch (r06): the target-sorted CSR of the batch's columns, the node pack from
 // integer node codes, the edge codes' one-hot columns of the edge pack.  They are made by SIDE WORKGROUPS of the same launch (side_block
 // below), every (SIDE_EVERY + 1)-th workgroup of the grid; the counting workgroups run count_body exactly as without them.
+// gsn_count_encode_keys_side_hip: the same launch leaving COMPACT outputs in place of the packs -- a key byte per vertex and a key word per sorted
+// column from the side workgroups, a 16-bit mask of the identifier classes per column from the counting workgroups (include/gsn_abi.h: gsn_count_keys).
 struct SideArgs {
     int32_t *csr_seg, *csr_perm, *csr_tgt, *csr_oth;   // csr_seg == null: no CSR
     int64_t tot_nodes, tot_edges;
@@ -39,6 +41,11 @@ struct SideArgs {
     int ncode_cols, ncode_clamp, ecode_cols, ecode_clamp, ecode_col0;
     unsigned ncode_ptr_w[2], ecode_ptr_w[2];    // first pack column of every code column's classes, one BYTE per column + the end (prefix sums; the
                                                 // edge codes' start at ecode_col0) -- as words: byte-sized kernel arguments are vector loads on gfx9
+    // compact outputs (gsn_count_encode_keys_side_hip): what layer 0 reads in place of the two packs
+    uint8_t *nkey;             // [tot_nodes] or null: row of the vertex in the node dictionary = the mixed-radix number of its code digits, column 0
+                               // most significant; without clamp every column has one digit more, "none" (a code outside its classes: zero segment)
+    uint32_t *ekeys;           // [tot_edges] or null, target-sorted order: nkey[target] | nkey[other] << 8 | edge-code class mask << 16
+    unsigned nkey_radix_w;     // digits per node code column, one byte per column
 };
 #ifndef GSN_SIDE_EVERY
 #define GSN_SIDE_EVERY 4
@@ -91,6 +98,8 @@ struct CountArgs {
     int n_items;               // counting work items of the launch (graphs, or pairs of graphs)
     int lds_bytes;             // dynamic LDS of the launch (a side workgroup sorts as many graphs at a time as fit there)
     unsigned cyc_len;          // cycle instantiation: the cycle length of output column c in byte c (count_core.h: cycle_plan_lengths)
+    uint16_t *idmask;          // [rows_total] or null: bit enc16_col0 + (first column of c's classes) + class of every column c of a row -- the hot pack
+                               // columns of the row as a bit mask, from the staged class indices (phase 4')
     SideArgs side;
 };
 
@@ -161,9 +170,38 @@ __device__ __forceinline__ void side_block(const CountArgs &a, unsigned char *sm
                     if (sd->csr_oth) sd->csr_oth[e0 + e] = (int32_t)n0;
                 }
             }
+            // the compact outputs of such a graph, by the plain loops as well: every column names the graph's first vertex at both ends
+            auto key_of = [&](int64_t v) {
+                const unsigned w0 = sd->ncode_ptr_w[0], w1 = sd->ncode_ptr_w[1];
+                unsigned key = 0;
+                for (int c = 0; c < sd->ncode_cols; ++c) {
+                    int64_t x = sd->ncode[v * sd->ncode_cols + c];
+                    const int ncls = side_byte(w0, w1, c + 1) - side_byte(w0, w1, c);
+                    if (sd->ncode_clamp) x = x < 0 ? 0 : (x >= ncls ? ncls - 1 : x);
+                    key = key * ((sd->nkey_radix_w >> (8 * c)) & 0xffu) + ((x >= 0 && x < ncls) ? (unsigned)x : (unsigned)ncls);
+                }
+                return key;
+            };
+            if (do_np && sd->nkey) for (int64_t v = tid; v < n64; v += T) sd->nkey[n0 + v] = (uint8_t)key_of(n0 + v);
+            if (do_csr && sd->ekeys && n64 > 0) {
+                const unsigned w0 = sd->ecode_ptr_w[0], w1 = sd->ecode_ptr_w[1];
+                const unsigned k0 = do_np ? key_of(n0) : 0u;
+                for (int64_t r = tid; r < E64; r += T) {
+                    unsigned hot = 0;
+                    for (int c = 0; do_ec && c < sd->ecode_cols; ++c) {
+                        int64_t x = sd->ecode[(e0 + r) * sd->ecode_cols + c];
+                        const int lo = side_byte(w0, w1, c), ncls = side_byte(w0, w1, c + 1) - lo;
+                        if (sd->ecode_clamp) x = x < 0 ? 0 : (x >= ncls ? ncls - 1 : x);
+                        if (x >= 0 && x < ncls) hot |= 1u << (lo - sd->ecode_col0 + (int)x);
+                        else if (sd->code_status && !sd->epack) atomicOr(sd->code_status, 1);
+                    }
+                    sd->ekeys[e0 + r] = k0 | (k0 << 8) | (hot << 16);
+                }
+            }
             if (do_np) {
                 const unsigned w0 = sd->ncode_ptr_w[0], w1 = sd->ncode_ptr_w[1];
                 for (int64_t i = tid; i < 4 * n64; i += T) {
+                    if (!sd->npack && (i & 3)) continue;     // (no pack: the pass only raises the code status)
                     const int64_t v = i >> 2;
                     const int q = (int)(i & 3);
                     unsigned m = 0x80000000u;
@@ -176,10 +214,10 @@ __device__ __forceinline__ void side_block(const CountArgs &a, unsigned char *sm
                     }
                     const unsigned hot = m >> (8 * q);
                     auto word = [&](int kk) { return ((hot >> kk) & 1u ? 0x3c00u : 0u) | ((hot >> (kk + 1)) & 1u ? 0x3c000000u : 0u); };
-                    *reinterpret_cast<u4v *>(sd->npack + (n0 + v) * 32 + 8 * q) = u4v{word(0), word(2), word(4), word(6)};
+                    if (sd->npack) *reinterpret_cast<u4v *>(sd->npack + (n0 + v) * 32 + 8 * q) = u4v{word(0), word(2), word(4), word(6)};
                 }
             }
-            if (do_ec) {
+            if (do_ec && sd->epack) {
                 const unsigned w0 = sd->ecode_ptr_w[0], w1 = sd->ecode_ptr_w[1];
                 const int q0 = sd->ecode_col0 >> 2;
                 for (int64_t i = tid; i < E64 * (4 - q0); i += T) {
@@ -205,7 +243,7 @@ __device__ __forceinline__ void side_block(const CountArgs &a, unsigned char *sm
         const int n = (int)n64, E = (int)E64;
         int *cstart = reinterpret_cast<int *>(smem);
         int *ccur = cstart + (n + 1);
-        unsigned *nmask = reinterpret_cast<unsigned *>(ccur + (n + 1));
+        unsigned *nmask = reinterpret_cast<unsigned *>(ccur + (n + 1));   // hot pack columns of the vertex as a bit mask; with SideArgs::nkey its dictionary row instead
         uint16_t *tloc = reinterpret_cast<uint16_t *>(nmask + n);
         uint16_t *oloc = tloc + E;
         uint16_t *pl = oloc + E;
@@ -235,6 +273,7 @@ __device__ __forceinline__ void side_block(const CountArgs &a, unsigned char *sm
         if (do_np) {
             const unsigned w0 = sd->ncode_ptr_w[0], w1 = sd->ncode_ptr_w[1];
             const int nc = sd->ncode_cols;
+            const bool as_key = sd->nkey != nullptr;
             for (int v0 = 0; v0 < n; v0 += 4 * T) {
                 if (nc == 1) {
                     int64_t xq[4];
@@ -247,20 +286,22 @@ __device__ __forceinline__ void side_block(const CountArgs &a, unsigned char *sm
                         int64_t x = xq[j];
                         if (sd->ncode_clamp) x = x < 0 ? 0 : (x >= ncls ? ncls - 1 : x);
                         const bool ok = x >= 0 && x < ncls;
-                        if (v < n) { nmask[v] = 0x80000000u | (ok ? 1u << (int)x : 0u); bad_code = bad_code || !ok; }
+                        if (v < n) { nmask[v] = as_key ? (unsigned)(ok ? (int)x : ncls) : 0x80000000u | (ok ? 1u << (int)x : 0u); bad_code = bad_code || !ok; }
                     }
                 } else {
                     for (int j = 0; j < 4; ++j) {
                         const int v = v0 + j * T + tid;
                         if (v >= n) break;
-                        unsigned m = 0x80000000u;
+                        unsigned m = 0x80000000u, key = 0;
                         for (int c = 0; c < nc; ++c) {
                             int64_t x = sd->ncode[(n0 + v) * nc + c];
                             const int lo = side_byte(w0, w1, c), ncls = side_byte(w0, w1, c + 1) - lo;
                             if (sd->ncode_clamp) x = x < 0 ? 0 : (x >= ncls ? ncls - 1 : x);
-                            if (x >= 0 && x < ncls) m |= 1u << (lo + (int)x); else bad_code = true;
+                            const bool ok = x >= 0 && x < ncls;
+                            if (ok) m |= 1u << (lo + (int)x); else bad_code = true;
+                            key = key * ((sd->nkey_radix_w >> (8 * c)) & 0xffu) + (ok ? (unsigned)x : (unsigned)ncls);
                         }
-                        nmask[v] = m;
+                        nmask[v] = as_key ? key : m;
                     }
                 }
             }
@@ -340,16 +381,19 @@ __device__ __forceinline__ void side_block(const CountArgs &a, unsigned char *sm
                 sd->csr_perm[e0 + i] = (int32_t)(e0 + le);
                 if (sd->csr_tgt) sd->csr_tgt[e0 + i] = (int32_t)(n0 + tloc[le]);
                 if (sd->csr_oth) sd->csr_oth[e0 + i] = (int32_t)(n0 + oloc[le]);
+                if (sd->ekeys)
+                    sd->ekeys[e0 + i] = (do_np ? nmask[tloc[le]] | (nmask[oloc[le]] << 8) : 0u) | (do_ec ? (unsigned)ecls[le] << 16 : 0u);
             }
         }
-        if (do_np)
+        if (do_np && sd->nkey) for (int v = tid; v < n; v += T) sd->nkey[n0 + v] = (uint8_t)nmask[v];
+        if (do_np && sd->npack)
             for (int i = tid; i < 4 * n; i += T) {
                 const int v = i >> 2, q = i & 3;
                 const unsigned hot = nmask[v] >> (8 * q);
                 auto word = [&](int kk) { return ((hot >> kk) & 1u ? 0x3c00u : 0u) | ((hot >> (kk + 1)) & 1u ? 0x3c000000u : 0u); };
                 *reinterpret_cast<u4v *>(sd->npack + (n0 + v) * 32 + 8 * q) = u4v{word(0), word(2), word(4), word(6)};
             }
-        if (do_ec) {
+        if (do_ec && sd->epack) {
             const int q0 = sd->ecode_col0 >> 2, nq = 4 - q0;      // the 4-column groups from ecode_col0 to the end of the row
             for (int i = tid; i < E * nq; i += T) {
                 const int r = nq == 1 ? i : i / nq;
@@ -442,6 +486,7 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
             if (a.out) for (int c = 0; c < 4; ++c) a.out[(row0 + r) * 4 + c] = 0;
             if (z32) for (int k = 0; k < a.enc_width; ++k) a.enc_out[(row0 + r) * a.enc_width + k] = 0.f;
             if (z16) for (int k = 0; k < a.enc_width; ++k) a.enc16[(row0 + r) * a.enc16_stride + a.enc16_col0 + k] = 0;
+            if (!DIR && args_late()->idmask) args_late()->idmask[row0 + r] = 0;
         }
     };
     if (ng > 1 && (n64 > a.n_cap || E64 > a.e_cap || n64 > W * 64)) return 1;
@@ -453,6 +498,7 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
             if (a.out) for (int64_t i = tid; i < rows64 * n_cols; i += T) a.out[row0 * n_cols + i] = 0;
             if (a.enc_out && !a.enc_no32) for (int64_t i = tid; i < rows64 * a.enc_width; i += T) a.enc_out[row0 * a.enc_width + i] = 0.f;
             if (a.enc16) for (int64_t i = tid; i < rows64 * a.enc_width; i += T) a.enc16[(row0 + i / a.enc_width) * a.enc16_stride + a.enc16_col0 + i % a.enc_width] = 0;
+            if (!DIR && args_late()->idmask) for (int64_t i = tid; i < rows64; i += T) args_late()->idmask[row0 + i] = 0;
             }
             if (tid == 0) atomicMax(&a.status[g], (int)GSN_ST_TOO_LARGE);
         }
@@ -751,6 +797,7 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
             if (a.out) for (int i = tid; i < rows * n_cols; i += T) a.out[row0 * n_cols + i] = 0;
             if (a.enc_out && !a.enc_no32) for (int i = tid; i < rows * a.enc_width; i += T) a.enc_out[row0 * a.enc_width + i] = 0.f;
             if (a.enc16 && a.enc_no32) for (int i = tid; i < rows * a.enc_width; i += T) a.enc16[(row0 + i / a.enc_width) * a.enc16_stride + a.enc16_col0 + i % a.enc_width] = 0;
+            if (!DIR && args_late()->idmask) for (int i = tid; i < rows; i += T) args_late()->idmask[row0 + i] = 0;
             }
             if (tid == 0) atomicMax(&a.status[g], misc[2]);
         }
@@ -987,9 +1034,13 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
                         p2[k >> 2] = o;
                     }
                 }
+                // the row's hot pack columns as a bit mask (2 bytes instead of the 8 enc_width / 4 above)
+                if (!DIR && args_late()->idmask)
+                    args_late()->idmask[row0 + r] = (uint16_t)(((h0 < 0 ? 0u : 1u << h0) | (h1 < 0 ? 0u : 1u << h1) | (h2 < 0 ? 0u : 1u << h2) | (h3 < 0 ? 0u : 1u << h3)) << a.enc16_col0);
             }
-        } else
+        } else {
         // column c owns floats enc[2c] .. enc[2c] + enc[2c + 1] of a row; the table is short: a linear scan per float
+        if (!a.enc_no32 || a.enc16)
         for (int i = tid; i < total; i += T) {
             const int r = i / a.enc_width;              // (exact: the reciprocal multiply was off by one for wide encodings, e.g. width 1000 from row 6100 on; this loop is bound by its stores)
             const int j = i - r * a.enc_width;
@@ -1000,6 +1051,16 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
             const bool hot = k < enc[2 * c + 1] && cls == k;
             if (!a.enc_no32) dst[i] = hot ? 1.f : 0.f;
             if (a.enc16) a.enc16[(row0 + r) * a.enc16_stride + a.enc16_col0 + j] = hot ? (uint16_t)0x3c00 : (uint16_t)0;
+        }
+        if (!DIR && args_late()->idmask)                                   // the same rows as bit masks, a row per thread
+            for (int r = tid; r < rows; r += T) {
+                unsigned m = 0;
+                for (int c = 0; c < n_cols; ++c) {
+                    const int cls = a_enc_from_counts ? cls_from_count(out_lds[r * n_cols + c], c) : (int)est[r * n_cols + c];
+                    if (cls < enc[2 * c + 1]) m |= 1u << (enc[2 * c] + cls);
+                }
+                args_late()->idmask[row0 + r] = (uint16_t)(m << a.enc16_col0);
+            }
         }
     }
     COUNT_T(6);
@@ -1201,7 +1262,7 @@ static int count_launch(const uint32_t *plan_host, const uint32_t *plan_dev, int
                         int64_t edge_row_stride, int ids_are_global, const int32_t *graph_ids, int64_t n_items,
                         int64_t max_nodes, int64_t max_edges, int64_t *out, int32_t *status, const int32_t *n_classes,
                         int enc_clamp, float *enc_out, void *stream, uint16_t *enc16 = nullptr, int64_t enc16_stride = 0, int64_t enc16_col0 = 0, int enc_no32 = 0,
-                        const gsn_count_side *side = nullptr) {
+                        const gsn_count_side *side = nullptr, const gsn_count_keys *keys = nullptr) {
     if (!plan_host || !plan_dev || plan_words < PLAN_HEADER_WORDS || plan_host[0] != PLAN_MAGIC)
         return set_error(GSN_E_INVALID, "gsn_count_hip: not a plan table (build it with gsn_count_plan_build)");
     if (!node_ptr || !edge_ptr || (!out && !enc_out) || !status) return set_error(GSN_E_INVALID, "gsn_count_hip: null pointer argument");
@@ -1255,20 +1316,29 @@ static int count_launch(const uint32_t *plan_host, const uint32_t *plan_dev, int
         }
         a.side.csr_row = side->csr_row ? 1 : 0; a.side.tot_nodes = side->n_nodes; a.side.tot_edges = side->n_edges;
         if (side->node_codes) {
-            if (!side->node_pack || (reinterpret_cast<uintptr_t>(side->node_pack) & 15) || side->node_code_cols < 1 || side->node_code_cols > 4)
+            const bool nk = keys && keys->nkey;          // (the node keys may stand in for the node pack)
+            if ((side->node_pack ? (reinterpret_cast<uintptr_t>(side->node_pack) & 15) != 0 : !nk) || side->node_code_cols < 1 || side->node_code_cols > 4)
                 return set_error(GSN_E_INVALID, "gsn_count_encode_pack16_side_hip: node pack (16-byte aligned) and 1..4 node code columns");
             int o = 0;
+            int64_t dict_rows = 1;
             for (int c = 0; c < side->node_code_cols; ++c) {
                 if (side->node_n_classes[c] < 1) return set_error(GSN_E_INVALID, "gsn_count_encode_pack16_side_hip: node_n_classes[%d] < 1", c);
                 a.side.ncode_ptr_w[c >> 2] |= (unsigned)o << (8 * (c & 3)); o += side->node_n_classes[c];
                 if (o > 28) return set_error(GSN_E_INVALID, "gsn_count_encode_pack16_side_hip: more than 28 encoded node columns");
+                const int radix = side->node_n_classes[c] + (side->node_clamp ? 0 : 1);
+                a.side.nkey_radix_w |= (unsigned)radix << (8 * c); dict_rows *= radix;
             }
+            if (nk && dict_rows > 256)
+                return set_error(GSN_E_UNSUPPORTED, "gsn_count_encode_keys_side_hip: a node dictionary of %lld rows (one byte per key: <= 256)", (long long)dict_rows);
+            if (nk && side->node_pack)
+                return set_error(GSN_E_INVALID, "gsn_count_encode_keys_side_hip: node keys stand in for the node pack (side->node_pack must be NULL)");
+            a.side.nkey = nk ? keys->nkey : nullptr;
             a.side.ncode_ptr_w[side->node_code_cols >> 2] |= (unsigned)o << (8 * (side->node_code_cols & 3));
             a.side_mask |= 2;
             a.side.ncode = side->node_codes; a.side.npack = side->node_pack; a.side.ncode_cols = side->node_code_cols; a.side.ncode_clamp = side->node_clamp ? 1 : 0;
         }
         if (side->edge_codes) {
-            if (!enc16 || enc16_stride != 16 || (reinterpret_cast<uintptr_t>(enc16) & 15) || side->edge_code_cols < 1 || side->edge_code_cols > 4)
+            if ((enc16 ? (enc16_stride != 16 || (reinterpret_cast<uintptr_t>(enc16) & 15)) : !(keys && keys->ekeys)) || side->edge_code_cols < 1 || side->edge_code_cols > 4)
                 return set_error(GSN_E_INVALID, "gsn_count_encode_pack16_side_hip: edge codes need a 16-column, 16-byte-aligned edge pack and 1..4 code columns");
             if (side->edge_col0 < 0 || (side->edge_col0 & 3) || side->edge_col0 < enc16_col0 + enc_width)
                 return set_error(GSN_E_INVALID, "gsn_count_encode_pack16_side_hip: edge_col0 %d must be a multiple of 4 behind the identifier columns (%lld .. %lld)",
@@ -1286,6 +1356,18 @@ static int count_launch(const uint32_t *plan_host, const uint32_t *plan_dev, int
             a.side.ecode_col0 = side->edge_col0;
         }
         a.side.code_status = side->code_status;
+        if (keys && keys->ekeys) {
+            if (!(a.side_mask & 1) || !side->sorted_target || !side->sorted_other)
+                return set_error(GSN_E_INVALID, "gsn_count_encode_keys_side_hip: the edge keys are written with the CSR arrays (seg_ptr, perm, sorted_target, sorted_other)");
+            a.side.ekeys = keys->ekeys;
+        }
+    }
+    if (keys && keys->idmask) {
+        if (directed) return set_error(GSN_E_UNSUPPORTED, "gsn_count_encode_keys_side_hip: directed plans (their instantiations carry no identifier masks)");
+        if (!enc_out || enc16_col0 < 0 || enc16_col0 + enc_width > 16)
+            return set_error(GSN_E_INVALID, "gsn_count_encode_keys_side_hip: the identifier masks hold pack columns %lld .. %lld (<= 16) of an encoded launch", (long long)enc16_col0,
+                             (long long)(enc16_col0 + enc_width));
+        a.idmask = keys->idmask;
     }
 
     const int W = max_nodes <= 64 ? 1 : (max_nodes <= 128 ? 2 : (max_nodes <= 256 ? 4 : (max_nodes <= 512 ? 8 : 12)));
@@ -1404,7 +1486,7 @@ static int count_launch(const uint32_t *plan_host, const uint32_t *plan_dev, int
     // every cell writes its floats itself
     a.enc_stage = 0; a.off_encst = o; a.enc_from_counts = 0;
     a.enc16 = enc16; a.enc16_stride = (int)enc16_stride; a.enc16_col0 = (int)enc16_col0;
-    a.enc_no32 = (enc16 && enc_no32) ? 1 : 0;
+    a.enc_no32 = ((enc16 || a.idmask) && enc_no32) ? 1 : 0;
     if (enc_out && a.split == 1 && enc_bytes && rows_cap_u * enc_width < (int64_t)1 << 24 && o + rows_cap_u * a.n_cols <= 150 * 1024) {
         a.enc_stage = 1;
         const bool bytes_forced = sw_present(SW_COUNT_ENC_BYTES);     // (A/B: keep the byte array beside staged counts)
@@ -1424,6 +1506,8 @@ static int count_launch(const uint32_t *plan_host, const uint32_t *plan_dev, int
     if (o > 160 * 1024) return set_error(GSN_E_UNSUPPORTED, "graph too large for LDS (%d B needed)", o);
     // (a pair of one-word graphs of <= 128 columns each: a few KiB, class indices in a byte -- always staged)
     if (cyc && !(a.enc_stage && a.split == 1)) return set_error(GSN_E_UNSUPPORTED, "gsn_count_hip: cycle launch without staged class indices (%d B of LDS)", o);
+    if (a.idmask && !a.enc_stage)
+        return set_error(GSN_E_UNSUPPORTED, "gsn_count_encode_keys_side_hip: the identifier masks are written from the staged class indices (one workgroup per graph, n_classes <= 255)");
     if (enc16 && !a.enc_stage)
         return set_error(GSN_E_UNSUPPORTED, "gsn_count_encode_pack16_hip: the fp16 rows are written from the staged class indices (one workgroup per graph, "
                                             "n_classes <= 255); pack the fp32 rows with gsn_pack16_rows_hip instead");
@@ -1505,4 +1589,16 @@ extern "C" int gsn_count_encode_pack16_side_hip(const uint32_t *plan_host, const
         return set_error(GSN_E_INVALID, "gsn_count_encode_pack16_side_hip: columns %lld .. %lld outside a pack row of %lld", (long long)pack_col0, (long long)(pack_col0 + w), (long long)pack_stride);
     return count_launch(plan_host, plan_dev, plan_words, n_graphs, node_ptr, edge_ptr, edge_index, edge_row_stride, ids_are_global, nullptr, n_graphs,
                         max_nodes, max_edges, out, status, n_classes, clamp, reinterpret_cast<float *>(pack), stream, pack, pack_stride, pack_col0, 1, side);
+}
+
+extern "C" int gsn_count_encode_keys_side_hip(const uint32_t *plan_host, const uint32_t *plan_dev, int64_t plan_words, int64_t n_graphs,
+                                              const int64_t *node_ptr, const int64_t *edge_ptr, const int64_t *edge_index,
+                                              int64_t edge_row_stride, int ids_are_global, int64_t max_nodes, int64_t max_edges, int64_t *out,
+                                              int32_t *status, const int32_t *n_classes, int clamp, int64_t pack_col0, const gsn_count_side *side,
+                                              const gsn_count_keys *keys, void *stream) {
+    if (!side || !keys || !keys->idmask) return set_error(GSN_E_INVALID, "gsn_count_encode_keys_side_hip: side / keys / keys->idmask is null");
+    if (!out) return set_error(GSN_E_INVALID, "gsn_count_encode_keys_side_hip: the int64 counts are always written (out is null)");
+    // (no fp32 rows and no pack: the identifier masks are the only form of the encoded rows; enc_out is a placeholder that is never written)
+    return count_launch(plan_host, plan_dev, plan_words, n_graphs, node_ptr, edge_ptr, edge_index, edge_row_stride, ids_are_global, nullptr, n_graphs,
+                        max_nodes, max_edges, out, status, n_classes, clamp, reinterpret_cast<float *>(keys->idmask), stream, nullptr, 16, pack_col0, 1, side, keys);
 }

@@ -48,23 +48,43 @@ struct RpArgs {
     const unsigned *prep;
     int n_ranges;
     int n_split;                       // nodes of the older half of the waves (0: equal ranges)
+    // KEYS variant (gsn_count_layer_step_keys_hip): node16 is the node DICTIONARY (<= 256 rows), edge16 the identifier masks uint16 [n_edges] in
+    // column order (read through role_idx[2] = perm), role_idx[0 / 1] are not read
+    const uint32_t *ekeys;             // per sorted edge row: dictionary row of x_i | that of x_j << 8 | edge-code class mask << 16
+    const uint8_t *nkey;               // per node: its dictionary row
+    int edge_col0;                     // first pack column of the edge-code classes
 };
 
-struct RpIdx { int r[3]; int pt, pt1; };
+// KEYS: r[0] = the edge key word, r[2] = perm (r[1] unused); nk = the dictionary row of node m0 + li
+struct RpIdx { int r[3]; int pt, pt1; int nk; };
 
+template <bool KEYS>
 __device__ __forceinline__ void rp_idx_load(const RpArgs &a, const RrDesc &d, int li, RpIdx &ix) {
     const int ne = d.ne();
     if (d.valid() && ne > 0) {
         const int e = d.e0 + (li < ne ? li : ne - 1);
+        if constexpr (KEYS) {
+            ix.r[0] = (int)a.ekeys[e];
+            ix.r[2] = a.role_idx[2][e];
+        } else {
 #pragma unroll
-        for (int q = 0; q < 3; ++q) ix.r[q] = a.role_idx[q][e];
+            for (int q = 0; q < 3; ++q) ix.r[q] = a.role_idx[q][e];
+        }
     }
     if (d.valid()) {
         int t = d.m0 + li;
         t = t < a.n_nodes ? t : a.n_nodes - 1;          // (lanes past nn are masked when used)
         ix.pt = a.seg_ptr[t];
         ix.pt1 = a.seg_ptr[t + 1];
+        if constexpr (KEYS) ix.nk = (int)a.nkey[t];
     }
+}
+
+// KEYS: byte b -> the eight fp16 values 0 / 1.0 of its bits (bit j = value j): half an edge pack row from one byte of its hot-column mask.
+// 256 entries of 16 bytes in LDS behind the weights; word q of an entry holds values 2 q (low half) and 2 q + 1.
+constexpr int RP_BYTE_TAB_BYTES = 256 * 16;
+__device__ __host__ __forceinline__ unsigned rp_byte_tab_word(unsigned b, int q) {
+    return ((b >> (2 * q)) & 1u ? 0x3c00u : 0u) | ((b >> (2 * q + 1)) & 1u ? 0x3c000000u : 0u);
 }
 
 #define RP_LOAD(RS, VOFF, IMM) __builtin_bit_cast(rr_u4, __builtin_amdgcn_raw_buffer_load_b128(RS, (int)((VOFF) + (IMM)), 0, 0))
@@ -110,7 +130,7 @@ __device__ __forceinline__ unsigned rp_pk_max_u16(unsigned a, unsigned b) { unsi
 #define RP_S1E 1           // node stage 1: the first pair's output rows leave under the second pair's products
 #endif
 
-template <int WB, int NKX, bool PROF>
+template <int WB, int NKX, bool PROF, bool KEYS = false>
 __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_NW / 4, RR_NW / 4))) void layer_fused_kernel_rp(RpArgs a, unsigned long long *prof) {
     auto clk = [&]() -> unsigned {
         if (!PROF) return 0u;
@@ -141,6 +161,10 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
         const float *tsrc = reinterpret_cast<const float *>(a.prep + RR_HDR + SH::F_ALL * 256);
         float *tdst = reinterpret_cast<float *>(smem + SH::F_LDS * 1024);
         for (int i = tid; i < SH::TAB_WORDS; i += 64 * RR_NW) tdst[i] = tsrc[i];
+        if constexpr (KEYS) {
+            rr_u4 *bt = reinterpret_cast<rr_u4 *>(smem + SH::LDS_BYTES);
+            for (int b = tid; b < 256; b += 64 * RR_NW) bt[b] = rr_u4{rp_byte_tab_word(b, 0), rp_byte_tab_word(b, 1), rp_byte_tab_word(b, 2), rp_byte_tab_word(b, 3)};
+        }
     }
     __syncthreads();
     // (wave-uniform header words: scalar registers -- read as they stand they are ONE vector load of four, kept in vector registers for the
@@ -158,6 +182,7 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
     const __amdgpu_buffer_rsrc_t rs_n = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(a.node16), 0, (int)a.node_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_e = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(a.edge16), 0, (int)a.edge_bytes, 0x00020000);
     const int esh = a.edge_shift;
+    const int ec0 = a.edge_col0;
     // where the in-degree goes: k-slots d_x (high part) and d_x + 1 (residual) of the node pack's row = one word of one chunk, one lane half
     const int deg_c = a.d_x >> 4, deg_h = (a.d_x >> 3) & 1, deg_w = (a.d_x >> 1) & 3;
 
@@ -201,19 +226,32 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
 #pragma unroll
     for (int q = 0; q < 3; ++q) { ixc.r[q] = 0; ixn.r[q] = 0; }
     ixc.pt = ixc.pt1 = ixn.pt = ixn.pt1 = 0;
-    rp_idx_load(a, cur, li0, ixc);
+    ixc.nk = ixn.nk = 0;
+    rp_idx_load<KEYS>(a, cur, li0, ixc);
     RrDesc nxt = rr_iter_next(it, lane0);
-    rp_idx_load(a, nxt, li0, ixn);
+    rp_idx_load<KEYS>(a, nxt, li0, ixn);
     rr_u4 g[RR_NKE];                                   // the gathered rows of the CURRENT block (in flight at the top of the loop)
     auto gather = [&](const int (&r)[3], int lh) {
+        if constexpr (KEYS) {
+            // the same four node loads, their rows named by the key word's two bytes (rows of the dictionary: L1 hits); of the edge-level
+            // row only its identifier mask, 2 bytes through perm -- the row itself is looked up at the block's top
+            const unsigned k = (unsigned)r[0];
+            const unsigned vt = ((k & 0xffu) << 6) | ((unsigned)lh << 4), vs = (((k >> 8) & 0xffu) << 6) | ((unsigned)lh << 4);
+            g[0] = RP_LOAD(rs_n, vt, 0); g[1] = RP_LOAD(rs_n, vt, 32);
+            g[2] = RP_LOAD(rs_n, vs, 0); g[3] = RP_LOAD(rs_n, vs, 32);
+            g[4][0] = (unsigned)__builtin_amdgcn_raw_buffer_load_b16(rs_e, (int)((unsigned)r[2] << 1), 0, 0);
+        } else {
         const unsigned vt = ((unsigned)r[0] << 6) | ((unsigned)lh << 4), vs = ((unsigned)r[1] << 6) | ((unsigned)lh << 4);
         const unsigned ve = ((unsigned)r[2] << esh) | ((unsigned)lh << 4);
         g[0] = RP_LOAD(rs_n, vt, 0); g[1] = RP_LOAD(rs_n, vt, 32);
         g[2] = RP_LOAD(rs_n, vs, 0); g[3] = RP_LOAD(rs_n, vs, 32);
         g[4] = RP_LOAD(rs_e, ve, 0);
+        }
     };
     gather(ixc.r, lh0);
     int pt = ixc.pt, pt1 = ixc.pt1;
+    int nk = ixc.nk;                                   // KEYS: dictionary row of node m0 + li of the current tile
+    unsigned kc = (unsigned)ixc.r[0];                  // KEYS: the key word of the current block's row (its edge-code classes are read at the block's top)
 
     const unsigned t_start = clk();
     while (cur.valid()) {
@@ -230,7 +268,7 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
         // tile's last block, in front of its last epilogue (rows this tile's edge blocks have just gathered: cache hits)
         rr_u4 X[NKX];                                  // (requested with EVERY block -- an assignment under `last` makes a loop-carried value of it)
         auto load_x = [&]() {
-            const unsigned vx = ((unsigned)(m0 + (li < nn ? li : nn - 1)) << 6) | ((unsigned)lh << 4);
+            const unsigned vx = ((unsigned)(KEYS ? nk : m0 + (li < nn ? li : nn - 1)) << 6) | ((unsigned)lh << 4);
 #pragma unroll
             for (int c = 0; c < NKX; ++c) X[c] = RP_LOAD(rs_n, vx, 32 * c);
         };
@@ -258,15 +296,23 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
             rr_u4 Ah[RR_NKE];
 #pragma unroll
             for (int c = 0; c < RR_NKE; ++c) Ah[c] = g[c];
+            if constexpr (KEYS) {
+                // the edge-level fragment: lane (e, h) takes byte h of the row's hot-column mask (identifier classes | edge-code classes behind
+                // them) and reads its eight fp16 values from the byte table -- used ~16 products later (chunk 4 of the first pair)
+                const unsigned m16 = g[RR_NKE - 1][0] | ((kc >> 16) << ec0);
+                const unsigned byte = (m16 >> (8 * lh)) & 0xffu;
+                Ah[RR_NKE - 1] = *reinterpret_cast<rr_ldsp>(ldsb[2] - 16u * (unsigned)lane + 16u * byte + (unsigned)(SH::LDS_BYTES - 0x20000));
+            }
             last = cur.last() != 0;
             // the next block's gathers: inside a tile right here (they fly under this block's edge stage); across a tile boundary they
             // would hold 20 registers through both node stages -- issued in node stage 1, once the hidden rows' registers are free
             if (!last) gather(ixn.r, lh);
 #pragma unroll
             for (int q = 0; q < 3; ++q) rnext[q] = ixn.r[q];
-            const int npt = ixn.pt, npt1 = ixn.pt1;
+            kc = (unsigned)ixn.r[0];
+            const int npt = ixn.pt, npt1 = ixn.pt1, nnk = ixn.nk;
             const RrDesc nn2 = rr_iter_next(it, lane);
-            rp_idx_load(a, nn2, li, ixn);
+            rp_idx_load<KEYS>(a, nn2, li, ixn);
             const unsigned t1 = clk();
             unsigned t2 = t1;
             // =========================================================================================================================
@@ -347,7 +393,7 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
             const unsigned t3 = clk();
             if (PROF) { pc[0] += t1 - t0; pc[1] += t2 - t1; pc[2] += t3 - t2; pc[6] += 1; }
             cur = nxt; nxt = nn2;
-            pt = npt; pt1 = npt1;
+            pt = npt; pt1 = npt1; nk = nnk;
         } while (!last);
         // (the x rows exist HERE: left alone the compiler sinks their loads to their use, where nothing hides them)
 #pragma unroll
@@ -777,20 +823,36 @@ int rp_supported(const gsn_chain_stage *edge, int64_t d_x, const gsn_chain_stage
 
 int rp_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const gsn_chain_stage *edge, const float *x, int64_t d_x,
                const gsn_chain_stage *node0, const gsn_chain_stage *node1, const void *prepared, const gsn_pack16 *pack, int64_t edge_rows,
-               float *out, hipStream_t st) {
+               float *out, hipStream_t st, const RpKeys *keys) {
     using SH = RrShape<4, 2>;
     int cols = 0;
     if (!rp_blocks(edge, d_x, x, &cols)) return set_error(GSN_E_INVALID, "gsn_layer_fused_fwd_pack16_hip: the edge stage is not cat(x[i], x[j], edge-level blocks through one index)");
+    if (keys) {
+        if (!keys->ekeys || !keys->nkey || !keys->idmask || !keys->node_dict || (reinterpret_cast<uintptr_t>(keys->node_dict) & 15) || (reinterpret_cast<uintptr_t>(keys->idmask) & 1))
+            return set_error(GSN_E_INVALID, "gsn_count_layer_step_keys_hip: null / misaligned key arrays or node dictionary");
+        if (keys->dict_rows < 1 || keys->dict_rows > 256 || cols < 1 || keys->edge_col0 < 0 || keys->edge_col0 > 16 || edge_rows != n_edges)
+            return set_error(GSN_E_INVALID, "gsn_count_layer_step_keys_hip: node dictionary of %lld rows (1 .. 256), %d edge-level columns (>= 1), edge codes at column %d, %lld edge rows",
+                             (long long)keys->dict_rows, cols, keys->edge_col0, (long long)edge_rows);
+        if (edge_rows * 2 > 0x7fffffffll) return 1;
+    } else {
     if (!pack || !pack->node_rows || (cols > 0 && !pack->edge_rows)) return set_error(GSN_E_INVALID, "gsn_layer_fused_fwd_pack16_hip: null pack");
     if ((reinterpret_cast<uintptr_t>(pack->node_rows) | reinterpret_cast<uintptr_t>(pack->edge_rows)) & 15) return set_error(GSN_E_INVALID, "gsn_layer_fused_fwd_pack16_hip: packs must be 16-byte aligned");
     if (n_nodes * 64 > 0x7fffffffll || edge_rows * 32 > 0x7fffffffll) return 1;        // (32-bit buffer offsets: the fp32 kernel takes the call)
+    }
     if (reinterpret_cast<const unsigned *>(prepared) == nullptr) return set_error(GSN_E_INVALID, "gsn_layer_fused_fwd_pack16_hip: null prepared");
     RpArgs a{};
     a.n_nodes = (int)n_nodes; a.n_edges = (int)n_edges; a.seg_ptr = seg_ptr;
     a.role_idx[0] = edge->blocks[0].idx32; a.role_idx[1] = edge->blocks[1].idx32;
     a.role_idx[2] = cols > 0 ? edge->blocks[2].idx32 : edge->blocks[0].idx32;
-    a.node16 = pack->node_rows; a.node_bytes = (unsigned)(n_nodes * 64);
-    if (cols > 0) { a.edge16 = pack->edge_rows; a.edge_bytes = (unsigned)(edge_rows * 32); a.edge_shift = 5; }
+    if (keys) {
+        a.node16 = keys->node_dict; a.node_bytes = (unsigned)(keys->dict_rows * 64);
+        a.edge16 = keys->idmask; a.edge_bytes = (unsigned)(edge_rows * 2); a.edge_shift = 1;
+        a.ekeys = keys->ekeys; a.nkey = keys->nkey; a.edge_col0 = keys->edge_col0;
+    } else {
+        a.node16 = pack->node_rows; a.node_bytes = (unsigned)(n_nodes * 64);
+    }
+    if (keys) {}                       // (set above)
+    else if (cols > 0) { a.edge16 = pack->edge_rows; a.edge_bytes = (unsigned)(edge_rows * 32); a.edge_shift = 5; }
     else { a.edge16 = pack->node_rows; a.edge_bytes = a.node_bytes; a.edge_shift = 6; }      // (finite values under zero weights)
     a.d_x = (int)d_x; a.out = out; a.prep = reinterpret_cast<const unsigned *>(prepared);
     const int64_t n_tiles = (n_nodes + RR_TN - 1) / RR_TN;
@@ -806,12 +868,23 @@ int rp_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const g
         a.n_split = (ranges == gx * RR_NW && share > 0.0 && share < 1.0) ? (int)((double)n_nodes * share) : 0;
     }
     static const bool prof_on = sw_on(SW_FUSED_PROF, false);
-    const void *fn = prof_on ? reinterpret_cast<const void *>(&layer_fused_kernel_rp<4, 2, true>) : reinterpret_cast<const void *>(&layer_fused_kernel_rp<4, 2, false>);
-    static DeviceOnce attr_set;
-    if (int rc = lds_limit(&attr_set, {fn}, "layer_fused_kernel_rp")) return rc;
-    trace("gsn chain: layer_fused_kernel_rp<4,2> nodes %d edges %d grid %lld ranges %d\n", a.n_nodes, a.n_edges, (long long)gx, a.n_ranges);
+    // (the KEYS variant's byte table lies behind the shared layout: its launch alone is sized for it)
+    const int lds_bytes = SH::LDS_BYTES + (keys ? RP_BYTE_TAB_BYTES : 0);
+    static_assert(SH::LDS_BYTES % 16 == 0 && SH::LDS_BYTES + RP_BYTE_TAB_BYTES <= 160 * 1024, "the byte table fits behind the weights");
+    if (keys) {
+        const void *fn = prof_on ? reinterpret_cast<const void *>(&layer_fused_kernel_rp<4, 2, true, true>) : reinterpret_cast<const void *>(&layer_fused_kernel_rp<4, 2, false, true>);
+        static DeviceOnce attr_set_keys;
+        if (int rc = lds_limit(&attr_set_keys, {fn}, "layer_fused_kernel_rp keys", lds_bytes)) return rc;
+    } else {
+        const void *fn = prof_on ? reinterpret_cast<const void *>(&layer_fused_kernel_rp<4, 2, true>) : reinterpret_cast<const void *>(&layer_fused_kernel_rp<4, 2, false>);
+        static DeviceOnce attr_set;
+        if (int rc = lds_limit(&attr_set, {fn}, "layer_fused_kernel_rp")) return rc;
+    }
+    trace("gsn chain: layer_fused_kernel_rp<4,2>%s nodes %d edges %d grid %lld ranges %d\n", keys ? " keys" : "", a.n_nodes, a.n_edges, (long long)gx, a.n_ranges);
     if (prof_on) {
         ProfCounters prof(32 + 2 * (size_t)a.n_ranges, st);
+        if (keys) hipLaunchKernelGGL((layer_fused_kernel_rp<4, 2, true, true>), dim3((unsigned)gx), dim3(64 * RR_NW), lds_bytes, st, a, prof.ptr());
+        else
         hipLaunchKernelGGL((layer_fused_kernel_rp<4, 2, true>), dim3((unsigned)gx), dim3(64 * RR_NW), SH::LDS_BYTES, st, a, prof.ptr());
         const std::vector<unsigned long long> hv = prof.fetch(st);
         const unsigned long long *h = hv.data();
@@ -837,6 +910,8 @@ int rp_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const g
                 fprintf(stderr, "rpprof range %s: blocks %llu tiles %llu total %llu cycles | per block: top %.0f edge %.0f | per tile: exposed edge epilogue %.0f stage0 %.0f split %.0f stage1 %.0f\n",
                         w ? "mid" : "0", o[6], o[7], o[8], o[0] / nb, o[1] / nb, o[2] / nt, o[3] / nt, o[4] / nt, o[5] / nt);
             }
+    } else if (keys) {
+        hipLaunchKernelGGL((layer_fused_kernel_rp<4, 2, false, true>), dim3((unsigned)gx), dim3(64 * RR_NW), lds_bytes, st, a, (unsigned long long *)nullptr);
     } else {
         hipLaunchKernelGGL((layer_fused_kernel_rp<4, 2, false>), dim3((unsigned)gx), dim3(64 * RR_NW), SH::LDS_BYTES, st, a, (unsigned long long *)nullptr);
     }
@@ -859,4 +934,16 @@ extern "C" int gsn_pack16_rows_hip(const float *src, int64_t rows, int64_t width
     hipLaunchKernelGGL(pack16_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, rows, (int)width, dst,
                        (int)dst_stride, (int)col0, (int)(one_col < 0 ? -1 : one_col), status);
     return launch_check("pack16_rows_kernel");
+}
+
+// the byte table of the KEYS variant as the kernel's prologue fills it (fp16 bits [256][8]): for hosts and tests
+extern "C" int gsn_layer_keys_byte_table(uint16_t *dst) {
+    if (!dst) return set_error(GSN_E_INVALID, "gsn_layer_keys_byte_table: dst is null");
+    for (unsigned b = 0; b < 256; ++b)
+        for (int q = 0; q < 4; ++q) {
+            const unsigned w = rp_byte_tab_word(b, q);
+            dst[8 * b + 2 * q] = (uint16_t)(w & 0xffffu);
+            dst[8 * b + 2 * q + 1] = (uint16_t)(w >> 16);
+        }
+    return GSN_OK;
 }

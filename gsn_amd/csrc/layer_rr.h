@@ -21,10 +21,21 @@ int rr_prepare(const gsn_chain_stage *edge, int64_t d_x, const gsn_chain_stage *
 int rr_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const gsn_chain_stage *edge, const float *x, int64_t d_x,
                const gsn_chain_stage *node0, const gsn_chain_stage *node1, const void *prepared, float *out, hipStream_t st);
 
+struct RpKeys;
 // layer_rp.hip: the same layer on exact fp16 row packs (gsn_pack16).  rp_forward returns 1 when the call is outside its 32-bit offsets.
 int rp_supported(const gsn_chain_stage *edge, int64_t d_x, const gsn_chain_stage *node0, const gsn_chain_stage *node1);
 int rp_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const gsn_chain_stage *edge, const float *x, int64_t d_x,
                const gsn_chain_stage *node0, const gsn_chain_stage *node1, const void *prepared, const gsn_pack16 *pack, int64_t edge_rows,
-               float *out, hipStream_t st);
+               float *out, hipStream_t st, const RpKeys *keys = nullptr);
+// keys != null: the KEYS variant (gsn_count_layer_step_keys_hip) -- the operand rows come from the node dictionary and a byte table through the
+// compact outputs of the counting launch; `pack` is not read, x and the node blocks' data pointers are the dictionary
+struct RpKeys {
+    const uint32_t *ekeys;
+    const uint8_t *nkey;
+    const uint16_t *idmask;
+    const uint16_t *node_dict;
+    int64_t dict_rows;
+    int edge_col0;
+};
 
 }  // namespace gsn

@@ -206,6 +206,32 @@ int gsn_count_encode_pack16_side_hip(const uint32_t *plan_host, const uint32_t *
                                      int32_t *status, const int32_t *n_classes, int clamp, uint16_t *pack, int64_t pack_stride,
                                      int64_t pack_col0, const gsn_count_side *side, void *stream);
 
+/* The same launch with COMPACT outputs in place of the packs: layer 0's inputs are one-hot encodings of a few integer codes, and the keys
+ * below say which rows of two tiny tables they are (gsn_count_layer_step_keys_hip reads them; ~0.2 GB of pack rows per 65 536 molecules are
+ * then neither written nor read back).  Each is optional (NULL) except idmask:
+ *   nkey   uint8  [n_nodes]   row of vertex v in the NODE DICTIONARY: the mixed-radix number of its code digits, column 0 most significant.
+ *                             Column c has node_n_classes[c] digits when side->node_clamp (the clamped code), one more otherwise: digit
+ *                             node_n_classes[c] = "none", a code outside its classes (zero segment, *code_status set as above).  Row k of the
+ *                             dictionary is what gsn_one_hot_pack16_hip(clamp = 0, col0 = 0, one_col = 31) writes for the k-th digit tuple
+ *                             in that order; <= 256 rows (GSN_E_UNSUPPORTED beyond).  With nkey, side->node_pack may be NULL.
+ *   ekeys  uint32 [n_edges]   target-sorted order (position i of perm): nkey[sorted_target[i]] | nkey[sorted_other[i]] << 8 | m << 16, m = the
+ *                             edge codes' hot columns of column perm[i] as a bit mask (bit j = pack column side->edge_col0 + j).  Needs the
+ *                             four CSR arrays, which are written as before.
+ *   idmask uint16 [n_edges]   column order: the hot pack columns pack_col0 .. of the row's identifier classes as a bit mask (bit j = pack
+ *                             column j; a count outside its classes, unclamped, sets none) -- 2 bytes in place of 2 sum(n_classes);
+ *                             pack_col0 + sum(n_classes) <= 16.
+ * No edge pack is written (side->edge_codes only feed ekeys); everything else is gsn_count_encode_pack16_side_hip's. */
+typedef struct {
+    uint8_t *nkey;
+    uint32_t *ekeys;
+    uint16_t *idmask;
+} gsn_count_keys;
+int gsn_count_encode_keys_side_hip(const uint32_t *plan_host, const uint32_t *plan_dev, int64_t plan_words, int64_t n_graphs,
+                                   const int64_t *node_ptr, const int64_t *edge_ptr, const int64_t *edge_index,
+                                   int64_t edge_row_stride, int ids_are_global, int64_t max_nodes, int64_t max_edges, int64_t *out,
+                                   int32_t *status, const int32_t *n_classes, int clamp, int64_t pack_col0, const gsn_count_side *side,
+                                   const gsn_count_keys *keys, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * HP-2  aggregation target index (device).  The scatter-add of the layers,
  *   torch.sparse.FloatTensor(edge_index, msgs, [N,N,d]) + torch.sparse.sum(msgs, aggr_dim).to_dense()
@@ -523,6 +549,18 @@ typedef struct {
 int gsn_count_layer_step_hip(const gsn_count_call *count, const gsn_layer_pack16_call *layer, void *event_between, void *stream);
 /* event_between: a hipEvent_t recorded on `stream` between the two launches, or NULL (a measuring host brackets the two kernels of the one
  * call with it: bench.py's per-kernel HIP-event times). */
+/* The same step on code keys (gsn_count_encode_keys_side_hip + the KEYS variant of the packed-row layer kernel): the counting launch leaves
+ * count->side's CSR and `keys` instead of the two packs, the layer gathers its x_i / x_j / x_v operand rows from `node_dict` (fp16
+ * [dict_rows][32], the node dictionary described at gsn_count_keys, <= 256 rows, 16-byte aligned, constant per class configuration) through
+ * the key bytes and expands its edge-level operand rows from idmask[perm[e]] | bond mask << side->edge_col0 through a constant table in
+ * LDS.  The operand fragments are those of the pack path bit for bit, and so are the layer rows.  count->pack and layer->pack are not read
+ * (count->pack_col0 is); the edge stage's blocks 0 / 1 / 2 must be indexed by side->sorted_target / sorted_other / perm.  Two launches, no
+ * allocation, no host synchronisation, capturable; event_between as above. */
+/* The constant table that variant expands the edge-level operand rows from, as its kernel fills it into LDS: host array fp16 bits [256][8],
+ * entry b = the eight values 0 / 1.0 (0x3c00) of the bits of b, value j from bit j (no device work). */
+int gsn_layer_keys_byte_table(uint16_t *dst);
+int gsn_count_layer_step_keys_hip(const gsn_count_call *count, const gsn_layer_pack16_call *layer, const gsn_count_keys *keys,
+                                  const uint16_t *node_dict, int64_t dict_rows, void *event_between, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * HP-2  dense stage on DIRECT rows with fp16x3 matrix arithmetic (device): the same operation as gsn_linear_fwd_hip
