@@ -87,6 +87,9 @@ SIGNATURES = {
     "gsn_count_plan_build": (c_int, [c_int, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "gsn_count_hip": (c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_i64, c_i64, c_i64,
                               c_vp, c_vp, c_vp]),
+    "gsn_count_sparse_hip": (c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_i64, c_i64, c_i64,
+                                     c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "gsn_count_sparse_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
     "gsn_count_encode_hip": (c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_i64, c_i64, c_i64,
                                      c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     "gsn_count_encode_pack16_hip": (c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_i64, c_i64, c_i64,

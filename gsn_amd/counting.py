@@ -8,6 +8,10 @@
 * :func:`count_batch` / :func:`counts2ids_batch` -- the batched driver: a whole dataset shard per launch.
 
 Everything routes through ``gsn_count_hip`` in libgsn_hip.so.  No CPU fallback: without a GPU these raise.
+
+Graphs the LDS-resident kernel refuses (more than 768 vertices, tables beyond its LDS, 65 535 columns per graph) go to the sparse kernel
+(``gsn_count_sparse_hip``, csrc/count_sparse.hip): :func:`count_batch` / :func:`counts2ids_batch` on request (``large="sparse"``), the
+per-graph drop-ins always.
 """
 from __future__ import annotations
 
@@ -79,8 +83,14 @@ def _as_dev_i64(x, device):
 
 def count_batch(plan: CountPlan, node_ptr, edge_ptr, edge_index, ids_are_global=True, max_nodes=None, max_edges=None,
                 device=None, graph_ids=None, out=None, check=True, encode=None, counts=True, encoded_out=None, encoded_pack=None,
-                encoded_rows=True):
+                encoded_rows=True, large="refuse"):
     """Run the counting kernel over a batch.
+
+    ``large``: what becomes of a launch the LDS-resident kernel refuses for its size (a graph of more than 768 vertices, tables beyond
+    160 KiB of LDS, 65 535 columns per graph).  ``"refuse"`` (default): :class:`GsnError`.  ``"sparse"``: the sparse kernel
+    (``gsn_count_sparse_hip``: sorted neighbour lists in HBM, one lane per rooted search) counts the launch -- at once when ``max_nodes``
+    exceeds 768, else after ``gsn_count_hip`` has refused.  Plain counts only: with ``encode`` it is a ``ValueError``; directed plans
+    are refused by the sparse kernel.
 
     ``encode=(n_classes, clamp)`` also returns the one-hot encoded identifiers the GSN layers consume (the reference's
     ``DiscreteEmbedding('one_hot_encoder')`` over the counts, utils_graph_learning.py:170-187) straight from the kernel
@@ -97,6 +107,10 @@ def count_batch(plan: CountPlan, node_ptr, edge_ptr, edge_index, ids_are_global=
     of edge_index in edge mode), ``status`` int32 [G].  With ``check`` the statuses are read back and the reference's
     errors are raised (KeyError when a match uses a direction that is not a column, utils_graph_processing.py:173).
     """
+    if large not in ("refuse", "sparse"):
+        raise ValueError("large: 'refuse' or 'sparse' (got %r)" % (large,))
+    if large == "sparse" and encode is not None:
+        raise ValueError("large='sparse' counts only: the fused encodings (encode=) stay on the LDS-resident kernel")
     _abi.require_gpu()
     if device is None:
         device = edge_index.device if isinstance(edge_index, torch.Tensor) and edge_index.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -167,7 +181,16 @@ def count_batch(plan: CountPlan, node_ptr, edge_ptr, edge_index, ids_are_global=
                     rc = _abi.lib().gsn_count_hip(*common, _abi.current_stream())
                     pack_codes_later = True
             elif enc is None:
-                rc = _abi.lib().gsn_count_hip(*common, _abi.current_stream())
+                rc = -2 if (large == "sparse" and int(max_nodes) > 768 and not plan.directed) else _abi.lib().gsn_count_hip(*common, _abi.current_stream())
+                if rc == -2 and large == "sparse" and not plan.directed:
+                    # GSN_E_UNSUPPORTED of a plain count is a size reason (vertices, columns, LDS): the sparse kernel has no such limit
+                    span = torch.stack([node_ptr_d[-1] - node_ptr_d[0], edge_ptr_d[-1] - edge_ptr_d[0]]).tolist()
+                    ws_bytes = _abi.lib().gsn_count_sparse_workspace_bytes(int(span[0]), int(span[1]), plan.n_cols)
+                    if ws_bytes < 0:
+                        raise _abi.GsnError("gsn_count_sparse_hip: %d vertices / %d columns in one launch are beyond its 32-bit ids" % (span[0], span[1]))
+                    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)       # (the allocator's blocks are 512-byte aligned)
+                    rc = _abi.lib().gsn_count_sparse_hip(*common, ws.data_ptr(), ws_bytes, _abi.current_stream())
+                    _abi.check(rc, "gsn_count_sparse_hip")
             elif encoded_pack is None:
                 packs.release(enc)                  # (rewritten through its raw pointer: an earlier pack no longer describes it)
                 rc = _abi.lib().gsn_count_encode_hip(*common, _abi.ptr(enc_tab), int(bool(encode[1])), enc.data_ptr(), _abi.current_stream())
@@ -304,11 +327,11 @@ def _raise_statuses(status):
         raise ValueError("graph %d: %s" % (int(bad[0]), _STATUS_MSG.get(int(st[bad[0]]), "status %d" % st[bad[0]])))
 
 
-def counts2ids_batch(batch, pattern_edge_lists, mode, induced, directed_orbits=False, device=None, directed=False):
+def counts2ids_batch(batch, pattern_edge_lists, mode, induced, directed_orbits=False, device=None, directed=False, large="refuse"):
     """Batched ``subgraph_counts2ids`` over a :class:`gsn_amd.synth.Batch`-like object (node_ptr, edge_ptr, edge_index
-    with batch-global ids, self loops already stripped).  -> int64 device tensor [rows_total, sum orbits]."""
+    with batch-global ids, self loops already stripped).  -> int64 device tensor [rows_total, sum orbits].  ``large``: as :func:`count_batch`."""
     plan = CountPlan.get(pattern_edge_lists, mode, induced, directed_orbits, directed)
-    out, _ = count_batch(plan, batch.node_ptr, batch.edge_ptr, batch.edge_index, ids_are_global=True, device=device)
+    out, _ = count_batch(plan, batch.node_ptr, batch.edge_ptr, batch.edge_index, ids_are_global=True, device=device, large=large)
     return out
 
 
@@ -333,6 +356,12 @@ def _directed_of(pats, directed):
     return directed
 
 
+def _large_for(plan):
+    """The per-graph drop-ins take graphs of any size, as the reference does: what the LDS-resident kernel refuses goes to the sparse
+    kernel.  Directed plans have no sparse kernel: they keep the LDS kernel's refusal and its message."""
+    return "refuse" if plan.directed else "sparse"
+
+
 def _single_graph(edge_index, num_nodes):
     ei = edge_index if isinstance(edge_index, torch.Tensor) else torch.as_tensor(np.asarray(edge_index))
     ei = ei.to(torch.int64)
@@ -353,7 +382,7 @@ def subgraph_isomorphism_vertex_counts(edge_index, **kwargs):
     directed = _directed_of([sg], kwargs.get("directed", False))
     plan = CountPlan.get([sg.edge_list], "vertex", induced, False, directed)
     ei, n, E = _single_graph(edge_index, num_nodes)
-    out, _ = count_batch(plan, [0, n], [0, E], ei, ids_are_global=False, max_nodes=n, max_edges=E)
+    out, _ = count_batch(plan, [0, n], [0, E], ei, ids_are_global=False, max_nodes=n, max_edges=E, large=_large_for(plan))
     return out[:int(num_nodes)].cpu().to(torch.float64)
 
 
@@ -366,7 +395,7 @@ def subgraph_isomorphism_edge_counts(edge_index, **kwargs):
     sg = _pattern_of(subgraph_dict)
     plan = CountPlan.get([sg.edge_list], "edge", induced, sg.directed_orbits)
     ei, n, E = _single_graph(edge_index, 0)
-    out, _ = count_batch(plan, [0, max(n, 1)], [0, E], ei, ids_are_global=False, max_nodes=max(n, 1), max_edges=E)
+    out, _ = count_batch(plan, [0, max(n, 1)], [0, E], ei, ids_are_global=False, max_nodes=max(n, 1), max_edges=E, large="sparse")
     if getattr(sg, "line_graph_orbits", False):
         _line_graph_orbits_keyerror(sg, out)
         return torch.zeros((E, len(subgraph_dict["orbit_partition"])), dtype=torch.float64)
@@ -407,7 +436,7 @@ def subgraph_counts2ids(count_fn, data, subgraph_dicts, subgraph_params):
     dirorb = any(p.directed_orbits for p in pats) if mode == "edge" else False
     plan = CountPlan.get([p.edge_list for p in pats], mode, subgraph_params["induced"], dirorb, directed)
     e_cpu, n, E = _single_graph(edge_index, num_nodes)
-    out, _ = count_batch(plan, [0, n], [0, E], e_cpu, ids_are_global=False, max_nodes=n, max_edges=E)
+    out, _ = count_batch(plan, [0, n], [0, E], e_cpu, ids_are_global=False, max_nodes=n, max_edges=E, large=_large_for(plan))
     ids = out[:num_nodes] if mode == "vertex" else out
     if mode == "edge" and any(getattr(p, "line_graph_orbits", False) for p in pats):
         cols, blocks = 0, []

@@ -1,0 +1,234 @@
+// Rooted subgraph search over sorted neighbour lists: the arithmetic core of the sparse counting kernel (count_sparse.hip), for the graphs
+// that the LDS-resident kernel (count.hip / count_core.h) refuses: more than 768 vertices, tables beyond 160 KiB of LDS, 65 535 columns.
+//
+// Shared between the HIP kernel and a host-side harness used ONLY by tests (tests/sparse_harness.cpp compiles this header with g++; it is
+// not a product fallback).  Everything is integer arithmetic; results are exact.
+//
+// The graph is a CSR of neighbour lists: the neighbours of vertex v are nbr[row_ptr[v] .. row_ptr[v + 1]), 32-bit vertex ids, STRICTLY
+// increasing -- no duplicate entries and no self loops (the set-up pass, or the harness, removes both).  Vertex ids are whatever the
+// caller numbers the rows of row_ptr with (batch-global in the kernel): only their order within one graph matters, and an offset keeps it.
+//
+// One lane runs one rooted search of one plan of the packed plan table (gsn_internal.h).  Only the per-level masks
+// adj | nonadj << 8 | gt << 16 | lt << 24 of levels n_fixed .. k - 1 are read: they define the result completely.  min_degree, the distance
+// bytes and the cores of the LDS kernel only prune work and are ignored here.  Closed forms of the plan's tail (patterns.cpp:
+// plan_tail_mode) that are honoured because they are cheap on lists: mode 2 (twin levels: C(|C|, r)) and mode 1 (independent last levels:
+// |C1| |C2| - |C1 & C2|); mode 3 (chain) runs the generic search.  Directed plans are not handled (the launcher refuses them).
+//
+// The search is an iterative depth-first walk (no recursion).  Level l takes its candidates from the neighbour list of ONE earlier image named by its
+// adjacency mask (the anchor: the one with the shortest list), rejects a candidate equal to an earlier image, checks the other adjacency
+// bits by binary search in the earlier images' lists, the non-adjacency bits by a failing binary search, and gt / lt by comparison.  A level
+// with an empty adjacency mask (a disconnected pattern; none of the pattern families of the reference has one) walks all vertices of the
+// graph instead.  The last level is counted, never descended into.
+//
+// Per-lane state: for each level 0 .. 7 the image, the cursor and the end of its candidate list, and the masks still to check (the
+// level's masks without the anchor's adjacency bit): SP_FIELDS * SP_LEVELS words at st[(field * SP_LEVELS + level) * ss] -- ss = 1 for a
+// plain array (host), ss = the lane count with st pointing at the lane's own word of a lane-interleaved LDS array (device).
+#pragma once
+
+#include <stdint.h>
+
+#include "count_core.h"
+
+namespace gsn {
+
+constexpr int SP_LEVELS = 8;          // levels that hold an image or a cursor: 0 .. k - 2 with k <= GSN_KMAX = 9
+enum { SP_IMG = 0, SP_CUR = 1, SP_END = 2, SP_CHK = 3, SP_FIELDS = 4 };
+static_assert(GSN_KMAX - 1 <= SP_LEVELS, "the last level is counted, every earlier one has a slot");
+
+struct SparseGraph {
+    const uint32_t *row_ptr;   // [n + 1] over the caller's vertex numbering
+    const uint32_t *nbr;       // strictly increasing within a row
+    uint32_t v_lo, v_hi;       // the vertices of the graph the roots lie in (walked only by a level without an adjacency mask)
+};
+
+#define GSN_SP(F, L) st[((F) * SP_LEVELS + (L)) * ss]
+
+// position of b in the list of a, or -1
+GSN_HD int64_t sp_find(const SparseGraph &g, uint32_t a, uint32_t b) {
+    uint32_t lo = g.row_ptr[a], hi = g.row_ptr[a + 1];
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        const uint32_t x = g.nbr[mid];
+        if (x == b) return (int64_t)mid;
+        if (x < b) lo = mid + 1; else hi = mid;
+    }
+    return -1;
+}
+
+// does v satisfy the masks `chk` against the images of the levels they name?
+GSN_HD bool sp_masks_hold(const SparseGraph &g, const uint32_t *st, int ss, uint32_t chk, uint32_t v) {
+    uint32_t m = chk & 0xffu;
+    while (m) {
+        const int j = ctz64(m);
+        m &= m - 1u;
+        if (sp_find(g, GSN_SP(SP_IMG, j), v) < 0) return false;
+    }
+    m = (chk >> 8) & 0xffu;
+    while (m) {
+        const int j = ctz64(m);
+        m &= m - 1u;
+        if (sp_find(g, GSN_SP(SP_IMG, j), v) >= 0) return false;
+    }
+    m = (chk >> 16) & 0xffu;
+    while (m) {
+        const int j = ctz64(m);
+        m &= m - 1u;
+        if (!(v > GSN_SP(SP_IMG, j))) return false;
+    }
+    m = chk >> 24;
+    while (m) {
+        const int j = ctz64(m);
+        m &= m - 1u;
+        if (!(v < GSN_SP(SP_IMG, j))) return false;
+    }
+    return true;
+}
+
+// candidate of a level with the images of levels 0 .. nimg - 1 placed: distinct from all of them, and the masks hold
+GSN_HD bool sp_accept(const SparseGraph &g, const uint32_t *st, int ss, uint32_t chk, int nimg, uint32_t v) {
+    for (int j = 0; j < nimg; ++j)
+        if (GSN_SP(SP_IMG, j) == v) return false;
+    return sp_masks_hold(g, st, ss, chk, v);
+}
+
+// the candidate list of a level with masks `desc`: positions cur .. end of nbr (or vertex ids, when the level has no adjacency mask),
+// and the masks that remain to be checked per candidate
+GSN_HD void sp_open(const SparseGraph &g, const uint32_t *st, int ss, uint32_t desc, uint32_t &cur, uint32_t &end, uint32_t &chk) {
+    uint32_t m = desc & 0xffu;
+    if (!m) { cur = g.v_lo; end = g.v_hi; chk = desc; return; }
+    int best = -1;
+    uint32_t blen = 0, bcur = 0;
+    while (m) {
+        const int j = ctz64(m);
+        m &= m - 1u;
+        const uint32_t a = GSN_SP(SP_IMG, j), lo = g.row_ptr[a], len = g.row_ptr[a + 1] - lo;
+        if (best < 0 || len < blen) { best = j; blen = len; bcur = lo; }
+    }
+    cur = bcur; end = bcur + blen; chk = desc & ~(1u << best);
+}
+GSN_HD uint32_t sp_at(const SparseGraph &g, uint32_t desc, uint32_t pos) { return (desc & 0xffu) ? g.nbr[pos] : pos; }
+
+// number of candidates of a level with masks `desc` (images 0 .. nimg - 1 placed) that, with `both`, also satisfy the masks `desc2`
+GSN_HD uint64_t sp_count_level(const SparseGraph &g, const uint32_t *st, int ss, uint32_t desc, int nimg, bool both = false, uint32_t desc2 = 0) {
+    uint32_t cur, end, chk;
+    sp_open(g, st, ss, desc, cur, end, chk);
+    uint64_t c = 0;
+    for (; cur < end; ++cur) {
+        const uint32_t v = sp_at(g, desc, cur);
+        if (!sp_accept(g, st, ss, chk, nimg, v)) continue;
+        if (both && !sp_masks_hold(g, st, ss, desc2, v)) continue;
+        ++c;
+    }
+    return c;
+}
+
+// One rooted search, resumable: sp_begin places the roots, every sp_step runs one turn of the walk (opens a level -- or counts it, when it
+// is the last or the head of a closed-form tail -- or tries one candidate), s.l < 0 = finished, s.cnt holds the maps.  The kernel's lanes
+// interleave turns of different searches; sp_search is the same thing run to the end.
+struct SparseLane {
+    const uint32_t *plan;
+    int k, nfix, tm, tl;      // tail mode honoured by this search (0: none) and the level it starts at
+    int l;                    // level being opened or consumed; < 0: no search in progress
+    bool enter;               // level l is to be opened
+    uint64_t cnt;             // accumulates over the plans of a cell
+};
+
+// the roots: r0 = level 0, r1 = level 1 (plans with two fixed levels)
+GSN_HD void sp_begin(SparseLane &s, const uint32_t *plan, uint32_t r0, uint32_t r1, uint32_t *st, int ss) {
+    s.plan = plan;
+    s.k = (int)(plan[0] & 0xffu); s.nfix = (int)((plan[0] >> 8) & 0xffu);
+    GSN_SP(SP_IMG, 0) = r0;
+    if (s.nfix > 1) GSN_SP(SP_IMG, 1) = r1;
+    s.l = -1;
+    if (s.nfix >= s.k) { s.cnt += 1; return; }
+    s.tm = plan_tail(plan); s.tl = -1;
+    if (s.tm == 2) s.tl = plan_tail_level(plan, s.k);
+    if (s.tm == 1) s.tl = s.k - 2;
+    if (s.tl < s.nfix) s.tm = 0;                 // (mode 3, or a tail that starts inside the roots: the generic walk)
+    s.l = s.nfix;
+    s.enter = true;
+}
+
+GSN_HD void sp_step(const SparseGraph &g, SparseLane &s, uint32_t *st, int ss) {
+    const int l = s.l, k = s.k;
+    const uint32_t desc = s.plan[2 + l];
+    if (s.enter) {
+        s.enter = false;
+        if (l == k - 1) {
+            s.cnt += sp_count_level(g, st, ss, desc, l);
+        } else if (s.tm == 2 && l == s.tl) {     // r twin levels: any r of the candidates, in one order
+            const uint64_t n1 = sp_count_level(g, st, ss, desc, l);
+            const int r = 2 + (int)(s.plan[1] >> 30);
+            if (n1 >= (uint64_t)r) {
+                uint64_t c = 1;
+                for (int i = 0; i < r; ++i) c = c * (n1 - (uint64_t)i) / (uint64_t)(i + 1);     // (exact at every step)
+                s.cnt += c;
+            }
+        } else if (s.tm == 1 && l == s.tl) {     // the last level's masks do not name level k - 2: pairs minus the coinciding ones
+            const uint32_t d2 = s.plan[2 + k - 1];
+            const uint64_t n1 = sp_count_level(g, st, ss, desc, l);
+            if (n1) s.cnt += n1 * sp_count_level(g, st, ss, d2, l) - sp_count_level(g, st, ss, desc, l, true, d2);
+        } else {
+            uint32_t cur, end, chk;
+            sp_open(g, st, ss, desc, cur, end, chk);
+            GSN_SP(SP_CUR, l) = cur; GSN_SP(SP_END, l) = end; GSN_SP(SP_CHK, l) = chk;
+            return;
+        }
+        s.l = l - 1 < s.nfix ? -1 : l - 1;       // counted: back to the level above
+        return;
+    }
+    const uint32_t cur = GSN_SP(SP_CUR, l);
+    if (cur >= GSN_SP(SP_END, l)) {
+        s.l = l - 1 < s.nfix ? -1 : l - 1;
+        return;
+    }
+    GSN_SP(SP_CUR, l) = cur + 1;
+    const uint32_t v = sp_at(g, desc, cur);
+    if (!sp_accept(g, st, ss, GSN_SP(SP_CHK, l), l, v)) return;
+    GSN_SP(SP_IMG, l) = v;
+    s.l = l + 1;
+    s.enter = true;
+}
+
+// the number of maps of one plan
+GSN_HD uint64_t sp_search(const SparseGraph &g, const uint32_t *plan, uint32_t r0, uint32_t r1, uint32_t *st, int ss) {
+    SparseLane s;
+    s.cnt = 0; s.tm = 0; s.tl = -1;
+    sp_begin(s, plan, r0, r1, st, ss);
+    while (s.l >= 0) sp_step(g, s, st, ss);
+    return s.cnt;
+}
+
+// one cell: the plans col_ptr[col] .. col_ptr[col + 1] of the table all add to output column `col`
+GSN_HD uint64_t sp_cell(const SparseGraph &g, const uint32_t *table, int col, uint32_t r0, uint32_t r1, uint32_t *st, int ss) {
+    const uint32_t *col_ptr = table + PLAN_HEADER_WORDS;
+    const uint32_t *plans = table + table[7];
+    uint64_t cnt = 0;
+    for (uint32_t p = col_ptr[col]; p < col_ptr[col + 1]; ++p) cnt += sp_search(g, plans + (size_t)p * PLAN_STRIDE_WORDS, r0, r1, st, ss);
+    return cnt;
+}
+
+// Edge mode: what the lane that draws column c = (u, v) does with the row.  arc_col[slot] = the LAST column that holds the arc of that
+// slot of nbr (utils_graph_processing.py:142-144: the last duplicate carries the counts), -1 = none.
+//   SP_ROW_ZERO    the row carries nothing: a self loop, an earlier duplicate
+//   SP_ROW_MIRROR  undirected orbit classes (sym) and u > v with the reverse column present: that column's lane writes this row too
+//   SP_ROW_SEARCH  search; `mirror` = the reverse column to write as well (sym), else -1; `rev_missing`: a non-zero count is a KeyError
+enum { SP_ROW_ZERO = 0, SP_ROW_MIRROR = 1, SP_ROW_SEARCH = 2 };
+GSN_HD int sp_edge_row(const SparseGraph &g, const int32_t *arc_col, int64_t c, uint32_t u, uint32_t v, bool sym, int64_t &mirror, bool &rev_missing) {
+    mirror = -1; rev_missing = false;
+    if (u == v) return SP_ROW_ZERO;
+    const int64_t s = sp_find(g, u, v);
+    if (s < 0 || (int64_t)arc_col[s] != c) return SP_ROW_ZERO;
+    const int64_t rs = sp_find(g, v, u);          // (the graph is symmetric: the slot exists)
+    const int64_t rev = rs < 0 ? -1 : (int64_t)arc_col[rs];
+    rev_missing = rev < 0;
+    if (sym && rev >= 0) {
+        if (u > v) return SP_ROW_MIRROR;
+        mirror = rev;
+    }
+    return SP_ROW_SEARCH;
+}
+
+#undef GSN_SP
+
+}  // namespace gsn

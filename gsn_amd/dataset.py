@@ -6,7 +6,7 @@ What stays identical to the reference, graph by graph: the attributes each prepa
 ``identifiers`` int64 [rows, sum orbits] with columns in pattern order then orbit index -- utils_ids.py:7-29), the
 returned tuple, the ``.pt`` cache tuple ``(graphs, num_classes, orbit_partition_sizes)`` (utils.py:272-274) and
 ``downgrade_k`` slicing (utils.py:332-345).  Collation of the raw graphs is host-side numpy; the counts come from the
-HIP kernel (gsn_count_hip) -- there is no CPU counting path here.
+HIP kernels (gsn_count_hip; gsn_count_sparse_hip for graphs of more than 768 vertices) -- there is no CPU counting path here.
 """
 from __future__ import annotations
 
@@ -15,6 +15,9 @@ import torch
 
 from . import counting, data as gdata, dist
 from .patterns import PatternGraph
+
+
+_WIDTH_CLASSES = np.array([64, 128, 256, 512, 768])      # vertices: the LDS kernel's bit rows of 1 / 2 / 4 / 8 / 12 words; above: the sparse kernel
 
 
 def _mode_of(count_fn):
@@ -75,9 +78,12 @@ def prepare_graphs(graphs, subgraph_dicts, subgraph_params, regression, dataset_
     # 768 vertices), so one 222-vertex molecule would put all 41 k graphs of ogbg-molhiv (25 vertices on average) on the four-word kernel
     # instead of the molecule kernel (two graphs per wave, compile-time invariants).  Graphs are independent: they are processed grouped by
     # class -- one launch per class that occurs, each over a contiguous range of the regrouped batch -- and handed back in the caller's order.
+    # Graphs of more than 768 vertices are a class of their own: the LDS-resident kernel does not take them, the sparse kernel
+    # (gsn_count_sparse_hip) counts them in a launch of its own.  A class whose launch the LDS kernel refuses for its size all the same
+    # (tables beyond its LDS, 65 535 columns in a graph) is repeated on the sparse kernel (count_batch: large="sparse").
     order = None
     if len(graphs) > 1:
-        cls = np.searchsorted(np.array([64, 128, 256, 512]), np.array([int(g.node_features.shape[0]) for g in graphs]), side="left")
+        cls = np.searchsorted(_WIDTH_CLASSES, np.array([int(g.node_features.shape[0]) for g in graphs]), side="left")
         if cls.min() != cls.max():
             order = np.argsort(cls, kind="stable")
             graphs = [graphs[int(i)] for i in order]
@@ -124,19 +130,19 @@ def prepare_graphs(graphs, subgraph_dicts, subgraph_params, regression, dataset_
         if order is None:
             out, _ = counting.count_batch(plan, node_ptr, edge_ptr, torch.from_numpy(ei), ids_are_global=False,
                                           max_nodes=int(max(n_nodes.max(), 1)), max_edges=int(n_kept.max()), device=device,
-                                          graph_ids=by_falling_cost(0, G))
+                                          graph_ids=by_falling_cost(0, G), large="sparse")
         else:
             dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
             ei_d = torch.from_numpy(ei).to(dev)
             out = torch.empty((int(node_ptr[-1]) if mode == "vertex" else int(edge_ptr[-1]), n_cols), dtype=torch.int64, device=dev)
-            cls_sorted = np.searchsorted(np.array([64, 128, 256, 512]), n_nodes, side="left")
+            cls_sorted = np.searchsorted(_WIDTH_CLASSES, n_nodes, side="left")
             for c in np.unique(cls_sorted):
                 lo, hi = int(np.searchsorted(cls_sorted, c, side="left")), int(np.searchsorted(cls_sorted, c, side="right"))
                 if mode == "edge" and edge_ptr[hi] == edge_ptr[lo]:
                     continue
                 counting.count_batch(plan, node_ptr[lo:hi + 1], edge_ptr[lo:hi + 1], ei_d, ids_are_global=False,
                                      max_nodes=int(max(n_nodes[lo:hi].max(), 1)), max_edges=int(n_kept[lo:hi].max()), device=dev, out=out,
-                                     graph_ids=by_falling_cost(lo, hi))
+                                     graph_ids=by_falling_cost(lo, hi), large="sparse")
         ids_all = out.cpu()
     else:
         ids_all = torch.zeros((0, n_cols), dtype=torch.int64)

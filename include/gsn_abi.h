@@ -31,7 +31,7 @@ extern "C" {
 enum {
     GSN_OK = 0,
     GSN_E_INVALID = -1,     /* bad argument */
-    GSN_E_UNSUPPORTED = -2, /* valid in the reference but outside this build (e.g. k > GSN_KMAX, n > 768: INTEGRATION.md 11) */
+    GSN_E_UNSUPPORTED = -2, /* valid in the reference but outside this build or this entry (e.g. k > GSN_KMAX; n > 768 in gsn_count_hip: INTEGRATION.md 11) */
     GSN_E_HIP = -3,         /* HIP runtime error (message has hipGetErrorString) */
     GSN_E_NOSPACE = -4,     /* caller buffer too small */
     GSN_E_NODEVICE = -5     /* no gfx950 device visible */
@@ -136,6 +136,27 @@ int gsn_count_hip(const uint32_t *plan_host, const uint32_t *plan_dev, int64_t p
                   const int64_t *node_ptr, const int64_t *edge_ptr, const int64_t *edge_index,
                   int64_t edge_row_stride, int ids_are_global, const int32_t *graph_ids, int64_t n_items,
                   int64_t max_nodes, int64_t max_edges, int64_t *out, int32_t *status, void *stream);
+
+/* The same counts for the graphs gsn_count_hip refuses (more than 768 vertices, tables beyond 160 KiB of LDS, 65 535 columns per graph):
+ * the same reference lines (utils_ids.py:7-29 over utils_graph_processing.py:103-131 / :134-179), by a kernel whose graph lives in HBM as
+ * sorted neighbour lists -- one lane per rooted search, no table sized by LDS (csrc/count_sparse.hip).  Opt-in: gsn_count_hip never
+ * forwards to it.  Arguments as gsn_count_hip, except
+ *   max_nodes, max_edges  carry no size limit here (no GSN_ST_TOO_LARGE)
+ *   workspace             device scratch of workspace_bytes >= gsn_count_sparse_workspace_bytes(...), 256-byte aligned; GSN_E_NOSPACE below
+ * Statuses: GSN_ST_BAD_INDEX (an endpoint outside the graph, or the graph's pointers outside the launch's): that graph's rows are zero,
+ * the other graphs are counted; GSN_ST_KEYERROR as gsn_count_hip.  Rows of graphs outside graph_ids are untouched.
+ * Limits: vertices and columns are numbered from node_ptr[0] / edge_ptr[0] of the launch in 32 bits (< 2^31 - 1 vertices, <= 2^30 columns:
+ * GSN_E_UNSUPPORTED beyond); directed plans (GSN_FLAG_DIRECTED) -> GSN_E_UNSUPPORTED; no fused encodings.  The call reads four
+ * pointer entries back (one stream synchronisation), so it cannot be captured into a graph.  Deterministic: every cell has one writer. */
+int gsn_count_sparse_hip(const uint32_t *plan_host, const uint32_t *plan_dev, int64_t plan_words, int64_t n_graphs,
+                         const int64_t *node_ptr, const int64_t *edge_ptr, const int64_t *edge_index,
+                         int64_t edge_row_stride, int ids_are_global, const int32_t *graph_ids, int64_t n_items,
+                         int64_t max_nodes, int64_t max_edges, int64_t *out, int32_t *status, void *workspace,
+                         int64_t workspace_bytes, void *stream);
+/* Host: bytes of workspace for a launch that spans n_vertices_total = node_ptr[G] - node_ptr[0] vertices and n_columns_processed =
+ * edge_ptr[G] - edge_ptr[0] columns (the launch's tables cover the whole span, also when graph_ids names a few of its graphs); n_cols =
+ * the plan's output columns (no table depends on it today).  -1 beyond the 32-bit limits above. */
+int64_t gsn_count_sparse_workspace_bytes(int64_t n_vertices_total, int64_t n_columns_processed, int64_t n_cols);
 
 /* Counting with the identifier encoding fused into the kernel's output: what the reference does in two steps -- int64 counts
  * (utils_ids.py:7-29), then DiscreteEmbedding('one_hot_encoder') on them in front of every GSN layer
