@@ -105,9 +105,6 @@ __device__ __forceinline__ unsigned rp_hi_lo_word(float a, float s) {
 }
 __device__ __forceinline__ unsigned rp_pk_max_u16(unsigned a, unsigned b) { unsigned r; asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
-#ifndef RP_DEFER
-#define RP_DEFER 0         // 1: the second feature pair's epilogue of a block waits for the next block's first products (not at a tile's end): +40 live registers, spills
-#endif
 #ifndef RP_GATHER_AT
 #define RP_GATHER_AT 3        // chunk step of node stage 1's first pair at which the next tile's first gathers are issued
 #endif
@@ -182,6 +179,12 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
     const __amdgpu_buffer_rsrc_t rs_n = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(a.node16), 0, (int)a.node_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_e = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(a.edge16), 0, (int)a.edge_bytes, 0x00020000);
     const int esh = a.edge_shift;
+    // multiples of 4 096 held in scalar registers for the whole kernel: a buffer instruction's immediate reaches 4 095 bytes, so the constant
+    // offsets of the output stores (row 8 q + r of a tile: 4096 q + 512 r + 128 fb) and of the weight stream (fragment i: 1024 i) are one of
+    // these + an immediate -- written as plain constants every one of them gets a scalar move of its own (opaque: or they are constants again)
+    int sbase[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { sbase[k] = 4096 * k; asm volatile("" : "+s"(sbase[k])); }
     const int ec0 = a.edge_col0;
     // where the in-degree goes: k-slots d_x (high part) and d_x + 1 (residual) of the node pack's row = one word of one chunk, one lane half
     const int deg_c = a.d_x >> 4, deg_h = (a.d_x >> 3) & 1, deg_w = (a.d_x >> 1) & 3;
@@ -230,8 +233,11 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
     rp_idx_load<KEYS>(a, cur, li0, ixc);
     RrDesc nxt = rr_iter_next(it, lane0);
     rp_idx_load<KEYS>(a, nxt, li0, ixn);
-    rr_u4 g[RR_NKE];                                   // the gathered rows of the CURRENT block (in flight at the top of the loop)
-    auto gather = [&](const int (&r)[3], int lh) {
+    // the gathered rows of the blocks in flight: TWO sets that take turns (a tile's first block reads gA, the next gB, ...; the gathers of
+    // block i + 1 are issued at the top of block i into the set block i does not read).  One set would have to be moved to where the loop
+    // expects it on every back edge -- 10 register copies behind a wait for every load in flight.
+    rr_u4 gA[RR_NKE], gB[RR_NKE];
+    auto gather = [&](rr_u4 (&g)[RR_NKE], const int (&r)[3], int lh) {
         if constexpr (KEYS) {
             // the same four node loads, their rows named by the key word's two bytes (rows of the dictionary: L1 hits); of the edge-level
             // row only its identifier mask, 2 bytes through perm -- the row itself is looked up at the block's top
@@ -248,7 +254,7 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
         g[4] = RP_LOAD(rs_e, ve, 0);
         }
     };
-    gather(ixc.r, lh0);
+    gather(gA, ixc.r, lh0);
     int pt = ixc.pt, pt1 = ixc.pt1;
     int nk = ixc.nk;                                   // KEYS: dictionary row of node m0 + li of the current tile
     unsigned kc = (unsigned)ixc.r[0];                  // KEYS: the key word of the current block's row (its edge-code classes are read at the block's top)
@@ -266,47 +272,42 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
         const int m0 = cur.m0, nn = cur.nn();
         // the x rows of the tile's nodes in the operand layout of node stage 0 (lane (t, h): bytes 32 c + 16 h of row t): requested in the
         // tile's last block, in front of its last epilogue (rows this tile's edge blocks have just gathered: cache hits)
-        rr_u4 X[NKX];                                  // (requested with EVERY block -- an assignment under `last` makes a loop-carried value of it)
+        rr_u4 X[NKX];                                  // (requested with EVERY block -- an assignment under `last` makes a loop-carried value of it, moved about with waits)
         auto load_x = [&]() {
             const unsigned vx = ((unsigned)(KEYS ? nk : m0 + (li < nn ? li : nn - 1)) << 6) | ((unsigned)lh << 4);
 #pragma unroll
             for (int c = 0; c < NKX; ++c) X[c] = RP_LOAD(rs_n, vx, 32 * c);
         };
         f32x16 sacc[WB];                               // S^T tiles: row = feature in block, column = target
-#pragma unroll
-        for (int fb = 0; fb < WB; ++fb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sacc[fb][r] = 0.f;
-        // the second feature pair of a block that is not the tile's last waits here: its activation / plane split / incidence products run
-        // under the first products of the NEXT block
-        f32x16 pa0, pa1;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { pa0[r] = 0.f; pa1[r] = 0.f; }
-        rr_u4 Mp[2] = {rr_u4{0, 0, 0, 0}, rr_u4{0, 0, 0, 0}};
-        bool deferred = false;
         int tpt = 0, tpt1 = 0;
         int rnext[3] = {0, 0, 0};
-        bool last;
-        do {
+        // =============================================================================================================================
+        // one BLOCK of the tile: edge stage + per-node sums.  The tile's FIRST block is peeled out of the loop: its incidence products
+        // start from C = 0 (no zero fill of the 64 sum registers), every further block adds to the sums IN PLACE -- the loop carries the
+        // sums and the gathers in flight, nothing is copied on its back edge (gc: the set this block reads; gn: the set the next block's
+        // rows are gathered into).  Returns whether the block was the tile's last.
+        // =============================================================================================================================
+        auto block = [&](auto first_c, rr_u4 (&gc)[RR_NKE], rr_u4 (&gn)[RR_NKE]) __attribute__((always_inline)) -> bool {
+            constexpr bool FIRST = decltype(first_c)::value;
             const unsigned t0 = clk();
             const int ne = cur.ne();
             if (li >= nn) { pt = 0; pt1 = 0; }
             tpt = pt; tpt1 = pt1;
-            // ---- the gathered rows ARE the operand fragments; the next block's gathers take their place in flight ----------------------------
+            // ---- the gathered rows ARE the operand fragments; the next block's gathers fly beside them in the other set -------------------
             rr_u4 Ah[RR_NKE];
 #pragma unroll
-            for (int c = 0; c < RR_NKE; ++c) Ah[c] = g[c];
+            for (int c = 0; c < RR_NKE; ++c) Ah[c] = gc[c];
             if constexpr (KEYS) {
                 // the edge-level fragment: lane (e, h) takes byte h of the row's hot-column mask (identifier classes | edge-code classes behind
                 // them) and reads its eight fp16 values from the byte table -- used ~16 products later (chunk 4 of the first pair)
-                const unsigned m16 = g[RR_NKE - 1][0] | ((kc >> 16) << ec0);
+                const unsigned m16 = gc[RR_NKE - 1][0] | ((kc >> 16) << ec0);
                 const unsigned byte = (m16 >> (8 * lh)) & 0xffu;
                 Ah[RR_NKE - 1] = *reinterpret_cast<rr_ldsp>(ldsb[2] - 16u * (unsigned)lane + 16u * byte + (unsigned)(SH::LDS_BYTES - 0x20000));
             }
-            last = cur.last() != 0;
+            const bool last = cur.last() != 0;
             // the next block's gathers: inside a tile right here (they fly under this block's edge stage); across a tile boundary they
             // would hold 20 registers through both node stages -- issued in node stage 1, once the hidden rows' registers are free
-            if (!last) gather(ixn.r, lh);
+            if (!last) gather(gn, ixn.r, lh);
 #pragma unroll
             for (int q = 0; q < 3; ++q) rnext[q] = ixn.r[q];
             kc = (unsigned)ixn.r[0];
@@ -320,8 +321,9 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
             // into the incidence product.  Feature blocks in pairs = two accumulator chains issued alternately; weight fragments one step
             // ahead.  A wave issues in order and only vector work BETWEEN two of its own MFMAs runs under them: the activation + plane
             // split of a pair (80 vector instructions) and its 8 incidence products are spread over the 20 products of the NEXT pair.
+            // A block without edges is its tile's only block (rr_iter_next): every block behind the first has some.
             // =========================================================================================================================
-            if (ne > 0) {
+            if (!FIRST || ne > 0) {
                 const unsigned bm = rr_edge_mask(pt, pt1, cur.e0);
                 rr_u4 M[2];
                 rr_incidence(bm, lh, M);
@@ -338,10 +340,19 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
                                   yh[4 * h + 2 * q], yl[4 * h + 2 * q], yh[4 * h + 2 * q + 1], yl[4 * h + 2 * q + 1]);
                     }
                 };
+                // (the first product into a sum of the tile's first block takes the constant 0 as its C operand)
                 auto incid = [&](f32x16 &sv, const unsigned (&yh)[8], const unsigned (&yl)[8], const rr_u4 (&MM)[2], int h) {
                     const rr_u4 pl = rr_u4{yl[4 * h], yl[4 * h + 1], yl[4 * h + 2], yl[4 * h + 3]};
                     const rr_u4 ph = rr_u4{yh[4 * h], yh[4 * h + 1], yh[4 * h + 2], yh[4 * h + 3]};
-                    RR_MFH(pl, MM[h], sv);
+                    if (FIRST && h == 0) {
+                        f32x16 z;
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) z[r] = 0.f;
+                        RR_MFH(pl, MM[h], z);
+                        sv = z;
+                    } else {
+                        RR_MFH(pl, MM[h], sv);
+                    }
                     RR_MFH(ph, MM[h], sv);
                 };
                 // step c (0 .. 4) of a pair's epilogue: 0: tile 0 rows 0-7 | 1: tile 0 rows 8-15 + its first incidence pair | 2: tile 1 rows 0-7 +
@@ -373,28 +384,36 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
                     }
                 };
                 f32x16 qa0, qa1, ra0, ra1;
-                if (deferred) products(0, qa0, qa1, [&](int c) { ep_step(c, pa0, pa1, sacc[2], sacc[3], Mp); });
-                else products(0, qa0, qa1, [&](int) {});
+                products(0, qa0, qa1, [&](int) {});
                 products(2, ra0, ra1, [&](int c) { ep_step(c, qa0, qa1, sacc[0], sacc[1], M); });
                 t2 = clk();
-                if (!last && RP_DEFER) {
-                    pa0 = ra0; pa1 = ra1; Mp[0] = M[0]; Mp[1] = M[1];
-                    deferred = true;
-                } else {
-                    // the tile's last block: its second pair's epilogue behind its own products
-                    load_x();
+                // the second pair's epilogue behind its own products
+                load_x();
 #pragma unroll
-                    for (int c = 0; c < RR_NKE; ++c) ep_step(c, ra0, ra1, sacc[2], sacc[3], M);
-                    RR_SB();
-                    deferred = false;
-                }
+                for (int c = 0; c < RR_NKE; ++c) ep_step(c, ra0, ra1, sacc[2], sacc[3], M);
+                RR_SB();
+            } else {
+                // a tile without any edge: its sums are zero
+#pragma unroll
+                for (int fb = 0; fb < WB; ++fb)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) sacc[fb][r] = 0.f;
+                load_x();
             }
-            else load_x();
             const unsigned t3 = clk();
             if (PROF) { pc[0] += t1 - t0; pc[1] += t2 - t1; pc[2] += t3 - t2; pc[6] += 1; }
             cur = nxt; nxt = nn2;
             pt = npt; pt1 = npt1; nk = nnk;
-        } while (!last);
+            return last;
+        };
+        {
+            bool last = block(std::true_type{}, gA, gB);
+#pragma unroll 1
+            while (!last) {
+                last = block(std::false_type{}, gB, gA);
+                if (!last) last = block(std::false_type{}, gA, gB);
+            }
+        }
         // (the x rows exist HERE: left alone the compiler sinks their loads to their use, where nothing hides them)
 #pragma unroll
         for (int c = 0; c < NKX; ++c) asm volatile("" : "+v"(X[c]));
@@ -489,7 +508,7 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
 #elif defined(RR_ABL_STREAM1)       // (ablation: every stream load hits the same two fragments -- L1 hits instead of the L2 path; results wrong)
 #define RP_STREAM(I) __builtin_bit_cast(rr_u4, __builtin_amdgcn_raw_buffer_load_b128(wstream, 16 * lane, ((I) & 1) * 1024, 0))
 #else
-#define RP_STREAM(I) __builtin_bit_cast(rr_u4, __builtin_amdgcn_raw_buffer_load_b128(wstream, 16 * lane, (I) * 1024, 0))
+#define RP_STREAM(I) __builtin_bit_cast(rr_u4, __builtin_amdgcn_raw_buffer_load_b128(wstream, 16 * lane + ((I) & 3) * 1024, sbase[(I) >> 2], 0))
 #endif
         constexpr int PD = RP_PD, NSL = NKS * WB;
         static_assert(PD % 2 == 0, "the stream is consumed two fragments per step");
@@ -633,7 +652,7 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
                     RR_MFH(b0h, Hh[c], o0);
                     RR_MFH(b1h, Hh[c], o1);
                     if (fp == 0 && c + 1 < NKS) hsplit(c + 1);
-                    if (fp == 0 && c == RP_GATHER_AT) gather(rnext, lh);      // the next tile's first block
+                    if (fp == 0 && c == RP_GATHER_AT) gather(gA, rnext, lh);  // the next tile's first block
                     if (fp > 0 && RP_S1E) { if (c < 4) put4(po0, fp - 2, c); else put4(po1, fp - 1, c - 4); }
                     RR_SB();
                     b0h = n0h; b0l = n0l; b1h = n1h; b1l = n1l;
@@ -689,8 +708,8 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
 #ifdef RR_ABL_NOSTORE
                     asm volatile("" :: "v"(max(__float_as_int(t[u]), lo_1)));
 #else
-                    __builtin_amdgcn_raw_buffer_store_b32((unsigned)max(__float_as_int(t[u]), lo_1), orow, voff_lane,
-                                                          (((r + u) & 3) + 8 * ((r + u) >> 2)) * (32 * WB * 4) + 32 * fbn * 4, RP_STORE_AUX);    // (row / block offset: scalar)
+                    __builtin_amdgcn_raw_buffer_store_b32((unsigned)max(__float_as_int(t[u]), lo_1), orow, voff_lane + ((r + u) & 3) * (32 * WB * 4) + 32 * fbn * 4,
+                                                          sbase[(r + u) >> 2], RP_STORE_AUX);    // (row 8 q + r': 8 rows = 4096 bytes -> the held base q, the rest an immediate)
 #endif
             }
         };
@@ -726,7 +745,7 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
                     RR_MFH(Hh[c], b0h, o0);
                     RR_MFH(Hh[c], b1h, o1);
                     if (fp == 0 && c + 1 < NKS) hsplit(c + 1);
-                    if (fp == 0 && c == RP_GATHER_AT) gather(rnext, lh);      // the next tile's first block
+                    if (fp == 0 && c == RP_GATHER_AT) gather(gA, rnext, lh);  // the next tile's first block
                     if (fp == 0 && c + 1 == NKS) {
                         int inv2l = __float_as_int(inv2);                    // (opaque here: the permutes would otherwise be issued in front of the stage and their results spilled)
                         asm volatile("" : "+v"(inv2l));
