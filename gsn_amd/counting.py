@@ -11,7 +11,7 @@ Everything routes through ``gsn_count_hip`` in libgsn_hip.so.  No CPU fallback: 
 
 Graphs the LDS-resident kernel refuses (more than 768 vertices, tables beyond its LDS, 65 535 columns per graph) go to the sparse kernel
 (``gsn_count_sparse_hip``, csrc/count_sparse.hip): :func:`count_batch` / :func:`counts2ids_batch` on request (``large="sparse"``), the
-per-graph drop-ins always.
+per-graph drop-ins always.  Undirected plans and directed ones (``directed=True``: vertex counts) alike.
 """
 from __future__ import annotations
 
@@ -89,8 +89,8 @@ def count_batch(plan: CountPlan, node_ptr, edge_ptr, edge_index, ids_are_global=
     ``large``: what becomes of a launch the LDS-resident kernel refuses for its size (a graph of more than 768 vertices, tables beyond
     160 KiB of LDS, 65 535 columns per graph).  ``"refuse"`` (default): :class:`GsnError`.  ``"sparse"``: the sparse kernel
     (``gsn_count_sparse_hip``: sorted neighbour lists in HBM, one lane per rooted search) counts the launch -- at once when ``max_nodes``
-    exceeds 768, else after ``gsn_count_hip`` has refused.  Plain counts only: with ``encode`` it is a ``ValueError``; directed plans
-    are refused by the sparse kernel.
+    exceeds 768, else after ``gsn_count_hip`` has refused.  Plain counts only: with ``encode`` it is a ``ValueError``.  Directed plans
+    (vertex mode) take the same route.
 
     ``encode=(n_classes, clamp)`` also returns the one-hot encoded identifiers the GSN layers consume (the reference's
     ``DiscreteEmbedding('one_hot_encoder')`` over the counts, utils_graph_learning.py:170-187) straight from the kernel
@@ -181,8 +181,8 @@ def count_batch(plan: CountPlan, node_ptr, edge_ptr, edge_index, ids_are_global=
                     rc = _abi.lib().gsn_count_hip(*common, _abi.current_stream())
                     pack_codes_later = True
             elif enc is None:
-                rc = -2 if (large == "sparse" and int(max_nodes) > 768 and not plan.directed) else _abi.lib().gsn_count_hip(*common, _abi.current_stream())
-                if rc == -2 and large == "sparse" and not plan.directed:
+                rc = -2 if (large == "sparse" and int(max_nodes) > 768) else _abi.lib().gsn_count_hip(*common, _abi.current_stream())
+                if rc == -2 and large == "sparse":
                     # GSN_E_UNSUPPORTED of a plain count is a size reason (vertices, columns, LDS): the sparse kernel has no such limit
                     span = torch.stack([node_ptr_d[-1] - node_ptr_d[0], edge_ptr_d[-1] - edge_ptr_d[0]]).tolist()
                     ws_bytes = _abi.lib().gsn_count_sparse_workspace_bytes(int(span[0]), int(span[1]), plan.n_cols)
@@ -356,12 +356,6 @@ def _directed_of(pats, directed):
     return directed
 
 
-def _large_for(plan):
-    """The per-graph drop-ins take graphs of any size, as the reference does: what the LDS-resident kernel refuses goes to the sparse
-    kernel.  Directed plans have no sparse kernel: they keep the LDS kernel's refusal and its message."""
-    return "refuse" if plan.directed else "sparse"
-
-
 def _single_graph(edge_index, num_nodes):
     ei = edge_index if isinstance(edge_index, torch.Tensor) else torch.as_tensor(np.asarray(edge_index))
     ei = ei.to(torch.int64)
@@ -382,7 +376,7 @@ def subgraph_isomorphism_vertex_counts(edge_index, **kwargs):
     directed = _directed_of([sg], kwargs.get("directed", False))
     plan = CountPlan.get([sg.edge_list], "vertex", induced, False, directed)
     ei, n, E = _single_graph(edge_index, num_nodes)
-    out, _ = count_batch(plan, [0, n], [0, E], ei, ids_are_global=False, max_nodes=n, max_edges=E, large=_large_for(plan))
+    out, _ = count_batch(plan, [0, n], [0, E], ei, ids_are_global=False, max_nodes=n, max_edges=E, large="sparse")
     return out[:int(num_nodes)].cpu().to(torch.float64)
 
 
@@ -436,7 +430,7 @@ def subgraph_counts2ids(count_fn, data, subgraph_dicts, subgraph_params):
     dirorb = any(p.directed_orbits for p in pats) if mode == "edge" else False
     plan = CountPlan.get([p.edge_list for p in pats], mode, subgraph_params["induced"], dirorb, directed)
     e_cpu, n, E = _single_graph(edge_index, num_nodes)
-    out, _ = count_batch(plan, [0, n], [0, E], e_cpu, ids_are_global=False, max_nodes=n, max_edges=E, large=_large_for(plan))
+    out, _ = count_batch(plan, [0, n], [0, E], e_cpu, ids_are_global=False, max_nodes=n, max_edges=E, large="sparse")
     ids = out[:num_nodes] if mode == "vertex" else out
     if mode == "edge" and any(getattr(p, "line_graph_orbits", False) for p in pats):
         cols, blocks = 0, []

@@ -6,12 +6,15 @@
 //   set-up   sparse_mark_kernel    status words of the processed graphs, their pointers checked, rows -> graph
 //            sparse_check_kernel   every endpoint inside its graph (else GSN_ST_BAD_INDEX on the graph), the largest id per graph
 //            sparse_keys_kernel    per column the arcs (u, v) and (v, u) as 64-bit keys u << 32 | v -- either direction of a column makes the
-//                                  edge; self loops, columns of a bad graph and of graphs outside the launch become an end marker
+//                                  edge; self loops, columns of a bad graph and of graphs outside the launch become an end marker.
+//                                  A directed plan: column (u, v) is the arc u -> v only -- keys u << 32 | v (row u: out-neighbours) and
+//                                  (nv + v) << 32 | u (row nv + v: in-neighbours of v); the end marker is row 2 nv
 //            rocPRIM               device radix sort of the keys, then unique: parallel columns merged, lists strictly increasing
 //            sparse_csr_kernel     row_ptr by binary search over the sorted keys, nbr = their low halves
 //            sparse_arc_kernel     edge mode: per arc slot the LAST column that holds that direction (utils_graph_processing.py:142-144)
-//   search   sparse_search_kernel  persistent waves; lanes pull (output column, row) cells from one global counter with a wave-aggregated
-//                                  atomic; every cell is written by exactly one lane, no atomics on counts: deterministic
+//   search   sparse_search_kernel  <DIR>: undirected / directed plans (vertex mode only: there are no directed edge counts).  Persistent
+//                                  waves; lanes pull (output column, row) cells from one global counter with a wave-aggregated atomic;
+//                                  every cell is written by exactly one lane, no atomics on counts: deterministic
 // Vertices and columns are numbered from the first pointer of the launch (node_ptr[0], edge_ptr[0]), 32 bits each.  The launcher reads
 // those two and the two last pointers back (one stream synchronisation): the launch cannot be captured into a graph.
 #include <hip/hip_runtime.h>
@@ -45,7 +48,7 @@ SparseLayout sparse_layout(int64_t nv, int64_t ec) {
     L.keys_b = o; o += up256(arcs * 8 + 8);
     L.nbr = o; o += up256(arcs * 4 + 4);
     L.arc_col = o; o += up256(arcs * 4 + 4);
-    L.row_ptr = o; o += up256((nv + 2) * 4);
+    L.row_ptr = o; o += up256((2 * nv + 2) * 4);                         // (two row sets, out and in, when the plan is directed)
     L.row_graph = o; o += up256(rows * 4 + 4);
     L.vmax = o; o += up256((nv + 1) * 4);
     L.misc = o; o += 256;
@@ -56,11 +59,12 @@ SparseLayout sparse_layout(int64_t nv, int64_t ec) {
 
 struct SparseArgs {
     const uint32_t *plan;
-    int mode, n_cols, sym, ids_are_global;
+    int mode, n_cols, sym, ids_are_global, directed;
     const int64_t *node_ptr, *edge_ptr, *src, *dst;
     const int32_t *graph_ids;
     int64_t n_graphs;
     int64_t n0, e0, nv, ec;            // first vertex / column of the launch, their numbers
+    int64_t nr;                        // rows of row_ptr: nv, or 2 nv for a directed plan (row nv + v: the in-neighbours of v)
     int64_t *out;
     int32_t *status;
     uint64_t *keys_a, *keys_b;
@@ -83,7 +87,7 @@ __device__ __forceinline__ bool graph_ranges(const SparseArgs &a, int64_t g, int
 }
 
 __global__ __launch_bounds__(SP_T) void sparse_fill_kernel(SparseArgs a) {
-    const uint64_t endmark = (uint64_t)a.nv << 32;
+    const uint64_t endmark = (uint64_t)a.nr << 32;
     const int64_t stride = (int64_t)gridDim.x * SP_T;
     for (int64_t i = (int64_t)blockIdx.x * SP_T + threadIdx.x; i < 2 * a.ec; i += stride) a.keys_a[i] = endmark;
     const int64_t rows = a.mode == GSN_MODE_EDGE ? a.ec : a.nv;
@@ -141,15 +145,15 @@ __global__ __launch_bounds__(SP_T) void sparse_keys_kernel(SparseArgs a) {
         if (u == v) continue;
         const uint64_t gu = (uint64_t)(v0 + u), gv = (uint64_t)(v0 + v);
         a.keys_a[2 * c] = gu << 32 | gv;
-        a.keys_a[2 * c + 1] = gv << 32 | gu;
+        a.keys_a[2 * c + 1] = a.directed ? ((uint64_t)a.nv + gv) << 32 | gu : gv << 32 | gu;      // directed: u joins the in-list of v
     }
 }
 
-// keys: the sorted, duplicate-free arcs, *n_unique of them, the end marker (vertex nv) last when any slot held it
+// keys: the sorted, duplicate-free arcs, *n_unique of them, the end marker (row nr) last when any slot held it
 __global__ __launch_bounds__(SP_T) void sparse_csr_kernel(SparseArgs a, const uint64_t *keys) {
     const int64_t nk = (int64_t)*a.n_unique;
     const int64_t stride = (int64_t)gridDim.x * SP_T;
-    for (int64_t v = (int64_t)blockIdx.x * SP_T + threadIdx.x; v <= a.nv; v += stride) {
+    for (int64_t v = (int64_t)blockIdx.x * SP_T + threadIdx.x; v <= a.nr; v += stride) {
         const uint64_t want = (uint64_t)v << 32;
         int64_t lo = 0, hi = nk;
         while (lo < hi) {
@@ -183,11 +187,14 @@ __global__ __launch_bounds__(SP_T) void sparse_arc_kernel(SparseArgs a) {
 constexpr int SP_PULL_BATCH = 8;      // idle lanes are refilled when this many wait, or when no lane of the wave is inside a search
 
 // One wave per workgroup.  A lane is idle, or owns one cell: the plans of its column run one after the other, a turn of the walk per trip.
+// DIR: a directed plan (vertex mode): a fifth state field for the in-masks, the longer plan stride, in-lists at rows nv + v.
+template <bool DIR>
 __global__ __launch_bounds__(64) void sparse_search_kernel(SparseArgs a) {
-    __shared__ uint32_t st_all[SP_FIELDS * SP_LEVELS * 64];
+    __shared__ uint32_t st_all[(DIR ? SP_FIELDS_DIRECTED : SP_FIELDS) * SP_LEVELS * 64];
+    constexpr int stride = DIR ? PLAN_STRIDE_DIRECTED : PLAN_STRIDE_WORDS;
     const int lane = threadIdx.x;
     uint32_t *st = st_all + lane;
-    const bool edge_mode = a.mode == GSN_MODE_EDGE;
+    const bool edge_mode = !DIR && a.mode == GSN_MODE_EDGE;
     const int64_t rows = edge_mode ? a.ec : a.nv;
     const unsigned long long n_cells = (unsigned long long)rows * (unsigned long long)a.n_cols;
     const uint32_t *col_ptr = a.plan + PLAN_HEADER_WORDS;
@@ -196,6 +203,7 @@ __global__ __launch_bounds__(64) void sparse_search_kernel(SparseArgs a) {
     const uint64_t lane_lt = (1ull << lane) - 1ull;
 
     SparseGraph gr{a.row_ptr, a.nbr, 0u, 0u};
+    if (DIR) gr.in_base = (uint32_t)a.nv;
     SparseLane s;
     s.plan = plans; s.k = 0; s.nfix = 0; s.tm = 0; s.tl = -1; s.l = -1; s.enter = false; s.cnt = 0;
     bool has = false, exhausted = false, rev_missing = false;
@@ -256,9 +264,9 @@ __global__ __launch_bounds__(64) void sparse_search_kernel(SparseArgs a) {
         }
         if (has) {
             if (s.l < 0) {
-                if (p_i < p_e) { sp_begin(s, plans + (size_t)p_i * PLAN_STRIDE_WORDS, r0, r1, st, 64); ++p_i; }
+                if (p_i < p_e) { sp_begin(s, plans + (size_t)p_i * stride, r0, r1, st, 64); ++p_i; }
             } else {
-                sp_step(gr, s, st, 64);
+                sp_step<DIR>(gr, s, st, 64);
             }
             if (s.l < 0 && p_i >= p_e) {                         // the cell's last plan ended in this trip (or it had none)
                 const int64_t rbase = edge_mode ? a.e0 : a.n0;
@@ -297,8 +305,9 @@ extern "C" int gsn_count_sparse_hip(const uint32_t *plan_host, const uint32_t *p
     if (!plan_host || !plan_dev || plan_words < PLAN_HEADER_WORDS || plan_host[0] != PLAN_MAGIC)
         return set_error(GSN_E_INVALID, "gsn_count_sparse_hip: not a plan table (build it with gsn_count_plan_build)");
     if (!node_ptr || !edge_ptr || !out || !status || !workspace) return set_error(GSN_E_INVALID, "gsn_count_sparse_hip: null pointer argument");
-    if (plan_host[6] & 2u)
-        return set_error(GSN_E_UNSUPPORTED, "gsn_count_sparse_hip: directed plans are outside the sparse kernel (graphs of <= 768 vertices: gsn_count_hip)");
+    const bool directed = (plan_host[6] & 2u) != 0;
+    if (directed && plan_host[1] != (uint32_t)GSN_MODE_VERTEX)
+        return set_error(GSN_E_UNSUPPORTED, "gsn_count_sparse_hip: directed plans are vertex-mode plans (no directed edge counts)");
     if (!graph_ids) n_items = n_graphs;
     if (n_graphs <= 0 || n_items <= 0) return GSN_OK;
     if (n_items >= ((int64_t)1 << 31)) return set_error(GSN_E_UNSUPPORTED, "gsn_count_sparse_hip: %lld graphs in one launch", (long long)n_items);
@@ -327,10 +336,10 @@ extern "C" int gsn_count_sparse_hip(const uint32_t *plan_host, const uint32_t *p
     SparseArgs a{};
     a.plan = plan_dev; a.mode = (int)plan_host[1]; a.n_cols = (int)plan_host[4];
     a.sym = (a.mode == GSN_MODE_EDGE && (plan_host[6] & 1u) == 0) ? 1 : 0;
-    a.ids_are_global = ids_are_global;
+    a.ids_are_global = ids_are_global; a.directed = directed ? 1 : 0;
     a.node_ptr = node_ptr; a.edge_ptr = edge_ptr; a.src = edge_index; a.dst = edge_index ? edge_index + edge_row_stride : nullptr;
     a.graph_ids = graph_ids; a.n_graphs = n_graphs;
-    a.n0 = ends[0]; a.e0 = ends[2]; a.nv = nv; a.ec = ec;
+    a.n0 = ends[0]; a.e0 = ends[2]; a.nv = nv; a.ec = ec; a.nr = directed ? 2 * nv : nv;
     a.out = out; a.status = status;
     a.keys_a = reinterpret_cast<uint64_t *>(ws + L.keys_a); a.keys_b = reinterpret_cast<uint64_t *>(ws + L.keys_b);
     a.nbr = reinterpret_cast<uint32_t *>(ws + L.nbr); a.arc_col = reinterpret_cast<int32_t *>(ws + L.arc_col);
@@ -338,7 +347,7 @@ extern "C" int gsn_count_sparse_hip(const uint32_t *plan_host, const uint32_t *p
     a.vmax = reinterpret_cast<uint32_t *>(ws + L.vmax);
     a.cell_counter = reinterpret_cast<unsigned long long *>(ws + L.misc);
     a.n_unique = reinterpret_cast<unsigned int *>(ws + L.misc + 8);
-    if (a.n_cols < 1 || plan_words < (int64_t)plan_host[7] + (int64_t)plan_host[3] * PLAN_STRIDE_WORDS)
+    if (a.n_cols < 1 || plan_words < (int64_t)plan_host[7] + (int64_t)plan_host[3] * plan_stride(plan_host[6]))
         return set_error(GSN_E_INVALID, "gsn_count_sparse_hip: plan table shorter than its header says");
 
     const int64_t arcs = 2 * ec, rows = a.mode == GSN_MODE_EDGE ? ec : nv;
@@ -354,9 +363,9 @@ extern "C" int gsn_count_sparse_hip(const uint32_t *plan_host, const uint32_t *p
     if (arcs > 0) {
         hipLaunchKernelGGL(sparse_keys_kernel, per_graph, dim3(SP_T), 0, st, a);
         if (int rc = launch_check("sparse_keys_kernel launch")) return rc;
-        // keys u << 32 | v with u <= nv: the bits above those of nv are zero
+        // keys row << 32 | v with row <= nr (the end marker): the bits above those of nr are zero
         unsigned end_bit = 33;
-        while (end_bit < 64 && ((uint64_t)nv >> (end_bit - 32)) != 0) ++end_bit;
+        while (end_bit < 64 && ((uint64_t)a.nr >> (end_bit - 32)) != 0) ++end_bit;
         rocprim::double_buffer<uint64_t> keys(a.keys_a, a.keys_b);
         size_t need_sort = 0, need_unique = 0;
         SP_HIP(rocprim::radix_sort_keys(nullptr, need_sort, keys, (size_t)arcs, 0u, end_bit, st), "rocprim::radix_sort_keys (size)");
@@ -371,7 +380,7 @@ extern "C" int gsn_count_sparse_hip(const uint32_t *plan_host, const uint32_t *p
         SP_HIP(rocprim::unique(ws + L.temp, tb, in, uniq, a.n_unique, (size_t)arcs, rocprim::equal_to<uint64_t>(), st), "rocprim::unique");
         sorted = uniq;
     }
-    hipLaunchKernelGGL(sparse_csr_kernel, dim3(blocks_for(arcs > nv + 1 ? arcs : nv + 1)), dim3(SP_T), 0, st, a, sorted);
+    hipLaunchKernelGGL(sparse_csr_kernel, dim3(blocks_for(arcs > a.nr + 1 ? arcs : a.nr + 1)), dim3(SP_T), 0, st, a, sorted);
     if (int rc = launch_check("sparse_csr_kernel launch")) return rc;
     if (a.mode == GSN_MODE_EDGE && arcs > 0) {
         hipLaunchKernelGGL(sparse_arc_kernel, per_graph, dim3(SP_T), 0, st, a);
@@ -381,7 +390,8 @@ extern "C" int gsn_count_sparse_hip(const uint32_t *plan_host, const uint32_t *p
         // persistent waves: at most 16 one-wave workgroups per CU's worth of the chip, fewer when the cells are few
         const int64_t cells = rows * (int64_t)a.n_cols, want = (cells + 63) / 64;
         const unsigned grid = (unsigned)(want < 1 ? 1 : (want > 256 * 16 ? 256 * 16 : want));
-        hipLaunchKernelGGL(sparse_search_kernel, dim3(grid), dim3(64), 0, st, a);
+        if (directed) hipLaunchKernelGGL(sparse_search_kernel<true>, dim3(grid), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL(sparse_search_kernel<false>, dim3(grid), dim3(64), 0, st, a);
         if (int rc = launch_check("sparse_search_kernel launch")) return rc;
     }
     return GSN_OK;

@@ -1,8 +1,8 @@
 // Rooted subgraph search over sorted neighbour lists: the arithmetic core of the sparse counting kernel (count_sparse.hip), for the graphs
 // that the LDS-resident kernel (count.hip / count_core.h) refuses: more than 768 vertices, tables beyond 160 KiB of LDS, 65 535 columns.
 //
-// Shared between the HIP kernel and a host-side harness used ONLY by tests (tests/sparse_harness.cpp compiles this header with g++; it is
-// not a product fallback).  Everything is integer arithmetic; results are exact.
+// Shared between the HIP kernel and host-side harnesses used ONLY by tests (tests/sparse_harness.cpp and tests/sparse_directed_harness.cpp
+// compile this header with g++; they are not a product fallback).  Everything is integer arithmetic; results are exact.
 //
 // The graph is a CSR of neighbour lists: the neighbours of vertex v are nbr[row_ptr[v] .. row_ptr[v + 1]), 32-bit vertex ids, STRICTLY
 // increasing -- no duplicate entries and no self loops (the set-up pass, or the harness, removes both).  Vertex ids are whatever the
@@ -12,7 +12,22 @@
 // adj | nonadj << 8 | gt << 16 | lt << 24 of levels n_fixed .. k - 1 are read: they define the result completely.  min_degree, the distance
 // bytes and the cores of the LDS kernel only prune work and are ignored here.  Closed forms of the plan's tail (patterns.cpp:
 // plan_tail_mode) that are honoured because they are cheap on lists: mode 2 (twin levels: C(|C|, r)) and mode 1 (independent last levels:
-// |C1| |C2| - |C1 & C2|); mode 3 (chain) runs the generic search.  Directed plans are not handled (the launcher refuses them).
+// |C1| |C2| - |C1 & C2|); mode 3 (chain) runs the generic search.
+//
+// Directed plans (header[6] & 2, vertex mode; the functions' DIR = true).  The graph has two lists per vertex, both strictly increasing and
+// without self loops: row v of the CSR holds the OUT-neighbours of v, row in_base + v its IN-neighbours (in_base = 0: an undirected graph,
+// one list per vertex), so sp_find serves both by an offset.  Level masks:
+//   plan[2 + l]                  adjacency bit j: the image of level l is an OUT-neighbour of f_j (pattern arc j -> l); non-adjacency bit j:
+//                                it is not; gt / lt as in an undirected plan
+//   plan[PLAN_STRIDE_WORDS + l]  in_adj | in_nonadj << 8: the same for IN-neighbours of f_j (pattern arc l -> j)
+// and the plans lie plan_stride(header[6]) = PLAN_STRIDE_DIRECTED words apart.  A level takes its candidates from the shortest list among
+// the out-lists named by the adjacency mask and the in-lists named by the in-adjacency mask, and checks every remaining bit of both words by
+// binary search in the matching list; with neither mask it walks the graph's vertices.  Closed-form tails: modes 1 and 2 are honoured, with
+// the candidate sets counted under both words.  Their derivations hold because the plan compiler only emits them for a directed plan when
+// they do: mode 1 when NEITHER word of the last level names level k - 2 (patterns.cpp: plan_tail_mode, in_ref), mode 2 when the twin levels
+// are equal in BOTH words and neither word of one names the other (twin_link: level_in[b] == level_in[a], in_ref) -- the two candidate sets
+// are then fixed once the levels above are placed, exactly as in the undirected case; mode 3 is never emitted for a directed plan.  The
+// oracle decides: tests/test_count_sparse_directed_cpu.py compares every cell.
 //
 // The search is an iterative depth-first walk (no recursion).  Level l takes its candidates from the neighbour list of ONE earlier image named by its
 // adjacency mask (the anchor: the one with the shortest list), rejects a candidate equal to an earlier image, checks the other adjacency
@@ -22,7 +37,9 @@
 //
 // Per-lane state: for each level 0 .. 7 the image, the cursor and the end of its candidate list, and the masks still to check (the
 // level's masks without the anchor's adjacency bit): SP_FIELDS * SP_LEVELS words at st[(field * SP_LEVELS + level) * ss] -- ss = 1 for a
-// plain array (host), ss = the lane count with st pointing at the lane's own word of a lane-interleaved LDS array (device).
+// plain array (host), ss = the lane count with st pointing at the lane's own word of a lane-interleaved LDS array (device).  A directed
+// search keeps the in-masks still to check in a fifth field (SP_CHK_IN; SP_FIELDS_DIRECTED * SP_LEVELS words): SP_CHK has no bit free, and
+// an undirected search neither reads nor reserves the field.
 #pragma once
 
 #include <stdint.h>
@@ -32,18 +49,19 @@
 namespace gsn {
 
 constexpr int SP_LEVELS = 8;          // levels that hold an image or a cursor: 0 .. k - 2 with k <= GSN_KMAX = 9
-enum { SP_IMG = 0, SP_CUR = 1, SP_END = 2, SP_CHK = 3, SP_FIELDS = 4 };
+enum { SP_IMG = 0, SP_CUR = 1, SP_END = 2, SP_CHK = 3, SP_FIELDS = 4, SP_CHK_IN = 4, SP_FIELDS_DIRECTED = 5 };
 static_assert(GSN_KMAX - 1 <= SP_LEVELS, "the last level is counted, every earlier one has a slot");
 
 struct SparseGraph {
-    const uint32_t *row_ptr;   // [n + 1] over the caller's vertex numbering
+    const uint32_t *row_ptr;   // [n + 1] over the caller's vertex numbering; directed: [in_base + n + 1]
     const uint32_t *nbr;       // strictly increasing within a row
     uint32_t v_lo, v_hi;       // the vertices of the graph the roots lie in (walked only by a level without an adjacency mask)
+    uint32_t in_base = 0;      // directed: row in_base + v holds the in-neighbours of v, row v its out-neighbours
 };
 
 #define GSN_SP(F, L) st[((F) * SP_LEVELS + (L)) * ss]
 
-// position of b in the list of a, or -1
+// position of b in row a, or -1
 GSN_HD int64_t sp_find(const SparseGraph &g, uint32_t a, uint32_t b) {
     uint32_t lo = g.row_ptr[a], hi = g.row_ptr[a + 1];
     while (lo < hi) {
@@ -55,8 +73,9 @@ GSN_HD int64_t sp_find(const SparseGraph &g, uint32_t a, uint32_t b) {
     return -1;
 }
 
-// does v satisfy the masks `chk` against the images of the levels they name?
-GSN_HD bool sp_masks_hold(const SparseGraph &g, const uint32_t *st, int ss, uint32_t chk, uint32_t v) {
+// does v satisfy the masks `chk` (and, directed, the in-masks `chk_in`) against the images of the levels they name?
+template <bool DIR = false>
+GSN_HD bool sp_masks_hold(const SparseGraph &g, const uint32_t *st, int ss, uint32_t chk, uint32_t chk_in, uint32_t v) {
     uint32_t m = chk & 0xffu;
     while (m) {
         const int j = ctz64(m);
@@ -68,6 +87,20 @@ GSN_HD bool sp_masks_hold(const SparseGraph &g, const uint32_t *st, int ss, uint
         const int j = ctz64(m);
         m &= m - 1u;
         if (sp_find(g, GSN_SP(SP_IMG, j), v) >= 0) return false;
+    }
+    if (DIR) {
+        m = chk_in & 0xffu;
+        while (m) {
+            const int j = ctz64(m);
+            m &= m - 1u;
+            if (sp_find(g, g.in_base + GSN_SP(SP_IMG, j), v) < 0) return false;
+        }
+        m = (chk_in >> 8) & 0xffu;
+        while (m) {
+            const int j = ctz64(m);
+            m &= m - 1u;
+            if (sp_find(g, g.in_base + GSN_SP(SP_IMG, j), v) >= 0) return false;
+        }
     }
     m = (chk >> 16) & 0xffu;
     while (m) {
@@ -85,17 +118,21 @@ GSN_HD bool sp_masks_hold(const SparseGraph &g, const uint32_t *st, int ss, uint
 }
 
 // candidate of a level with the images of levels 0 .. nimg - 1 placed: distinct from all of them, and the masks hold
-GSN_HD bool sp_accept(const SparseGraph &g, const uint32_t *st, int ss, uint32_t chk, int nimg, uint32_t v) {
+template <bool DIR = false>
+GSN_HD bool sp_accept(const SparseGraph &g, const uint32_t *st, int ss, uint32_t chk, uint32_t chk_in, int nimg, uint32_t v) {
     for (int j = 0; j < nimg; ++j)
         if (GSN_SP(SP_IMG, j) == v) return false;
-    return sp_masks_hold(g, st, ss, chk, v);
+    return sp_masks_hold<DIR>(g, st, ss, chk, chk_in, v);
 }
 
-// the candidate list of a level with masks `desc`: positions cur .. end of nbr (or vertex ids, when the level has no adjacency mask),
-// and the masks that remain to be checked per candidate
-GSN_HD void sp_open(const SparseGraph &g, const uint32_t *st, int ss, uint32_t desc, uint32_t &cur, uint32_t &end, uint32_t &chk) {
+// the candidate list of a level with masks `desc` (directed: and in-masks `din`): positions cur .. end of nbr (or vertex ids, when the
+// level has no adjacency mask in either word), and the masks that remain to be checked per candidate
+template <bool DIR = false>
+GSN_HD void sp_open(const SparseGraph &g, const uint32_t *st, int ss, uint32_t desc, uint32_t din, uint32_t &cur, uint32_t &end, uint32_t &chk,
+                    uint32_t &chk_in) {
     uint32_t m = desc & 0xffu;
-    if (!m) { cur = g.v_lo; end = g.v_hi; chk = desc; return; }
+    chk_in = din;
+    if (!m && !(DIR && (din & 0xffu))) { cur = g.v_lo; end = g.v_hi; chk = desc; return; }
     int best = -1;
     uint32_t blen = 0, bcur = 0;
     while (m) {
@@ -104,19 +141,35 @@ GSN_HD void sp_open(const SparseGraph &g, const uint32_t *st, int ss, uint32_t d
         const uint32_t a = GSN_SP(SP_IMG, j), lo = g.row_ptr[a], len = g.row_ptr[a + 1] - lo;
         if (best < 0 || len < blen) { best = j; blen = len; bcur = lo; }
     }
-    cur = bcur; end = bcur + blen; chk = desc & ~(1u << best);
+    if (DIR) {
+        m = din & 0xffu;
+        while (m) {
+            const int j = ctz64(m);
+            m &= m - 1u;
+            const uint32_t a = g.in_base + GSN_SP(SP_IMG, j), lo = g.row_ptr[a], len = g.row_ptr[a + 1] - lo;
+            if (best < 0 || len < blen) { best = 8 + j; blen = len; bcur = lo; }
+        }
+    }
+    cur = bcur; end = bcur + blen;
+    if (DIR && best >= 8) { chk = desc; chk_in = din & ~(1u << (best - 8)); }
+    else chk = desc & ~(1u << best);
 }
-GSN_HD uint32_t sp_at(const SparseGraph &g, uint32_t desc, uint32_t pos) { return (desc & 0xffu) ? g.nbr[pos] : pos; }
+template <bool DIR = false>
+GSN_HD uint32_t sp_at(const SparseGraph &g, uint32_t desc, uint32_t din, uint32_t pos) {
+    return ((desc & 0xffu) || (DIR && (din & 0xffu))) ? g.nbr[pos] : pos;
+}
 
-// number of candidates of a level with masks `desc` (images 0 .. nimg - 1 placed) that, with `both`, also satisfy the masks `desc2`
-GSN_HD uint64_t sp_count_level(const SparseGraph &g, const uint32_t *st, int ss, uint32_t desc, int nimg, bool both = false, uint32_t desc2 = 0) {
-    uint32_t cur, end, chk;
-    sp_open(g, st, ss, desc, cur, end, chk);
+// number of candidates of a level with masks `desc` / `din` (images 0 .. nimg - 1 placed) that, with `both`, also satisfy `desc2` / `din2`
+template <bool DIR = false>
+GSN_HD uint64_t sp_count_level(const SparseGraph &g, const uint32_t *st, int ss, uint32_t desc, uint32_t din, int nimg, bool both = false,
+                               uint32_t desc2 = 0, uint32_t din2 = 0) {
+    uint32_t cur, end, chk, chk_in;
+    sp_open<DIR>(g, st, ss, desc, din, cur, end, chk, chk_in);
     uint64_t c = 0;
     for (; cur < end; ++cur) {
-        const uint32_t v = sp_at(g, desc, cur);
-        if (!sp_accept(g, st, ss, chk, nimg, v)) continue;
-        if (both && !sp_masks_hold(g, st, ss, desc2, v)) continue;
+        const uint32_t v = sp_at<DIR>(g, desc, din, cur);
+        if (!sp_accept<DIR>(g, st, ss, chk, chk_in, nimg, v)) continue;
+        if (both && !sp_masks_hold<DIR>(g, st, ss, desc2, din2, v)) continue;
         ++c;
     }
     return c;
@@ -149,15 +202,16 @@ GSN_HD void sp_begin(SparseLane &s, const uint32_t *plan, uint32_t r0, uint32_t 
     s.enter = true;
 }
 
+template <bool DIR = false>
 GSN_HD void sp_step(const SparseGraph &g, SparseLane &s, uint32_t *st, int ss) {
     const int l = s.l, k = s.k;
-    const uint32_t desc = s.plan[2 + l];
+    const uint32_t desc = s.plan[2 + l], din = DIR ? s.plan[PLAN_STRIDE_WORDS + l] : 0u;
     if (s.enter) {
         s.enter = false;
         if (l == k - 1) {
-            s.cnt += sp_count_level(g, st, ss, desc, l);
+            s.cnt += sp_count_level<DIR>(g, st, ss, desc, din, l);
         } else if (s.tm == 2 && l == s.tl) {     // r twin levels: any r of the candidates, in one order
-            const uint64_t n1 = sp_count_level(g, st, ss, desc, l);
+            const uint64_t n1 = sp_count_level<DIR>(g, st, ss, desc, din, l);
             const int r = 2 + (int)(s.plan[1] >> 30);
             if (n1 >= (uint64_t)r) {
                 uint64_t c = 1;
@@ -165,13 +219,14 @@ GSN_HD void sp_step(const SparseGraph &g, SparseLane &s, uint32_t *st, int ss) {
                 s.cnt += c;
             }
         } else if (s.tm == 1 && l == s.tl) {     // the last level's masks do not name level k - 2: pairs minus the coinciding ones
-            const uint32_t d2 = s.plan[2 + k - 1];
-            const uint64_t n1 = sp_count_level(g, st, ss, desc, l);
-            if (n1) s.cnt += n1 * sp_count_level(g, st, ss, d2, l) - sp_count_level(g, st, ss, desc, l, true, d2);
+            const uint32_t d2 = s.plan[2 + k - 1], d2in = DIR ? s.plan[PLAN_STRIDE_WORDS + k - 1] : 0u;
+            const uint64_t n1 = sp_count_level<DIR>(g, st, ss, desc, din, l);
+            if (n1) s.cnt += n1 * sp_count_level<DIR>(g, st, ss, d2, d2in, l) - sp_count_level<DIR>(g, st, ss, desc, din, l, true, d2, d2in);
         } else {
-            uint32_t cur, end, chk;
-            sp_open(g, st, ss, desc, cur, end, chk);
+            uint32_t cur, end, chk, chk_in;
+            sp_open<DIR>(g, st, ss, desc, din, cur, end, chk, chk_in);
             GSN_SP(SP_CUR, l) = cur; GSN_SP(SP_END, l) = end; GSN_SP(SP_CHK, l) = chk;
+            if (DIR) GSN_SP(SP_CHK_IN, l) = chk_in;
             return;
         }
         s.l = l - 1 < s.nfix ? -1 : l - 1;       // counted: back to the level above
@@ -183,28 +238,32 @@ GSN_HD void sp_step(const SparseGraph &g, SparseLane &s, uint32_t *st, int ss) {
         return;
     }
     GSN_SP(SP_CUR, l) = cur + 1;
-    const uint32_t v = sp_at(g, desc, cur);
-    if (!sp_accept(g, st, ss, GSN_SP(SP_CHK, l), l, v)) return;
+    const uint32_t v = sp_at<DIR>(g, desc, din, cur);
+    if (!sp_accept<DIR>(g, st, ss, GSN_SP(SP_CHK, l), DIR ? GSN_SP(SP_CHK_IN, l) : 0u, l, v)) return;
     GSN_SP(SP_IMG, l) = v;
     s.l = l + 1;
     s.enter = true;
 }
 
 // the number of maps of one plan
+template <bool DIR = false>
 GSN_HD uint64_t sp_search(const SparseGraph &g, const uint32_t *plan, uint32_t r0, uint32_t r1, uint32_t *st, int ss) {
     SparseLane s;
     s.cnt = 0; s.tm = 0; s.tl = -1;
     sp_begin(s, plan, r0, r1, st, ss);
-    while (s.l >= 0) sp_step(g, s, st, ss);
+    while (s.l >= 0) sp_step<DIR>(g, s, st, ss);
     return s.cnt;
 }
 
-// one cell: the plans col_ptr[col] .. col_ptr[col + 1] of the table all add to output column `col`
+// one cell: the plans col_ptr[col] .. col_ptr[col + 1] of the table all add to output column `col`.  DIR must agree with the table's
+// header (table[6] & 2): it sets the plan stride and the size of st (SP_FIELDS_DIRECTED * SP_LEVELS words, else SP_FIELDS * SP_LEVELS)
+template <bool DIR = false>
 GSN_HD uint64_t sp_cell(const SparseGraph &g, const uint32_t *table, int col, uint32_t r0, uint32_t r1, uint32_t *st, int ss) {
+    constexpr int stride = DIR ? PLAN_STRIDE_DIRECTED : PLAN_STRIDE_WORDS;
     const uint32_t *col_ptr = table + PLAN_HEADER_WORDS;
     const uint32_t *plans = table + table[7];
     uint64_t cnt = 0;
-    for (uint32_t p = col_ptr[col]; p < col_ptr[col + 1]; ++p) cnt += sp_search(g, plans + (size_t)p * PLAN_STRIDE_WORDS, r0, r1, st, ss);
+    for (uint32_t p = col_ptr[col]; p < col_ptr[col + 1]; ++p) cnt += sp_search<DIR>(g, plans + (size_t)p * stride, r0, r1, st, ss);
     return cnt;
 }
 

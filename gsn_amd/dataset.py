@@ -6,7 +6,7 @@ What stays identical to the reference, graph by graph: the attributes each prepa
 ``identifiers`` int64 [rows, sum orbits] with columns in pattern order then orbit index -- utils_ids.py:7-29), the
 returned tuple, the ``.pt`` cache tuple ``(graphs, num_classes, orbit_partition_sizes)`` (utils.py:272-274) and
 ``downgrade_k`` slicing (utils.py:332-345).  Collation of the raw graphs is host-side numpy; the counts come from the
-HIP kernels (gsn_count_hip; gsn_count_sparse_hip for graphs of more than 768 vertices) -- there is no CPU counting path here.
+HIP kernels (gsn_count_hip; gsn_count_sparse_hip for graphs of more than 768 vertices, directed or not) -- there is no CPU counting path here.
 """
 from __future__ import annotations
 

@@ -146,8 +146,10 @@ int gsn_count_hip(const uint32_t *plan_host, const uint32_t *plan_dev, int64_t p
  * Statuses: GSN_ST_BAD_INDEX (an endpoint outside the graph, or the graph's pointers outside the launch's): that graph's rows are zero,
  * the other graphs are counted; GSN_ST_KEYERROR as gsn_count_hip.  Rows of graphs outside graph_ids are untouched.
  * Limits: vertices and columns are numbered from node_ptr[0] / edge_ptr[0] of the launch in 32 bits (< 2^31 - 1 vertices, <= 2^30 columns:
- * GSN_E_UNSUPPORTED beyond); directed plans (GSN_FLAG_DIRECTED) -> GSN_E_UNSUPPORTED; no fused encodings.  The call reads four
- * pointer entries back (one stream synchronisation), so it cannot be captured into a graph.  Deterministic: every cell has one writer. */
+ * GSN_E_UNSUPPORTED beyond); no fused encodings.  Directed plans (GSN_FLAG_DIRECTED) are vertex-mode plans, as for gsn_count_hip: every
+ * column (u, v) is the arc u -> v, antiparallel columns are two arcs, repeated columns merge, self loops drop out; a directed plan in edge
+ * mode -> GSN_E_UNSUPPORTED (there are no directed edge counts).  The call reads four pointer entries back (one stream synchronisation), so
+ * it cannot be captured into a graph.  Deterministic: every cell has one writer. */
 int gsn_count_sparse_hip(const uint32_t *plan_host, const uint32_t *plan_dev, int64_t plan_words, int64_t n_graphs,
                          const int64_t *node_ptr, const int64_t *edge_ptr, const int64_t *edge_index,
                          int64_t edge_row_stride, int ids_are_global, const int32_t *graph_ids, int64_t n_items,
@@ -155,7 +157,8 @@ int gsn_count_sparse_hip(const uint32_t *plan_host, const uint32_t *plan_dev, in
                          int64_t workspace_bytes, void *stream);
 /* Host: bytes of workspace for a launch that spans n_vertices_total = node_ptr[G] - node_ptr[0] vertices and n_columns_processed =
  * edge_ptr[G] - edge_ptr[0] columns (the launch's tables cover the whole span, also when graph_ids names a few of its graphs); n_cols =
- * the plan's output columns (no table depends on it today).  -1 beyond the 32-bit limits above. */
+ * the plan's output columns (no table depends on it today).  The size serves undirected and directed plans alike (the function takes no
+ * flag: the row table is sized for out- and in-lists always).  -1 beyond the 32-bit limits above. */
 int64_t gsn_count_sparse_workspace_bytes(int64_t n_vertices_total, int64_t n_columns_processed, int64_t n_cols);
 
 /* Counting with the identifier encoding fused into the kernel's output: what the reference does in two steps -- int64 counts
