@@ -915,29 +915,32 @@ extern "C" int gsn_wgrad_hip(int64_t m_rows, int64_t n_out, const float *grad_h,
     rows_per = (rows_per + WG_RB - 1) / WG_RB * WG_RB;
     a.rows_per_wg = rows_per;
     int64_t slabs = (m_rows + rows_per - 1) / rows_per;
-    trace("gsn wgrad: M %lld N %d K %d blocks %d%s slabs %lld x %lld rows\n", (long long)m_rows, (int)n_out, k, n_blocks, gathered ? " gathered" : "",
-                (long long)slabs, (long long)rows_per);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // one launch, and the trace line that names it (GSN_CHAIN_TRACE: one name per instantiation, so that a run under a switch shows which kernel it got)
+    auto go = [&](const char *name, void (*kernel)(WgradArgs), dim3 grid) {
+        trace("gsn wgrad: M %lld N %d K %d blocks %d%s slabs %lld x %lld rows %s\n", (long long)m_rows, (int)n_out, k, n_blocks, gathered ? " gathered" : "",
+                    (long long)slabs, (long long)rows_per, name);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, a);
+    };
     // GSN_WGRAD_FP32=1: the fp32-MFMA kernel (v_mfma_f32_32x32x2_f32), for A/B runs
     const bool fp32_kernel = sw_on(SW_WGRAD_FP32, false);
     if (fp32_kernel && !gathered)      // (gathered blocks: the bf16 kernel only)
-        hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)slabs, (unsigned)tn, (unsigned)tk), dim3(256), 0,
-                           reinterpret_cast<hipStream_t>(stream), a);
+        go("wgrad_kernel", wgrad_kernel, dim3((unsigned)slabs, (unsigned)tn, (unsigned)tk));
     else {
         a.tn = tn; a.tk = tk;
         const int64_t slab_groups = (slabs + 7) / 8;
         // GSN_WGRAD_PIPE: 0 = the kernel above for plain rows too; 4 / 5 / 6 = vector instructions asked for behind each MFMA (default 6; config-4 step on one box: off 19.71, 4: 19.43, 5: 19.22, 6: 19.06-19.21 ms)
         const int pipe_env = sw_int(SW_WGRAD_PIPE, 6), pipe = pipe_env == 1 ? 6 : pipe_env;
         const dim3 grid((unsigned)(slab_groups * tn * tk * 8));
-        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-        if (gathered && pipe) hipLaunchKernelGGL((wgrad_bf16_pipe_kernel<false, 6, true>), grid, dim3(256), 0, st, a);
-        else if (gathered) hipLaunchKernelGGL(wgrad_bf16_kernel<true>, grid, dim3(256), 0, st, a);
-        else if (pipe == 4 && n_blocks == 1) hipLaunchKernelGGL((wgrad_bf16_pipe_kernel<true, 4>), grid, dim3(256), 0, st, a);
-        else if (pipe == 4) hipLaunchKernelGGL((wgrad_bf16_pipe_kernel<false, 4>), grid, dim3(256), 0, st, a);
-        else if (pipe == 5 && n_blocks == 1) hipLaunchKernelGGL((wgrad_bf16_pipe_kernel<true, 5>), grid, dim3(256), 0, st, a);
-        else if (pipe == 5) hipLaunchKernelGGL((wgrad_bf16_pipe_kernel<false, 5>), grid, dim3(256), 0, st, a);
-        else if (pipe && n_blocks == 1) hipLaunchKernelGGL((wgrad_bf16_pipe_kernel<true, 6>), grid, dim3(256), 0, st, a);
-        else if (pipe) hipLaunchKernelGGL((wgrad_bf16_pipe_kernel<false, 6>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(wgrad_bf16_kernel<false>, dim3((unsigned)(slab_groups * tn * tk * 8)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+        if (gathered && pipe) go("wgrad_bf16_pipe_kernel<gather,6>", wgrad_bf16_pipe_kernel<false, 6, true>, grid);      // (at depth 4 / 5 too: one gather instantiation)
+        else if (gathered) go("wgrad_bf16_kernel<gather>", wgrad_bf16_kernel<true>, grid);
+        else if (pipe == 4 && n_blocks == 1) go("wgrad_bf16_pipe_kernel<single,4>", wgrad_bf16_pipe_kernel<true, 4>, grid);
+        else if (pipe == 4) go("wgrad_bf16_pipe_kernel<blocks,4>", wgrad_bf16_pipe_kernel<false, 4>, grid);
+        else if (pipe == 5 && n_blocks == 1) go("wgrad_bf16_pipe_kernel<single,5>", wgrad_bf16_pipe_kernel<true, 5>, grid);
+        else if (pipe == 5) go("wgrad_bf16_pipe_kernel<blocks,5>", wgrad_bf16_pipe_kernel<false, 5>, grid);
+        else if (pipe && n_blocks == 1) go("wgrad_bf16_pipe_kernel<single,6>", wgrad_bf16_pipe_kernel<true, 6>, grid);
+        else if (pipe) go("wgrad_bf16_pipe_kernel<blocks,6>", wgrad_bf16_pipe_kernel<false, 6>, grid);
+        else go("wgrad_bf16_kernel<plain>", wgrad_bf16_kernel<false>, grid);
     }
     return launch_check("wgrad_kernel");
 }
