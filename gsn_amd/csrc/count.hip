@@ -432,8 +432,15 @@ __device__ unsigned long long *g_count_prof2;  // [12] wave-level sums over the 
 // through the whole kernel (106 of them + spills before).  The launcher selects it when all of that holds (launch<>()).
 // CYC = L > 0 (with MOL): every column is a non-induced cycle of length <= L -- no plan table, candidate stack or distance tables in LDS,
 // and the task pool is one bitset path walk per searching row (count_core.h: cycle_walk) that yields the row's four cells at once.
-template <int W, int T, bool DIR, bool TAIL, bool MOL, int CYC = 0, class Args = CountArgs>
+// FL (CYC only): the flags that are the same for every workgroup of a launch, as a type.  CycAny tests them where they are used (scalar
+// loads and branches in every workgroup); CycKeys is the headline step's combination (gsn_count_encode_keys_side_hip on staged rows),
+// selected by the launcher when all of it holds: int64 rows staged in LDS as 16-bit counts, class indices taken from those counts, the
+// identifier masks the only encoded form (no fp32 rows, no fp16 pack).  Same body, the other arms are not compiled in.
+struct CycAny { static constexpr bool KEYS = false; };
+struct CycKeys { static constexpr bool KEYS = true; };
+template <int W, int T, bool DIR, bool TAIL, bool MOL, int CYC = 0, class FL = CycAny, class Args = CountArgs>
 __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, const int item, const int part, const int g, const int ng, const bool report) {
+    constexpr bool KEYS = CYC > 0 && FL::KEYS;
 #ifdef COUNT_PROF
     unsigned long long t_prev = __builtin_amdgcn_s_memtime();
 #endif
@@ -474,13 +481,21 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
     const int64_t rows64 = edge_mode ? E64 : n64;
     const int64_t row0 = edge_mode ? e0 : n0;
     const int n_cols = MOL ? 4 : a.n_cols;
-    const bool a_stage_out = a.stage_out != 0, a_sym = MOL || a.sym != 0, a_enc = MOL || a.enc_out != nullptr, a_enc_stage = MOL || a.enc_stage != 0;
-    const bool a_enc_from_counts = a.enc_from_counts != 0;
+    const bool a_stage_out = KEYS || a.stage_out != 0, a_sym = MOL || a.sym != 0, a_enc = MOL || a.enc_out != nullptr, a_enc_stage = MOL || a.enc_stage != 0;
+    const bool a_enc_from_counts = KEYS || a.enc_from_counts != 0;
     const int a_split = MOL ? 1 : a.split;
 
     // CYC: the zeros of an error path (a graph beyond the declared sizes, a bad index), a row per thread and trip: the same bytes as the
     // flat loops of the other instantiations without their 64-bit quotients, whose expansion was this instantiation's register peak
     auto zero_rows_cyc = [&](const int64_t nrows, const bool pack_always) {
+        if constexpr (KEYS) {                           // (the int64 rows and the masks are all there is)
+            (void)pack_always;
+            for (int64_t r = tid; r < nrows; r += T) {
+                for (int c = 0; c < 4; ++c) a.out[(row0 + r) * 4 + c] = 0;
+                a.idmask[row0 + r] = 0;
+            }
+            return;
+        }
         const bool z32 = a.enc_out && !a.enc_no32, z16 = a.enc16 && (pack_always || a.enc_no32);
         for (int64_t r = tid; r < nrows; r += T) {
             if (a.out) for (int c = 0; c < 4; ++c) a.out[(row0 + r) * 4 + c] = 0;
@@ -558,6 +573,10 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
     };
 
     // ---- phase 0: clear LDS state, copy the plan table ------------------------------------------------------------
+    typedef unsigned lds16_t __attribute__((ext_vector_type(4)));      // CYC: every cleared array starts and ends on 16 bytes (count_launch)
+    if constexpr (CYC > 0) {
+        for (int i = tid; i < (n + 1) / 2; i += T) reinterpret_cast<lds16_t *>(A)[i] = lds16_t{0u, 0u, 0u, 0u};
+    } else
     for (int i = tid; i < n * W; i += T) A[i] = 0ull;
     if (DIR)
         for (int i = tid; i < n * W; i += T) A_in[i] = 0ull;
@@ -577,10 +596,20 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
             reinterpret_cast<int *>(smem + a.off_enc)[2 * c] = o;
             reinterpret_cast<int *>(smem + a.off_enc)[2 * c + 1] = a.enc_n[c];
         }
+    if constexpr (CYC > 0) {
+        if (tid < 2) reinterpret_cast<lds16_t *>(misc)[tid] = lds16_t{0u, 0u, 0u, 0u};
+    } else
     if (tid < 8) misc[tid] = 0;
     // staged outputs start at zero: rows that carry nothing (self loops, earlier duplicates) and rows whose roots lie outside every plan's core
     // then need no cell-by-cell zeros from the one wave that ranks the columns (8 LDS stores per such row: 7 k of a molecule pair's 60 k cycles)
     const bool bulk_zero = edge_mode && a_stage_out && (!a_enc || a_enc_stage);
+    if constexpr (CYC > 0) {                            // (two staged rows, or four rows' class bytes, per 16-byte store: one trip for a ZINC pair)
+        if (bulk_zero) {
+            for (int i = tid; i < (rows + 1) / 2; i += T) reinterpret_cast<lds16_t *>(out_lds)[i] = lds16_t{0u, 0u, 0u, 0u};
+            if (!a_enc_from_counts)
+                for (int i = tid; i < (rows + 3) / 4; i += T) reinterpret_cast<lds16_t *>(smem + a.off_encst)[i] = lds16_t{0u, 0u, 0u, 0u};
+        }
+    } else
     if (bulk_zero) {
         uint32_t *z = reinterpret_cast<uint32_t *>(out_lds);
         for (int i = tid; i < (rows * n_cols + 1) / 2; i += T) z[i] = 0u;
@@ -593,18 +622,32 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
 
     COUNT_T(0);
     // ---- phase 1: adjacency bit matrix from the columns -----------------------------------------------------------
+    // CYC (one wave): no LDS atomic per column for the flag and the vertex count.  A column with a bad index raises its lane's flag, read
+    // with one ballot behind the loop; the vertex counts misc[1] / misc[5] are not kept at all: they bound the set of vertices that exist,
+    // and this path reads that set only to start the 2-core, which lies inside the vertices with a neighbour whatever the largest id is.
+    // Its endpoint loads: the graph's first column as a scalar base, the lane's column as a 32-bit byte offset.
+    bool bad_lane = false;
     for (int c = tid; c < E; c += T) {
         const bool second = c >= EA;                    // (a column of the pair's second graph: its vertices are nA .. n - 1)
         const int64_t off = a.ids_are_global ? n0 : (second ? -(int64_t)nA : 0);
-        const int64_t u64 = a.src[e0 + c] - off, v64 = a.dst[e0 + c] - off;
+        int64_t u64, v64;
+        if constexpr (CYC > 0) {
+            const uint32_t cb = (uint32_t)c * 8u;
+            u64 = *reinterpret_cast<const int64_t *>(reinterpret_cast<const char *>(a.src + e0) + cb) - off;
+            v64 = *reinterpret_cast<const int64_t *>(reinterpret_cast<const char *>(a.dst + e0) + cb) - off;
+        } else {
+            u64 = a.src[e0 + c] - off; v64 = a.dst[e0 + c] - off;
+        }
         const int64_t lo = second ? nA : 0, hi = second ? n : nA;
         if (u64 < lo || v64 < lo || u64 >= hi || v64 >= hi) {
-            atomicMax(&misc[2], (int)GSN_ST_BAD_INDEX);
+            if constexpr (CYC > 0) bad_lane = true;
+            else atomicMax(&misc[2], (int)GSN_ST_BAD_INDEX);
             if (edge_mode) { eu[c] = 0; ev[c] = 0; }
             continue;
         }
         const int u = (int)u64, v = (int)v64;
         if (edge_mode) { eu[c] = (vid_t)u; ev[c] = (vid_t)v; }
+        if constexpr (CYC == 0)
         atomicMax(&misc[second ? 5 : 1], (u > v ? u : v) + 1);  // graph-tool creates vertices 0..max id, self-loop columns included
         if (u != v) {
             atomicOr(reinterpret_cast<unsigned long long *>(&A[u * W + (v >> 6)]), 1ull << (v & 63));
@@ -614,9 +657,11 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
     __syncthreads();
     COUNT_T(1);
     uint64_t core2 = 0;                                  // CYC: the 2-core, the only core its plans name -- a wave-uniform register, never in LDS
+    bool cyc_bad = false;                                // CYC: some column of the pass has an endpoint outside its graph
     if constexpr (CYC > 0) {
+        cyc_bad = __ballot(bad_lane) != 0ull;
         const uint64_t arow = tid < n ? A[tid] : 0ull;
-        uint64_t cur = below_word(misc[1], 0) | (below_word(misc[5], 0) & ~below_word(nA, 0));      // the vertices that exist (as `valid` below)
+        uint64_t cur = __ballot(arow != 0ull);           // (the peeling may start from the vertices with a neighbour: no other vertex is in a 2-core)
         for (;;) {                                       // (the ballot peeling below, d = 2)
             const uint64_t nxt = __ballot(((cur >> tid) & 1ull) && popc64(arow & cur) >= 2);
             if (nxt == cur) break;
@@ -695,10 +740,22 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
         if (W == 1 && T == 64) {                 // one wave, n <= 64: the row starts are a wave prefix sum of the degrees
             const int d = tid < n ? popc64(A[tid]) : 0;
             int incl = d;
+            if constexpr (CYC > 0) {
+                // CYC: the scan as six adds with DPP operands (shifts inside a row of 16 lanes, then lane 15 / lane 31 broadcast to the rows behind;
+                // a lane without a source adds the `old` operand, 0) instead of six LDS permutes with their address and select instructions.
+                // All 64 lanes are active here.
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xf, 0xf, false);      // row_shr:1
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xf, 0xf, false);      // row_shr:2
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xf, 0xf, false);      // row_shr:4
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xf, 0xf, false);      // row_shr:8
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xa, 0xf, false);      // row_bcast:15 into rows 1 and 3
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xc, 0xf, false);      // row_bcast:31 into rows 2 and 3
+            } else {
 #pragma unroll
             for (int o = 1; o < 64; o <<= 1) {
                 const int t = __shfl_up(incl, o);
                 if (tid >= o) incl += t;
+            }
             }
             if (tid <= n) rowstart[tid] = (rs_t)(incl - d);
             if (tid == 63 && n == 64) rowstart[64] = (rs_t)incl;
@@ -789,7 +846,7 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
         }
     }
     __syncthreads();
-    if (misc[2] != 0) {  // bad index: zeros + status
+    if (CYC > 0 ? cyc_bad : misc[2] != 0) {  // bad index: zeros + status
         if (!report) return 1;
         if (part == 0) {
             if constexpr (CYC > 0) zero_rows_cyc(rows, false);
@@ -799,7 +856,7 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
             if (a.enc16 && a.enc_no32) for (int i = tid; i < rows * a.enc_width; i += T) a.enc16[(row0 + i / a.enc_width) * a.enc16_stride + a.enc16_col0 + i % a.enc_width] = 0;
             if (!DIR && args_late()->idmask) for (int i = tid; i < rows; i += T) args_late()->idmask[row0 + i] = 0;
             }
-            if (tid == 0) atomicMax(&a.status[g], misc[2]);
+            if (tid == 0) atomicMax(&a.status[g], CYC > 0 ? (int)GSN_ST_BAD_INDEX : misc[2]);
         }
         return 0;
     }
@@ -978,8 +1035,25 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
 #ifdef COUNT_PROF
     if (threadIdx.x == 0 && g_count_prof) { g_count_prof[(size_t)blockIdx.x * 16 + 7] = ((unsigned long long)prof_iters << 32) | prof_lanes; for (int q = 0; q < 4; ++q) g_count_prof[(size_t)blockIdx.x * 16 + 8 + q] = prof_arm[q]; }
 #endif
+    // ---- phases 4 and 4' of the headline combination (CycKeys) as ONE loop, a row per lane and trip: the row's four staged counts are one
+    // 8-byte LDS read; the int64 row leaves as two 16-byte stores (32 contiguous bytes per lane, 2 KiB per wave) and the 2-byte identifier
+    // mask is made from the same registers (count_core.h: cyc_row_store, cyc_row_mask).  Addresses: the graph's first row as a scalar base,
+    // the lane's row as a 32-bit byte offset.  An int64 base that is not 16-byte aligned takes 8-byte stores (row0 * 32 keeps the base's
+    // alignment: wave-uniform).
+    if constexpr (KEYS) {
+        char *orow = reinterpret_cast<char *>(a.out + row0 * 4), *mrow = reinterpret_cast<char *>(a.idmask + row0);
+        const bool wide = (reinterpret_cast<uintptr_t>(a.out) & 15) == 0;
+        const uint32_t ncls_w = (uint32_t)a.enc_n[0] | ((uint32_t)a.enc_n[1] << 8) | ((uint32_t)a.enc_n[2] << 16) | ((uint32_t)a.enc_n[3] << 24);
+        const bool clamp = a.enc_clamp != 0;
+        const int col0 = a.enc16_col0;
+        for (int r = tid; r < rows; r += T) {
+            const uint2 q = *reinterpret_cast<const uint2 *>(out_lds + 4 * r);
+            cyc_row_store(reinterpret_cast<int64_t *>(orow + (uint32_t)r * 32u), q.x, q.y, wide);
+            *reinterpret_cast<uint16_t *>(mrow + (uint32_t)r * 2u) = (uint16_t)(cyc_row_mask(q.x, q.y, ncls_w, clamp) << col0);
+        }
+    }
     // ---- phase 4: coalesced write of the staged rows --------------------------------------------------------------
-    if (a_stage_out) {   // (only with split == 1)
+    if (!KEYS && a_stage_out) {   // (only with split == 1)
         int64_t *dst = a.out + row0 * n_cols;
         for (int i = tid; i < rows * n_cols; i += T) {
             const uint16_t v = out_lds[i];
@@ -987,7 +1061,7 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
         }
     }
     // ---- phase 4': encoded rows from the staged class indices, one float per thread and trip, consecutive addresses ----------
-    if (a_enc && a_enc_stage) {
+    if (!KEYS && a_enc && a_enc_stage) {
         const unsigned char *est = smem + a.off_encst;
         // class index of cell (r, c): the staged byte, or from the staged 16-bit count (0xffff = a count of 65 535 and more: the last class
         // when clamped, none otherwise -- class counts fit a byte here)
@@ -1093,10 +1167,12 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
 // scratch (profiles/count_resources_after.txt; 95 registers = 5 waves before).  What brought it there is marked "CYC:" in count_body
 // -- error-path zeros without 64-bit quotients, arguments read where they are used, whole-row staging from 32-bit counters,
 // the 2-core in a register, the lane id opaque per pass; side_block, which shares the kernel, fits the bound as it is.
+// At eight waves the SIMD's vector issue is what is full (profiles/count_cycle_instruction_diet.txt), so the instantiation is also kept
+// short: both flag types, CycAny and CycKeys, stay at 55 registers without scratch (profiles/count_resources_diet.txt).
 #ifndef COUNT_CYC_WAVES
 #define COUNT_CYC_WAVES 8
 #endif
-template <int W, int T, bool DIR, bool TAIL, bool MOL = false, int CYC = 0>
+template <int W, int T, bool DIR, bool TAIL, bool MOL = false, int CYC = 0, class FL = CycAny>
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(CYC > 0 ? COUNT_CYC_WAVES : DIR ? 1 : (W == 1 ? COUNT_W1_WAVES : (W == 2 ? COUNT_W2_WAVES : (W == 4 ? COUNT_W4_WAVES : 1))))))
 void count_kernel(CountArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1125,7 +1201,7 @@ void count_kernel(CountArgs a) {
         const int g = pass == 2 ? g0 + 1 : g0;
         const int ng = (pass == 0 && two) ? 2 : 1;
         int rc;
-        if constexpr (CYC > 0) rc = count_body<W, T, DIR, TAIL, MOL, CYC>(*args_late(), smem, item, 0, g, ng, ng == 1);      // (the body reads every field where it uses it)
+        if constexpr (CYC > 0) rc = count_body<W, T, DIR, TAIL, MOL, CYC, FL>(*args_late(), smem, item, 0, g, ng, ng == 1);      // (the body reads every field where it uses it)
         else rc = count_body<W, T, DIR, TAIL, MOL, CYC>(a, smem, item, (MOL || a.pair) ? 0 : part, g, ng, ng == 1);
         if (!two || (pass == 0 && rc == 0)) break;
     }
@@ -1169,11 +1245,11 @@ __global__ void status_zero_kernel(const int32_t *graph_ids, int n, int32_t *sta
 
 static inline int align_up(int x, int a) { return (x + a - 1) / a * a; }
 
-template <int W, int T, bool DIR, bool TAIL, bool MOL = false, int CYC = 0>
+template <int W, int T, bool DIR, bool TAIL, bool MOL = false, int CYC = 0, class FL = CycAny>
 static int launch_d(CountArgs &a, int n_items, size_t lds, hipStream_t stream) {
     // (the size varies per call: no once-per-device flag; no label: the error names the byte count)
-    if (int rc = lds_limit(nullptr, {kernel_ptr(&count_kernel<W, T, DIR, TAIL, MOL, CYC>)}, nullptr, (int)lds)) return rc;
-    hipLaunchKernelGGL((count_kernel<W, T, DIR, TAIL, MOL, CYC>), dim3((unsigned)n_items), dim3(T), lds, stream, a);
+    if (int rc = lds_limit(nullptr, {kernel_ptr(&count_kernel<W, T, DIR, TAIL, MOL, CYC, FL>)}, nullptr, (int)lds)) return rc;
+    hipLaunchKernelGGL((count_kernel<W, T, DIR, TAIL, MOL, CYC, FL>), dim3((unsigned)n_items), dim3(T), lds, stream, a);
     if (int rc = launch_check("count_kernel launch")) return rc;
 #ifdef COUNT_PROF
     {
@@ -1187,7 +1263,7 @@ static int launch_d(CountArgs &a, int n_items, size_t lds, hipStream_t stream) {
             unsigned long long *buf2 = buf + (size_t)n_items * 16 - 16;      // (the last item's slots 16..: its own row is read first)
             (void)hipMalloc(&buf2, 128); (void)hipMemset(buf2, 0, 128);
             (void)hipMemcpyToSymbol(HIP_SYMBOL(g_count_prof2), &buf2, sizeof(buf2));
-            hipLaunchKernelGGL((count_kernel<W, T, DIR, TAIL, MOL, CYC>), dim3((unsigned)n_items), dim3(T), lds, stream, a);
+            hipLaunchKernelGGL((count_kernel<W, T, DIR, TAIL, MOL, CYC, FL>), dim3((unsigned)n_items), dim3(T), lds, stream, a);
             (void)hipStreamSynchronize(stream);
             unsigned long long *h = new unsigned long long[(size_t)n_items * 16];
             (void)hipMemcpy(h, buf, (size_t)n_items * 128, hipMemcpyDeviceToHost);
@@ -1242,7 +1318,11 @@ static int launch(CountArgs &a, int n_items, size_t lds, hipStream_t stream) {
             trace("gsn count: molecule instantiation %d cycle walk %d (tail %d mode %d sym %d cols %d pair %d split %d stage %d out %d enc %d enc_stage %d ids %d)\n", (int)mol,
                         (int)(a.cyc_len != 0), (int)tail, a.mode, a.sym, a.n_cols, a.pair, a.split, a.stage_out, a.out != nullptr, a.enc_out != nullptr, a.enc_stage, a.graph_ids != nullptr);
             // every column a cycle of length <= 6 (count_launch: the launch's LDS was laid out for it, under these very conditions): the walk
-            if (a.cyc_len) return launch_d<1, 64, false, false, true, 6>(a, n_items, lds, stream);
+            if (a.cyc_len) {
+                // (the headline step's flag combination as compile-time constants: count_body, CycKeys)
+                const bool keys = a.out && a.stage_out && a.enc_stage && a.enc_from_counts && a.enc_no32 && !a.enc16 && a.idmask && a.split == 1;
+                return keys ? launch_d<1, 64, false, false, true, 6, CycKeys>(a, n_items, lds, stream) : launch_d<1, 64, false, false, true, 6>(a, n_items, lds, stream);
+            }
             if (mol) {
                 if (int rc = lds_limit(nullptr, {kernel_ptr(&count_kernel_mol)}, nullptr, (int)lds)) return rc;
                 hipLaunchKernelGGL(count_kernel_mol, dim3((unsigned)n_items), dim3(64), lds, stream, a);

@@ -538,6 +538,46 @@ GSN_HD void cycle_walk(const uint64_t *A, const int u, const int v, const uint64
     for (int i = 0; i < L - 2; ++i) cnt[i] = (Out)c[i];
 }
 
+// ---- a finished row of a cycle launch leaving LDS: the four staged 16-bit counts (lo = cells 0, 1; hi = cells 2, 3: one 8-byte read) ------
+// A staged 0xffff means "this cell's count did not fit 16 bits and went to memory by itself" (count.hip: emit_row), so it is not stored again.
+// Does one of the four cells hold 0xffff?  (the zero-halfword test on the complement)
+GSN_HD bool cyc_row_has_direct(const uint32_t lo, const uint32_t hi) {
+    return ((((~lo) - 0x00010001u) & lo & 0x80008000u) | (((~hi) - 0x00010001u) & hi & 0x80008000u)) != 0u;
+}
+// The int64 row d[0 .. 3].  wide: d is 16-byte aligned -- two 16-byte stores, 32 contiguous bytes per lane; else four 8-byte stores.  A row
+// with a 0xffff cell goes cell by cell and skips those cells.
+typedef int64_t cyc_i64x2 __attribute__((vector_size(16)));
+GSN_HD void cyc_row_store(int64_t *d, const uint32_t lo, const uint32_t hi, const bool wide) {
+    const uint32_t c0 = lo & 0xffffu, c1 = lo >> 16, c2 = hi & 0xffffu, c3 = hi >> 16;
+    if (cyc_row_has_direct(lo, hi)) {
+        if (c0 != 0xffffu) d[0] = (int64_t)c0;
+        if (c1 != 0xffffu) d[1] = (int64_t)c1;
+        if (c2 != 0xffffu) d[2] = (int64_t)c2;
+        if (c3 != 0xffffu) d[3] = (int64_t)c3;
+    } else if (wide) {
+        cyc_i64x2 *d2 = reinterpret_cast<cyc_i64x2 *>(d);
+        d2[0] = cyc_i64x2{(int64_t)c0, (int64_t)c1};
+        d2[1] = cyc_i64x2{(int64_t)c2, (int64_t)c3};
+    } else {
+        d[0] = (int64_t)c0; d[1] = (int64_t)c1; d[2] = (int64_t)c2; d[3] = (int64_t)c3;
+    }
+}
+// The row's hot columns as bits: column c owns the bits  sum of the classes before it .. + its own; its class is the count, the last class
+// when clamped and beyond, none when not clamped and beyond (0xffff = 65 535 and more: beyond every class count, which fit a byte).
+// ncls_w: the four columns' class counts, a byte each.  The caller shifts the mask to its first pack column.
+GSN_HD uint32_t cyc_row_mask(const uint32_t lo, const uint32_t hi, const uint32_t ncls_w, const bool clamp) {
+    const uint32_t cell[4] = {lo & 0xffffu, lo >> 16, hi & 0xffffu, hi >> 16};
+    uint32_t m = 0u, first = 0u;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const uint32_t n = (ncls_w >> (8 * c)) & 0xffu;
+        const uint32_t cls = cell[c] < n ? cell[c] : n - 1u;
+        if (cell[c] < n || clamp) m |= 1u << (first + cls);
+        first += n;
+    }
+    return m;
+}
+
 // Is this plan table a set of such columns?  Judged from the plans' structure, not from pattern names: edge mode, non-induced, undirected
 // orbit classes; every column has exactly one plan (a cycle has one arc orbit: a second plan would ADD to the column), rooted at an arc,
 // without non-adjacency or order masks, and the pattern rebuilt from its levels' adjacency masks plus the root edge is one cycle: k
