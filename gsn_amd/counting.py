@@ -12,6 +12,9 @@ Everything routes through ``gsn_count_hip`` in libgsn_hip.so.  No CPU fallback: 
 Graphs the LDS-resident kernel refuses (more than 768 vertices, tables beyond its LDS, 65 535 columns per graph) go to the sparse kernel
 (``gsn_count_sparse_hip``, csrc/count_sparse.hip): :func:`count_batch` / :func:`counts2ids_batch` on request (``large="sparse"``), the
 per-graph drop-ins always.  Undirected plans and directed ones (``directed=True``: vertex counts) alike.
+
+Pattern lists whose largest pattern has 10 to 16 vertices compile into a WIDE plan table (``CountPlan(..., wide=True)``), which only the
+sparse kernel executes: ``large="sparse"`` then sends every graph there, at any size; the per-graph drop-ins ask for it on their own.
 """
 from __future__ import annotations
 
@@ -27,6 +30,9 @@ __all__ = ["CountPlan", "count_batch", "counts2ids_batch", "subgraph_isomorphism
            "subgraph_isomorphism_edge_counts", "subgraph_counts2ids"]
 
 GSN_KMAX = 9                                            # include/gsn_abi.h
+GSN_KMAX_WIDE = 16                                      # include/gsn_abi.h: patterns of a wide plan table
+_FLAG_WIDE = 4                                          # include/gsn_abi.h: GSN_FLAG_WIDE
+_PLAN_MAGIC_WIDE = 0x47534e32                           # csrc/gsn_internal.h: 'GSN2'
 PLAN_STRIDE_WORDS = 2 + GSN_KMAX + (GSN_KMAX + 3) // 4  # csrc/gsn_internal.h (undirected plans)
 _MODE = {"vertex": 0, "edge": 1}
 _STATUS_MSG = {2: "graph larger than the max_nodes / max_edges given to the call", 3: "vertex id outside [0, num_nodes)"}
@@ -34,9 +40,13 @@ _PLAN_CACHE = {}
 
 
 class CountPlan:
-    """Compiled search plans for a list of patterns (built on the host by gsn_count_plan_build, cached per device)."""
+    """Compiled search plans for a list of patterns (built on the host by gsn_count_plan_build, cached per device).
 
-    def __init__(self, pattern_edge_lists, mode, induced, directed_orbits=False, directed=False):
+    ``wide=True`` admits patterns of 10 to 16 vertices (else a ``GsnError``: k <= 9).  ``plan.wide`` tells whether the table that came back
+    is a wide one -- it is when the largest pattern has more than nine vertices; a list of smaller patterns gives the same table with
+    and without ``wide``.  A wide table is counted by the sparse kernel only (:func:`count_batch` with ``large="sparse"``)."""
+
+    def __init__(self, pattern_edge_lists, mode, induced, directed_orbits=False, directed=False, wide=False):
         self.mode = mode
         self.induced = bool(induced)
         self.directed_orbits = bool(directed_orbits)
@@ -48,7 +58,7 @@ class CountPlan:
         pat_edges = np.ascontiguousarray(np.concatenate(pats, axis=0))
         L = _abi.lib()
         words, ncols = ctypes.c_int64(), ctypes.c_int64()
-        args = (_MODE[mode], int(self.induced), int(self.directed_orbits) | (2 if self.directed else 0), len(pats),
+        args = (_MODE[mode], int(self.induced), int(self.directed_orbits) | (2 if self.directed else 0) | (_FLAG_WIDE if wide else 0), len(pats),
                 _abi.ptr(pat_ptr), _abi.ptr(pat_edges))
         _abi.check(L.gsn_count_plan_build(*args, None, 0, ctypes.addressof(words), ctypes.addressof(ncols)),
                    "gsn_count_plan_build")
@@ -58,14 +68,15 @@ class CountPlan:
         self.n_cols = int(ncols.value)
         self.n_plans = int(self.table[3])
         self.kmax = int(self.table[5])
+        self.wide = int(self.table[0]) == _PLAN_MAGIC_WIDE
         self._dev = {}
 
     @staticmethod
-    def get(pattern_edge_lists, mode, induced, directed_orbits=False, directed=False):
+    def get(pattern_edge_lists, mode, induced, directed_orbits=False, directed=False, wide=False):
         key = (tuple(tuple((int(u), int(v)) for u, v in el) for el in pattern_edge_lists), mode, bool(induced),
-               bool(directed_orbits), bool(directed))
+               bool(directed_orbits), bool(directed), bool(wide))
         if key not in _PLAN_CACHE:
-            _PLAN_CACHE[key] = CountPlan(pattern_edge_lists, mode, induced, directed_orbits, directed)
+            _PLAN_CACHE[key] = CountPlan(pattern_edge_lists, mode, induced, directed_orbits, directed, wide)
         return _PLAN_CACHE[key]
 
     def device_table(self, device):
@@ -90,7 +101,8 @@ def count_batch(plan: CountPlan, node_ptr, edge_ptr, edge_index, ids_are_global=
     160 KiB of LDS, 65 535 columns per graph).  ``"refuse"`` (default): :class:`GsnError`.  ``"sparse"``: the sparse kernel
     (``gsn_count_sparse_hip``: sorted neighbour lists in HBM, one lane per rooted search) counts the launch -- at once when ``max_nodes``
     exceeds 768, else after ``gsn_count_hip`` has refused.  Plain counts only: with ``encode`` it is a ``ValueError``.  Directed plans
-    (vertex mode) take the same route.
+    (vertex mode) take the same route.  A WIDE plan (``plan.wide``: patterns of 10 to 16 vertices) is executed by the sparse kernel only:
+    ``large="sparse"`` sends every graph of the launch there, at any size; ``"refuse"`` raises :class:`GsnError`, ``encode`` ``ValueError``.
 
     ``encode=(n_classes, clamp)`` also returns the one-hot encoded identifiers the GSN layers consume (the reference's
     ``DiscreteEmbedding('one_hot_encoder')`` over the counts, utils_graph_learning.py:170-187) straight from the kernel
@@ -111,6 +123,10 @@ def count_batch(plan: CountPlan, node_ptr, edge_ptr, edge_index, ids_are_global=
         raise ValueError("large: 'refuse' or 'sparse' (got %r)" % (large,))
     if large == "sparse" and encode is not None:
         raise ValueError("large='sparse' counts only: the fused encodings (encode=) stay on the LDS-resident kernel")
+    if plan.wide and encode is not None:
+        raise ValueError("wide plans count only: the fused encodings (encode=) need patterns of at most %d vertices" % GSN_KMAX)
+    if plan.wide and large != "sparse":
+        raise _abi.GsnError("wide plan (patterns of up to %d vertices): only the sparse kernel counts it -- pass large=\"sparse\"" % plan.kmax)
     _abi.require_gpu()
     if device is None:
         device = edge_index.device if isinstance(edge_index, torch.Tensor) and edge_index.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -181,7 +197,7 @@ def count_batch(plan: CountPlan, node_ptr, edge_ptr, edge_index, ids_are_global=
                     rc = _abi.lib().gsn_count_hip(*common, _abi.current_stream())
                     pack_codes_later = True
             elif enc is None:
-                rc = -2 if (large == "sparse" and int(max_nodes) > 768) else _abi.lib().gsn_count_hip(*common, _abi.current_stream())
+                rc = -2 if (large == "sparse" and (int(max_nodes) > 768 or plan.wide)) else _abi.lib().gsn_count_hip(*common, _abi.current_stream())
                 if rc == -2 and large == "sparse":
                     # GSN_E_UNSUPPORTED of a plain count is a size reason (vertices, columns, LDS): the sparse kernel has no such limit
                     span = torch.stack([node_ptr_d[-1] - node_ptr_d[0], edge_ptr_d[-1] - edge_ptr_d[0]]).tolist()
@@ -239,6 +255,8 @@ def count_batch_side(plan, node_ptr, edge_ptr, edge_index, max_nodes, max_edges,
     that ``layer(x_codes, edge_index, identifiers=id_codes, edge_features=ef_codes)`` right behind this call launches the layer kernel
     and nothing else.  GsnError(GSN_E_UNSUPPORTED) when this launch configuration cannot write them (a graph split over workgroups)."""
     from ._index import Codes, _CSR, _cache_put
+    if plan.wide:
+        raise ValueError("count_batch_side: wide plans count only (count_batch with large=\"sparse\")")
     _abi.require_gpu()
     dev = edge_index.device
     if not (edge_index.is_cuda and node_ptr.is_cuda and edge_ptr.is_cuda) or edge_index.dtype != torch.int64 or edge_index.stride(1) != 1:
@@ -327,10 +345,11 @@ def _raise_statuses(status):
         raise ValueError("graph %d: %s" % (int(bad[0]), _STATUS_MSG.get(int(st[bad[0]]), "status %d" % st[bad[0]])))
 
 
-def counts2ids_batch(batch, pattern_edge_lists, mode, induced, directed_orbits=False, device=None, directed=False, large="refuse"):
+def counts2ids_batch(batch, pattern_edge_lists, mode, induced, directed_orbits=False, device=None, directed=False, large="refuse", wide=False):
     """Batched ``subgraph_counts2ids`` over a :class:`gsn_amd.synth.Batch`-like object (node_ptr, edge_ptr, edge_index
-    with batch-global ids, self loops already stripped).  -> int64 device tensor [rows_total, sum orbits].  ``large``: as :func:`count_batch`."""
-    plan = CountPlan.get(pattern_edge_lists, mode, induced, directed_orbits, directed)
+    with batch-global ids, self loops already stripped).  -> int64 device tensor [rows_total, sum orbits].  ``large``: as :func:`count_batch`;
+    ``wide``: as :class:`CountPlan`."""
+    plan = CountPlan.get(pattern_edge_lists, mode, induced, directed_orbits, directed, wide)
     out, _ = count_batch(plan, batch.node_ptr, batch.edge_ptr, batch.edge_index, ids_are_global=True, device=device, large=large)
     return out
 
@@ -374,7 +393,7 @@ def subgraph_isomorphism_vertex_counts(edge_index, **kwargs):
     subgraph_dict, induced, num_nodes = kwargs["subgraph_dict"], kwargs["induced"], kwargs["num_nodes"]
     sg = _pattern_of(subgraph_dict)
     directed = _directed_of([sg], kwargs.get("directed", False))
-    plan = CountPlan.get([sg.edge_list], "vertex", induced, False, directed)
+    plan = CountPlan.get([sg.edge_list], "vertex", induced, False, directed, wide=True)
     ei, n, E = _single_graph(edge_index, num_nodes)
     out, _ = count_batch(plan, [0, n], [0, E], ei, ids_are_global=False, max_nodes=n, max_edges=E, large="sparse")
     return out[:int(num_nodes)].cpu().to(torch.float64)
@@ -387,7 +406,7 @@ def subgraph_isomorphism_edge_counts(edge_index, **kwargs):
     if kwargs.get("directed", False):
         raise NotImplementedError("directed=True is not supported (NameError in the reference, utils_graph_processing.py:164)")
     sg = _pattern_of(subgraph_dict)
-    plan = CountPlan.get([sg.edge_list], "edge", induced, sg.directed_orbits)
+    plan = CountPlan.get([sg.edge_list], "edge", induced, sg.directed_orbits, wide=True)
     ei, n, E = _single_graph(edge_index, 0)
     out, _ = count_batch(plan, [0, max(n, 1)], [0, E], ei, ids_are_global=False, max_nodes=max(n, 1), max_edges=E, large="sparse")
     if getattr(sg, "line_graph_orbits", False):
@@ -428,14 +447,14 @@ def subgraph_counts2ids(count_fn, data, subgraph_dicts, subgraph_params):
     if directed and mode == "edge":
         raise NotImplementedError("directed=True is not supported (NameError in the reference, utils_graph_processing.py:164)")
     dirorb = any(p.directed_orbits for p in pats) if mode == "edge" else False
-    plan = CountPlan.get([p.edge_list for p in pats], mode, subgraph_params["induced"], dirorb, directed)
+    plan = CountPlan.get([p.edge_list for p in pats], mode, subgraph_params["induced"], dirorb, directed, wide=True)
     e_cpu, n, E = _single_graph(edge_index, num_nodes)
     out, _ = count_batch(plan, [0, n], [0, E], e_cpu, ids_are_global=False, max_nodes=n, max_edges=E, large="sparse")
     ids = out[:num_nodes] if mode == "vertex" else out
     if mode == "edge" and any(getattr(p, "line_graph_orbits", False) for p in pats):
         cols, blocks = 0, []
         for p, d in zip(pats, subgraph_dicts):        # per pattern, as the reference's loop would reach it
-            w = CountPlan.get([p.edge_list], mode, subgraph_params["induced"], dirorb).n_cols
+            w = CountPlan.get([p.edge_list], mode, subgraph_params["induced"], dirorb, wide=True).n_cols
             if p.line_graph_orbits:
                 _line_graph_orbits_keyerror(p, out[:, cols:cols + w])
                 blocks.append(torch.zeros((out.shape[0], len(d["orbit_partition"])), dtype=torch.int64, device=out.device))

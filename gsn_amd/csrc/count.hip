@@ -1343,6 +1343,7 @@ static int count_launch(const uint32_t *plan_host, const uint32_t *plan_dev, int
                         int64_t max_nodes, int64_t max_edges, int64_t *out, int32_t *status, const int32_t *n_classes,
                         int enc_clamp, float *enc_out, void *stream, uint16_t *enc16 = nullptr, int64_t enc16_stride = 0, int64_t enc16_col0 = 0, int enc_no32 = 0,
                         const gsn_count_side *side = nullptr, const gsn_count_keys *keys = nullptr) {
+    if (plan_host && plan_words >= PLAN_HEADER_WORDS && plan_host[0] == PLAN_MAGIC_WIDE) return set_error(GSN_E_UNSUPPORTED, GSN_WIDE_PLAN_REFUSAL);
     if (!plan_host || !plan_dev || plan_words < PLAN_HEADER_WORDS || plan_host[0] != PLAN_MAGIC)
         return set_error(GSN_E_INVALID, "gsn_count_hip: not a plan table (build it with gsn_count_plan_build)");
     if (!node_ptr || !edge_ptr || (!out && !enc_out) || !status) return set_error(GSN_E_INVALID, "gsn_count_hip: null pointer argument");

@@ -12,14 +12,15 @@
 //            rocPRIM               device radix sort of the keys, then unique: parallel columns merged, lists strictly increasing
 //            sparse_csr_kernel     row_ptr by binary search over the sorted keys, nbr = their low halves
 //            sparse_arc_kernel     edge mode: per arc slot the LAST column that holds that direction (utils_graph_processing.py:142-144)
-//   search   sparse_search_kernel  <DIR>: undirected / directed plans (vertex mode only: there are no directed edge counts).  Persistent
-//                                  waves; lanes pull (output column, row) cells from one global counter with a wave-aggregated atomic;
-//                                  every cell is written by exactly one lane, no atomics on counts: deterministic
+//   search   sparse_search_kernel  <DIR, WIDE>: undirected / directed plans (vertex mode only: there are no directed edge counts), narrow
+//                                  tables (patterns of <= 9 vertices) / wide ones (10 .. 16: gsn_internal.h).  Persistent waves; lanes
+//                                  pull (output column, row) cells from one global counter with a wave-aggregated atomic; every cell is written by exactly one lane, no atomics on counts: deterministic
 // Vertices and columns are numbered from the first pointer of the launch (node_ptr[0], edge_ptr[0]), 32 bits each.  The launcher reads
 // those two and the two last pointers back (one stream synchronisation): the launch cannot be captured into a graph.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <type_traits>
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_select.hpp>
@@ -188,10 +189,17 @@ constexpr int SP_PULL_BATCH = 8;      // idle lanes are refilled when this many 
 
 // One wave per workgroup.  A lane is idle, or owns one cell: the plans of its column run one after the other, a turn of the walk per trip.
 // DIR: a directed plan (vertex mode): a fifth state field for the in-masks, the longer plan stride, in-lists at rows nv + v.
-template <bool DIR>
+// WIDE: a wide plan table: 15 levels with a slot instead of 8 -- (4 or 5) * 15 * 64 state words, 15 360 B or 19 200 B of LDS a workgroup.
+template <bool WIDE>
+using SparseFormat = typename std::conditional<WIDE, SpWide, SpNarrow>::type;
+template <bool DIR, bool WIDE>
+constexpr int sparse_state_words() { return (DIR ? SP_FIELDS_DIRECTED : SP_FIELDS) * SparseFormat<WIDE>::LEVELS * 64; }
+
+template <bool DIR, bool WIDE = false>
 __global__ __launch_bounds__(64) void sparse_search_kernel(SparseArgs a) {
-    __shared__ uint32_t st_all[(DIR ? SP_FIELDS_DIRECTED : SP_FIELDS) * SP_LEVELS * 64];
-    constexpr int stride = DIR ? PLAN_STRIDE_DIRECTED : PLAN_STRIDE_WORDS;
+    using FMT = SparseFormat<WIDE>;
+    __shared__ uint32_t st_all[sparse_state_words<DIR, WIDE>()];
+    constexpr int stride = DIR ? FMT::STRIDE_DIRECTED : FMT::STRIDE;
     const int lane = threadIdx.x;
     uint32_t *st = st_all + lane;
     const bool edge_mode = !DIR && a.mode == GSN_MODE_EDGE;
@@ -264,9 +272,9 @@ __global__ __launch_bounds__(64) void sparse_search_kernel(SparseArgs a) {
         }
         if (has) {
             if (s.l < 0) {
-                if (p_i < p_e) { sp_begin(s, plans + (size_t)p_i * stride, r0, r1, st, 64); ++p_i; }
+                if (p_i < p_e) { sp_begin<FMT>(s, plans + (size_t)p_i * stride, r0, r1, st, 64); ++p_i; }
             } else {
-                sp_step<DIR>(gr, s, st, 64);
+                sp_step<DIR, FMT>(gr, s, st, 64);
             }
             if (s.l < 0 && p_i >= p_e) {                         // the cell's last plan ended in this trip (or it had none)
                 const int64_t rbase = edge_mode ? a.e0 : a.n0;
@@ -302,8 +310,9 @@ extern "C" int gsn_count_sparse_hip(const uint32_t *plan_host, const uint32_t *p
                                     int64_t max_nodes, int64_t max_edges, int64_t *out, int32_t *status, void *workspace,
                                     int64_t workspace_bytes, void *stream) {
     (void)max_nodes; (void)max_edges;                 // (no table here is sized by a single graph)
-    if (!plan_host || !plan_dev || plan_words < PLAN_HEADER_WORDS || plan_host[0] != PLAN_MAGIC)
+    if (!plan_host || !plan_dev || plan_words < PLAN_HEADER_WORDS || (plan_host[0] != PLAN_MAGIC && plan_host[0] != PLAN_MAGIC_WIDE))
         return set_error(GSN_E_INVALID, "gsn_count_sparse_hip: not a plan table (build it with gsn_count_plan_build)");
+    const bool wide = plan_host[0] == PLAN_MAGIC_WIDE;      // patterns of 10 .. 16 vertices: the wide instantiation of the search kernel
     if (!node_ptr || !edge_ptr || !out || !status || !workspace) return set_error(GSN_E_INVALID, "gsn_count_sparse_hip: null pointer argument");
     const bool directed = (plan_host[6] & 2u) != 0;
     if (directed && plan_host[1] != (uint32_t)GSN_MODE_VERTEX)
@@ -347,7 +356,7 @@ extern "C" int gsn_count_sparse_hip(const uint32_t *plan_host, const uint32_t *p
     a.vmax = reinterpret_cast<uint32_t *>(ws + L.vmax);
     a.cell_counter = reinterpret_cast<unsigned long long *>(ws + L.misc);
     a.n_unique = reinterpret_cast<unsigned int *>(ws + L.misc + 8);
-    if (a.n_cols < 1 || plan_words < (int64_t)plan_host[7] + (int64_t)plan_host[3] * plan_stride(plan_host[6]))
+    if (a.n_cols < 1 || plan_words < (int64_t)plan_host[7] + (int64_t)plan_host[3] * (wide ? plan_stride_wide(plan_host[6]) : plan_stride(plan_host[6])))
         return set_error(GSN_E_INVALID, "gsn_count_sparse_hip: plan table shorter than its header says");
 
     const int64_t arcs = 2 * ec, rows = a.mode == GSN_MODE_EDGE ? ec : nv;
@@ -389,8 +398,12 @@ extern "C" int gsn_count_sparse_hip(const uint32_t *plan_host, const uint32_t *p
     if (rows > 0) {
         // persistent waves: at most 16 one-wave workgroups per CU's worth of the chip, fewer when the cells are few
         const int64_t cells = rows * (int64_t)a.n_cols, want = (cells + 63) / 64;
-        const unsigned grid = (unsigned)(want < 1 ? 1 : (want > 256 * 16 ? 256 * 16 : want));
-        if (directed) hipLaunchKernelGGL(sparse_search_kernel<true>, dim3(grid), dim3(64), 0, st, a);
+        // (a wide search keeps 15 360 B / 19 200 B of state in LDS: 10 / 8 workgroups fit the 160 KiB of a CU, and no more are started)
+        const int64_t per_cu = !wide ? 16 : LDS_LIMIT_BYTES / (int64_t)(sizeof(uint32_t) * (directed ? sparse_state_words<true, true>() : sparse_state_words<false, true>()));
+        const unsigned grid = (unsigned)(want < 1 ? 1 : (want > 256 * per_cu ? 256 * per_cu : want));
+        if (wide && directed) hipLaunchKernelGGL((sparse_search_kernel<true, true>), dim3(grid), dim3(64), 0, st, a);
+        else if (wide) hipLaunchKernelGGL((sparse_search_kernel<false, true>), dim3(grid), dim3(64), 0, st, a);
+        else if (directed) hipLaunchKernelGGL(sparse_search_kernel<true>, dim3(grid), dim3(64), 0, st, a);
         else hipLaunchKernelGGL(sparse_search_kernel<false>, dim3(grid), dim3(64), 0, st, a);
         if (int rc = launch_check("sparse_search_kernel launch")) return rc;
     }

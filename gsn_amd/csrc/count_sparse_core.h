@@ -40,6 +40,15 @@
 // plain array (host), ss = the lane count with st pointing at the lane's own word of a lane-interleaved LDS array (device).  A directed
 // search keeps the in-masks still to check in a fifth field (SP_CHK_IN; SP_FIELDS_DIRECTED * SP_LEVELS words): SP_CHK has no bit free, and
 // an undirected search neither reads nor reserves the field.
+//
+// Plan width.  Every function below takes the format of the plan table as its last template parameter, a struct of four numbers: the
+// levels that hold a slot, the width of a mask field, the words per level and the plan stride.  The default, SpNarrow, is the table of
+// patterns of at most GSN_KMAX = 9 vertices described above.  SpWide is the wide table (gsn_internal.h: PLAN_MAGIC_WIDE) of pattern lists
+// with 10 .. GSN_KMAX_WIDE = 16 vertices: 15 levels with a slot, 16-bit fields, adj | nonadj << 16 at plan[2 + l], gt | lt << 16 in a second
+// word at plan[PLAN_WIDE_ORD_OFF + l] and, directed, in_adj | in_nonadj << 16 in a third at plan[PLAN_WIDE_IN_OFF + l].  The order word of
+// a level never changes during a search (only an adjacency bit, the anchor's, is ever struck), so a wide search reads it from the plan at
+// every turn and keeps the same four (directed: five) state fields per level: (4 or 5) * 15 words per lane.  Anchor choice, binary-search
+// checks, the closed-form tails and the edge-mode row rules are the same code for both formats.
 #pragma once
 
 #include <stdint.h>
@@ -49,8 +58,25 @@
 namespace gsn {
 
 constexpr int SP_LEVELS = 8;          // levels that hold an image or a cursor: 0 .. k - 2 with k <= GSN_KMAX = 9
+constexpr int SP_LEVELS_WIDE = 15;    // the same of a wide plan: k <= GSN_KMAX_WIDE = 16
 enum { SP_IMG = 0, SP_CUR = 1, SP_END = 2, SP_CHK = 3, SP_FIELDS = 4, SP_CHK_IN = 4, SP_FIELDS_DIRECTED = 5 };
 static_assert(GSN_KMAX - 1 <= SP_LEVELS, "the last level is counted, every earlier one has a slot");
+static_assert(GSN_KMAX_WIDE - 1 <= SP_LEVELS_WIDE, "the last level is counted, every earlier one has a slot");
+
+// the format of a plan table: LEVELS with a slot, BITS per mask field, WORDS per level (undirected; a directed plan has one more), and the
+// plan STRIDE (undirected / directed)
+template <int LEVELS_, int BITS_, int WORDS_, int STRIDE_, int STRIDE_DIRECTED_>
+struct SpFormat {
+    static constexpr int LEVELS = LEVELS_, BITS = BITS_, WORDS = WORDS_, STRIDE = STRIDE_, STRIDE_DIRECTED = STRIDE_DIRECTED_;
+    static constexpr uint32_t MASK = (1u << BITS_) - 1u;
+    static constexpr bool ORD_WORD = WORDS_ > 1;                          // gt | lt in a word of their own (else in the upper half of the first)
+    static constexpr int ORD_OFF = (STRIDE_ - 2) / WORDS_ + 2;            // wide: plan[ORD_OFF + l]
+    static constexpr int IN_OFF = STRIDE_;                                // directed: plan[IN_OFF + l]
+};
+using SpNarrow = SpFormat<SP_LEVELS, 8, 1, PLAN_STRIDE_WORDS, PLAN_STRIDE_DIRECTED>;
+using SpWide = SpFormat<SP_LEVELS_WIDE, 16, 2, PLAN_STRIDE_WIDE, PLAN_STRIDE_WIDE_DIRECTED>;
+static_assert(SpWide::ORD_OFF == PLAN_WIDE_ORD_OFF && SpWide::IN_OFF == PLAN_WIDE_IN_OFF, "the wide record of gsn_internal.h");
+static_assert(SpNarrow::IN_OFF == PLAN_STRIDE_WORDS, "the narrow record of gsn_internal.h");
 
 struct SparseGraph {
     const uint32_t *row_ptr;   // [n + 1] over the caller's vertex numbering; directed: [in_base + n + 1]
@@ -59,7 +85,7 @@ struct SparseGraph {
     uint32_t in_base = 0;      // directed: row in_base + v holds the in-neighbours of v, row v its out-neighbours
 };
 
-#define GSN_SP(F, L) st[((F) * SP_LEVELS + (L)) * ss]
+#define GSN_SP(F, L) st[((F) * FMT::LEVELS + (L)) * ss]
 
 // position of b in row a, or -1
 GSN_HD int64_t sp_find(const SparseGraph &g, uint32_t a, uint32_t b) {
@@ -73,42 +99,43 @@ GSN_HD int64_t sp_find(const SparseGraph &g, uint32_t a, uint32_t b) {
     return -1;
 }
 
-// does v satisfy the masks `chk` (and, directed, the in-masks `chk_in`) against the images of the levels they name?
-template <bool DIR = false>
-GSN_HD bool sp_masks_hold(const SparseGraph &g, const uint32_t *st, int ss, uint32_t chk, uint32_t chk_in, uint32_t v) {
-    uint32_t m = chk & 0xffu;
+// does v satisfy the masks `chk` (and, directed, the in-masks `chk_in`) against the images of the levels they name?  `ord`: the order
+// word of a format that has one (else the order masks are the upper half of `chk`)
+template <bool DIR = false, class FMT = SpNarrow>
+GSN_HD bool sp_masks_hold(const SparseGraph &g, const uint32_t *st, int ss, uint32_t chk, uint32_t chk_in, uint32_t ord, uint32_t v) {
+    uint32_t m = chk & FMT::MASK;
     while (m) {
         const int j = ctz64(m);
         m &= m - 1u;
         if (sp_find(g, GSN_SP(SP_IMG, j), v) < 0) return false;
     }
-    m = (chk >> 8) & 0xffu;
+    m = (chk >> FMT::BITS) & FMT::MASK;
     while (m) {
         const int j = ctz64(m);
         m &= m - 1u;
         if (sp_find(g, GSN_SP(SP_IMG, j), v) >= 0) return false;
     }
     if (DIR) {
-        m = chk_in & 0xffu;
+        m = chk_in & FMT::MASK;
         while (m) {
             const int j = ctz64(m);
             m &= m - 1u;
             if (sp_find(g, g.in_base + GSN_SP(SP_IMG, j), v) < 0) return false;
         }
-        m = (chk_in >> 8) & 0xffu;
+        m = (chk_in >> FMT::BITS) & FMT::MASK;
         while (m) {
             const int j = ctz64(m);
             m &= m - 1u;
             if (sp_find(g, g.in_base + GSN_SP(SP_IMG, j), v) >= 0) return false;
         }
     }
-    m = (chk >> 16) & 0xffu;
+    m = FMT::ORD_WORD ? ord & FMT::MASK : (chk >> 16) & 0xffu;
     while (m) {
         const int j = ctz64(m);
         m &= m - 1u;
         if (!(v > GSN_SP(SP_IMG, j))) return false;
     }
-    m = chk >> 24;
+    m = FMT::ORD_WORD ? ord >> FMT::BITS : chk >> 24;
     while (m) {
         const int j = ctz64(m);
         m &= m - 1u;
@@ -118,21 +145,21 @@ GSN_HD bool sp_masks_hold(const SparseGraph &g, const uint32_t *st, int ss, uint
 }
 
 // candidate of a level with the images of levels 0 .. nimg - 1 placed: distinct from all of them, and the masks hold
-template <bool DIR = false>
-GSN_HD bool sp_accept(const SparseGraph &g, const uint32_t *st, int ss, uint32_t chk, uint32_t chk_in, int nimg, uint32_t v) {
+template <bool DIR = false, class FMT = SpNarrow>
+GSN_HD bool sp_accept(const SparseGraph &g, const uint32_t *st, int ss, uint32_t chk, uint32_t chk_in, uint32_t ord, int nimg, uint32_t v) {
     for (int j = 0; j < nimg; ++j)
         if (GSN_SP(SP_IMG, j) == v) return false;
-    return sp_masks_hold<DIR>(g, st, ss, chk, chk_in, v);
+    return sp_masks_hold<DIR, FMT>(g, st, ss, chk, chk_in, ord, v);
 }
 
 // the candidate list of a level with masks `desc` (directed: and in-masks `din`): positions cur .. end of nbr (or vertex ids, when the
 // level has no adjacency mask in either word), and the masks that remain to be checked per candidate
-template <bool DIR = false>
+template <bool DIR = false, class FMT = SpNarrow>
 GSN_HD void sp_open(const SparseGraph &g, const uint32_t *st, int ss, uint32_t desc, uint32_t din, uint32_t &cur, uint32_t &end, uint32_t &chk,
                     uint32_t &chk_in) {
-    uint32_t m = desc & 0xffu;
+    uint32_t m = desc & FMT::MASK;
     chk_in = din;
-    if (!m && !(DIR && (din & 0xffu))) { cur = g.v_lo; end = g.v_hi; chk = desc; return; }
+    if (!m && !(DIR && (din & FMT::MASK))) { cur = g.v_lo; end = g.v_hi; chk = desc; return; }
     int best = -1;
     uint32_t blen = 0, bcur = 0;
     while (m) {
@@ -142,34 +169,35 @@ GSN_HD void sp_open(const SparseGraph &g, const uint32_t *st, int ss, uint32_t d
         if (best < 0 || len < blen) { best = j; blen = len; bcur = lo; }
     }
     if (DIR) {
-        m = din & 0xffu;
+        m = din & FMT::MASK;
         while (m) {
             const int j = ctz64(m);
             m &= m - 1u;
             const uint32_t a = g.in_base + GSN_SP(SP_IMG, j), lo = g.row_ptr[a], len = g.row_ptr[a + 1] - lo;
-            if (best < 0 || len < blen) { best = 8 + j; blen = len; bcur = lo; }
+            if (best < 0 || len < blen) { best = FMT::BITS + j; blen = len; bcur = lo; }
         }
     }
     cur = bcur; end = bcur + blen;
-    if (DIR && best >= 8) { chk = desc; chk_in = din & ~(1u << (best - 8)); }
+    if (DIR && best >= FMT::BITS) { chk = desc; chk_in = din & ~(1u << (best - FMT::BITS)); }
     else chk = desc & ~(1u << best);
 }
-template <bool DIR = false>
+template <bool DIR = false, class FMT = SpNarrow>
 GSN_HD uint32_t sp_at(const SparseGraph &g, uint32_t desc, uint32_t din, uint32_t pos) {
-    return ((desc & 0xffu) || (DIR && (din & 0xffu))) ? g.nbr[pos] : pos;
+    return ((desc & FMT::MASK) || (DIR && (din & FMT::MASK))) ? g.nbr[pos] : pos;
 }
 
-// number of candidates of a level with masks `desc` / `din` (images 0 .. nimg - 1 placed) that, with `both`, also satisfy `desc2` / `din2`
-template <bool DIR = false>
-GSN_HD uint64_t sp_count_level(const SparseGraph &g, const uint32_t *st, int ss, uint32_t desc, uint32_t din, int nimg, bool both = false,
-                               uint32_t desc2 = 0, uint32_t din2 = 0) {
+// number of candidates of a level with masks `desc` / `din` / `ord` (images 0 .. nimg - 1 placed) that, with `both`, also satisfy
+// `desc2` / `din2` / `ord2`
+template <bool DIR = false, class FMT = SpNarrow>
+GSN_HD uint64_t sp_count_level(const SparseGraph &g, const uint32_t *st, int ss, uint32_t desc, uint32_t din, uint32_t ord, int nimg,
+                               bool both = false, uint32_t desc2 = 0, uint32_t din2 = 0, uint32_t ord2 = 0) {
     uint32_t cur, end, chk, chk_in;
-    sp_open<DIR>(g, st, ss, desc, din, cur, end, chk, chk_in);
+    sp_open<DIR, FMT>(g, st, ss, desc, din, cur, end, chk, chk_in);
     uint64_t c = 0;
     for (; cur < end; ++cur) {
-        const uint32_t v = sp_at<DIR>(g, desc, din, cur);
-        if (!sp_accept<DIR>(g, st, ss, chk, chk_in, nimg, v)) continue;
-        if (both && !sp_masks_hold<DIR>(g, st, ss, desc2, din2, v)) continue;
+        const uint32_t v = sp_at<DIR, FMT>(g, desc, din, cur);
+        if (!sp_accept<DIR, FMT>(g, st, ss, chk, chk_in, ord, nimg, v)) continue;
+        if (both && !sp_masks_hold<DIR, FMT>(g, st, ss, desc2, din2, ord2, v)) continue;
         ++c;
     }
     return c;
@@ -187,6 +215,7 @@ struct SparseLane {
 };
 
 // the roots: r0 = level 0, r1 = level 1 (plans with two fixed levels)
+template <class FMT = SpNarrow>
 GSN_HD void sp_begin(SparseLane &s, const uint32_t *plan, uint32_t r0, uint32_t r1, uint32_t *st, int ss) {
     s.plan = plan;
     s.k = (int)(plan[0] & 0xffu); s.nfix = (int)((plan[0] >> 8) & 0xffu);
@@ -202,16 +231,16 @@ GSN_HD void sp_begin(SparseLane &s, const uint32_t *plan, uint32_t r0, uint32_t 
     s.enter = true;
 }
 
-template <bool DIR = false>
+template <bool DIR = false, class FMT = SpNarrow>
 GSN_HD void sp_step(const SparseGraph &g, SparseLane &s, uint32_t *st, int ss) {
     const int l = s.l, k = s.k;
-    const uint32_t desc = s.plan[2 + l], din = DIR ? s.plan[PLAN_STRIDE_WORDS + l] : 0u;
+    const uint32_t desc = s.plan[2 + l], din = DIR ? s.plan[FMT::IN_OFF + l] : 0u, ord = FMT::ORD_WORD ? s.plan[FMT::ORD_OFF + l] : 0u;
     if (s.enter) {
         s.enter = false;
         if (l == k - 1) {
-            s.cnt += sp_count_level<DIR>(g, st, ss, desc, din, l);
+            s.cnt += sp_count_level<DIR, FMT>(g, st, ss, desc, din, ord, l);
         } else if (s.tm == 2 && l == s.tl) {     // r twin levels: any r of the candidates, in one order
-            const uint64_t n1 = sp_count_level<DIR>(g, st, ss, desc, din, l);
+            const uint64_t n1 = sp_count_level<DIR, FMT>(g, st, ss, desc, din, ord, l);
             const int r = 2 + (int)(s.plan[1] >> 30);
             if (n1 >= (uint64_t)r) {
                 uint64_t c = 1;
@@ -219,12 +248,15 @@ GSN_HD void sp_step(const SparseGraph &g, SparseLane &s, uint32_t *st, int ss) {
                 s.cnt += c;
             }
         } else if (s.tm == 1 && l == s.tl) {     // the last level's masks do not name level k - 2: pairs minus the coinciding ones
-            const uint32_t d2 = s.plan[2 + k - 1], d2in = DIR ? s.plan[PLAN_STRIDE_WORDS + k - 1] : 0u;
-            const uint64_t n1 = sp_count_level<DIR>(g, st, ss, desc, din, l);
-            if (n1) s.cnt += n1 * sp_count_level<DIR>(g, st, ss, d2, d2in, l) - sp_count_level<DIR>(g, st, ss, desc, din, l, true, d2, d2in);
+            const uint32_t d2 = s.plan[2 + k - 1], d2in = DIR ? s.plan[FMT::IN_OFF + k - 1] : 0u;
+            const uint32_t ord2 = FMT::ORD_WORD ? s.plan[FMT::ORD_OFF + k - 1] : 0u;
+            const uint64_t n1 = sp_count_level<DIR, FMT>(g, st, ss, desc, din, ord, l);
+            if (n1)
+                s.cnt += n1 * sp_count_level<DIR, FMT>(g, st, ss, d2, d2in, ord2, l) -
+                         sp_count_level<DIR, FMT>(g, st, ss, desc, din, ord, l, true, d2, d2in, ord2);
         } else {
             uint32_t cur, end, chk, chk_in;
-            sp_open<DIR>(g, st, ss, desc, din, cur, end, chk, chk_in);
+            sp_open<DIR, FMT>(g, st, ss, desc, din, cur, end, chk, chk_in);
             GSN_SP(SP_CUR, l) = cur; GSN_SP(SP_END, l) = end; GSN_SP(SP_CHK, l) = chk;
             if (DIR) GSN_SP(SP_CHK_IN, l) = chk_in;
             return;
@@ -238,32 +270,33 @@ GSN_HD void sp_step(const SparseGraph &g, SparseLane &s, uint32_t *st, int ss) {
         return;
     }
     GSN_SP(SP_CUR, l) = cur + 1;
-    const uint32_t v = sp_at<DIR>(g, desc, din, cur);
-    if (!sp_accept<DIR>(g, st, ss, GSN_SP(SP_CHK, l), DIR ? GSN_SP(SP_CHK_IN, l) : 0u, l, v)) return;
+    const uint32_t v = sp_at<DIR, FMT>(g, desc, din, cur);
+    if (!sp_accept<DIR, FMT>(g, st, ss, GSN_SP(SP_CHK, l), DIR ? GSN_SP(SP_CHK_IN, l) : 0u, ord, l, v)) return;
     GSN_SP(SP_IMG, l) = v;
     s.l = l + 1;
     s.enter = true;
 }
 
 // the number of maps of one plan
-template <bool DIR = false>
+template <bool DIR = false, class FMT = SpNarrow>
 GSN_HD uint64_t sp_search(const SparseGraph &g, const uint32_t *plan, uint32_t r0, uint32_t r1, uint32_t *st, int ss) {
     SparseLane s;
     s.cnt = 0; s.tm = 0; s.tl = -1;
-    sp_begin(s, plan, r0, r1, st, ss);
-    while (s.l >= 0) sp_step<DIR>(g, s, st, ss);
+    sp_begin<FMT>(s, plan, r0, r1, st, ss);
+    while (s.l >= 0) sp_step<DIR, FMT>(g, s, st, ss);
     return s.cnt;
 }
 
 // one cell: the plans col_ptr[col] .. col_ptr[col + 1] of the table all add to output column `col`.  DIR must agree with the table's
-// header (table[6] & 2): it sets the plan stride and the size of st (SP_FIELDS_DIRECTED * SP_LEVELS words, else SP_FIELDS * SP_LEVELS)
-template <bool DIR = false>
+// header (table[6] & 2): it sets the plan stride and the size of st (SP_FIELDS_DIRECTED * FMT::LEVELS words, else SP_FIELDS * FMT::LEVELS);
+// FMT must agree with its magic word
+template <bool DIR = false, class FMT = SpNarrow>
 GSN_HD uint64_t sp_cell(const SparseGraph &g, const uint32_t *table, int col, uint32_t r0, uint32_t r1, uint32_t *st, int ss) {
-    constexpr int stride = DIR ? PLAN_STRIDE_DIRECTED : PLAN_STRIDE_WORDS;
+    constexpr int stride = DIR ? FMT::STRIDE_DIRECTED : FMT::STRIDE;
     const uint32_t *col_ptr = table + PLAN_HEADER_WORDS;
     const uint32_t *plans = table + table[7];
     uint64_t cnt = 0;
-    for (uint32_t p = col_ptr[col]; p < col_ptr[col + 1]; ++p) cnt += sp_search<DIR>(g, plans + (size_t)p * stride, r0, r1, st, ss);
+    for (uint32_t p = col_ptr[col]; p < col_ptr[col + 1]; ++p) cnt += sp_search<DIR, FMT>(g, plans + (size_t)p * stride, r0, r1, st, ss);
     return cnt;
 }
 

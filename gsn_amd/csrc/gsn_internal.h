@@ -34,6 +34,27 @@ static_assert(GSN_KMAX <= 9, "level masks are 8 bits wide: the last level may be
 constexpr int PLAN_STRIDE_DIRECTED = PLAN_STRIDE_WORDS + GSN_KMAX;
 inline int plan_stride(uint32_t flags) { return (flags & 2u) ? PLAN_STRIDE_DIRECTED : PLAN_STRIDE_WORDS; }
 
+// WIDE plan table: pattern lists whose largest pattern has 10 .. GSN_KMAX_WIDE = 16 vertices (gsn_count_plan_build with GSN_FLAG_WIDE).
+// Executed by the sparse kernel only (count_sparse.hip: sparse_search_kernel<DIR, true>); its magic word makes every consumer of the narrow
+// table refuse it.  Header, col_ptr and col_order as above (header[5] = kmax > GSN_KMAX); ALL plans of the table, those of its <= 9-vertex
+// patterns included, are wide records:
+//   plan p : at plans_off + p*plan_stride_wide(header[6]): [0] k | n_fixed<<8 | out_col<<16   [1] pattern | root_a<<16 | root_b<<24 |
+//            tail_mode<<28 | (twin_run - 2)<<30 as in the narrow record (min_degree = 0: cores, like distance balls, are pruning hints of
+//            the LDS kernel and are left out -- the tail mode is therefore decided without them)
+//            [2 + l]                        level l: adj_mask | nonadj_mask<<16          (bit j = earlier level j, j <= 14)
+//            [2 + GSN_KMAX_WIDE + l]        level l: gt_mask | lt_mask<<16
+//            directed patterns only: [2 + 2 GSN_KMAX_WIDE + l]  level l: in_adj_mask | in_nonadj_mask<<16
+// A search holds levels 0 .. 14 (the sixteenth is counted, never placed), so 15 bits of every 16-bit field are used.
+constexpr uint32_t PLAN_MAGIC_WIDE = 0x47534e32u;  // 'GSN2'
+constexpr int PLAN_WIDE_ORD_OFF = 2 + GSN_KMAX_WIDE;
+constexpr int PLAN_WIDE_IN_OFF = 2 + 2 * GSN_KMAX_WIDE;
+constexpr int PLAN_STRIDE_WIDE = 2 + 2 * GSN_KMAX_WIDE;
+constexpr int PLAN_STRIDE_WIDE_DIRECTED = 2 + 3 * GSN_KMAX_WIDE;
+static_assert(GSN_KMAX_WIDE <= 16, "wide level masks are 16 bits wide: the last level may be the sixteenth, no more");
+inline int plan_stride_wide(uint32_t flags) { return (flags & 2u) ? PLAN_STRIDE_WIDE_DIRECTED : PLAN_STRIDE_WIDE; }
+// what every entry but gsn_count_sparse_hip answers to a wide table (GSN_E_UNSUPPORTED)
+#define GSN_WIDE_PLAN_REFUSAL "wide plan (patterns of more than 9 vertices): gsn_count_sparse_hip only"
+
 int set_error(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
 // "done once per DEVICE" flag for per-device kernel attributes (hipFuncSetAttribute applies to the current device only; a

@@ -2,7 +2,7 @@
 //
 // Product code.  Mirrors the *results* of utils_graph_processing.automorphism_orbits (:10-56) and
 // induced_edge_automorphism_orbits (:58-100) of the reference, computed here by a direct permutation search over the
-// <= 8 pattern vertices (no graph-tool), and compiles each pattern into rooted search plans for the HIP kernel:
+// <= 16 pattern vertices (no graph-tool), and compiles each pattern into rooted search plans for the HIP kernel:
 //
 //   vertex mode: counts[v, o] = #occurrences of H that contain v at a position of vertex orbit o
 //                             = #maps f with f(rep_o) = v that satisfy the symmetry-breaking constraints of Stab(rep_o)
@@ -20,12 +20,18 @@
 
 namespace gsn {
 
+constexpr int KW = GSN_KMAX_WIDE;                // the host analysis handles 16 vertices; what a TABLE may hold is gsn_count_plan_build's matter
+// Every automorphism is stored (the reference does the same: generator=False, utils_graph_processing.py:22).  The cap is a condition,
+// not a measurement: every pattern of <= 9 vertices stays below it (K9, star_graph(9): 362 880), star_graph(10) and K10 (3 628 800) do not.
+constexpr size_t AUT_CAP = (size_t)1 << 20;
+constexpr uint64_t AUT_COUNT_STOP = (uint64_t)1 << 24;   // a pattern beyond the cap is still counted up to here, for the message
+
 struct Pattern {
     int k = 0;
     bool directed = false;                       // main.py --directed: the rows of the edge list are arcs
-    uint16_t adj[GSN_KMAX] = {0};                // adj[i] bit j: edge {i,j} (both rows) or, directed, arc i -> j
-    std::vector<std::array<uint8_t, GSN_KMAX>> aut;  // all automorphisms sigma: sigma[i] = image of i
-    int vorbit[GSN_KMAX] = {0};
+    uint16_t adj[KW] = {0};                      // adj[i] bit j: edge {i,j} (both rows) or, directed, arc i -> j
+    std::vector<std::array<uint8_t, KW>> aut;        // all automorphisms sigma: sigma[i] = image of i
+    int vorbit[KW] = {0};
     int n_vorbits = 0;
     std::vector<std::pair<int, int>> arcs;       // sorted directed edges
     std::vector<int> arc_class;                  // reference's "induced" edge orbit id per arc
@@ -36,22 +42,27 @@ static bool has(const Pattern &P, int i, int j) { return (P.adj[i] >> j) & 1; }
 static bool linked(const Pattern &P, int i, int j) { return has(P, i, j) || has(P, j, i); }   // adjacent in the underlying graph
 
 // all edge- (arc-) preserving bijections V(H)->V(H)  (= non-induced self-monomorphisms, which for equal edge counts are automorphisms)
-static void enum_aut(const Pattern &P, int l, std::array<uint8_t, GSN_KMAX> &sigma, unsigned used,
-                     std::vector<std::array<uint8_t, GSN_KMAX>> &out) {
-    if (l == P.k) { out.push_back(sigma); return; }
-    for (int v = 0; v < P.k; ++v) {
+// *total counts them all; beyond AUT_CAP they are no longer stored, and the enumeration stops at AUT_COUNT_STOP
+static void enum_aut(const Pattern &P, int l, std::array<uint8_t, KW> &sigma, unsigned used,
+                     std::vector<std::array<uint8_t, KW>> &out, uint64_t *total) {
+    if (l == P.k) {
+        if (++*total <= AUT_CAP) out.push_back(sigma);
+        return;
+    }
+    for (int v = 0; v < P.k && *total < AUT_COUNT_STOP; ++v) {
         if ((used >> v) & 1) continue;
         bool ok = true;
         for (int j = 0; j < l && ok; ++j)
             if ((has(P, l, j) && !has(P, v, sigma[j])) || (has(P, j, l) && !has(P, sigma[j], v))) ok = false;
         if (!ok) continue;
         sigma[l] = (uint8_t)v;
-        enum_aut(P, l + 1, sigma, used | (1u << v), out);
+        enum_aut(P, l + 1, sigma, used | (1u << v), out, total);
     }
 }
 
 // flags: bit 0 = directed_orbits (edge classes keep the order of the two vertex orbits), bit 1 = directed (digraph pattern)
-static int analyse(int64_t n_edges, const int64_t *edges, int flags, Pattern &P) {
+// kmax: the most vertices the caller takes (GSN_KMAX, or GSN_KMAX_WIDE)
+static int analyse(int64_t n_edges, const int64_t *edges, int flags, int kmax, Pattern &P) {
     const int directed_orbits = flags & 1;
     P.directed = (flags & 2) != 0;
     int64_t mx = -1;
@@ -59,7 +70,7 @@ static int analyse(int64_t n_edges, const int64_t *edges, int flags, Pattern &P)
         if (edges[i] < 0) return set_error(GSN_E_INVALID, "pattern vertex id < 0");
         mx = std::max(mx, edges[i]);
     }
-    if (mx + 1 > GSN_KMAX) return set_error(GSN_E_UNSUPPORTED, "pattern has %lld vertices; this build handles k <= %d", (long long)(mx + 1), GSN_KMAX);
+    if (mx + 1 > kmax) return set_error(GSN_E_UNSUPPORTED, "pattern has %lld vertices; this build handles k <= %d", (long long)(mx + 1), kmax);
     if (mx < 0) return set_error(GSN_E_INVALID, "empty pattern edge list");
     P.k = (int)mx + 1;
     for (int64_t i = 0; i < n_edges; ++i) {
@@ -68,10 +79,14 @@ static int analyse(int64_t n_edges, const int64_t *edges, int flags, Pattern &P)
         P.adj[u] |= (uint16_t)(1u << v);
         if (!P.directed) P.adj[v] |= (uint16_t)(1u << u);
     }
-    std::array<uint8_t, GSN_KMAX> sigma{};
-    enum_aut(P, 0, sigma, 0, P.aut);
+    std::array<uint8_t, KW> sigma{};
+    uint64_t n_aut = 0;
+    enum_aut(P, 0, sigma, 0, P.aut, &n_aut);
+    if (n_aut > AUT_CAP)
+        return set_error(GSN_E_UNSUPPORTED, "pattern of %d vertices has %s%llu automorphisms; every one is stored, at most %llu", P.k,
+                         n_aut >= AUT_COUNT_STOP ? "more than " : "", (unsigned long long)n_aut, (unsigned long long)AUT_CAP);
     // vertex orbits: orbit id = rank of the orbit's smallest vertex (np.unique(..., return_inverse) on the per-vertex minima)
-    int minrep[GSN_KMAX];
+    int minrep[KW];
     for (int v = 0; v < P.k; ++v) minrep[v] = v;
     for (auto &s : P.aut)
         for (int i = 0; i < P.k; ++i) minrep[s[i]] = std::min(minrep[s[i]], i);
@@ -100,9 +115,12 @@ static int analyse(int64_t n_edges, const int64_t *edges, int flags, Pattern &P)
 
 struct Plan {
     int k, n_fixed, out_col, pattern, root_a, root_b, min_degree;
-    uint32_t level[GSN_KMAX];
-    uint32_t level_in[GSN_KMAX];     // directed patterns: the constraints through arcs that LEAVE the level's vertex
-    uint8_t ball[GSN_KMAX];
+    uint16_t adj[KW], nonadj[KW], gt[KW], lt[KW];    // per level, bit j = earlier level j
+    uint16_t in_adj[KW], in_nonadj[KW];              // directed patterns: the constraints through arcs that LEAVE the level's vertex
+    uint8_t ball[KW];
+    // the words of the narrow record (gsn_internal.h): 8-bit fields, k <= GSN_KMAX
+    uint32_t level(int l) const { return (uint32_t)adj[l] | ((uint32_t)nonadj[l] << 8) | ((uint32_t)gt[l] << 16) | ((uint32_t)lt[l] << 24); }
+    uint32_t level_in(int l) const { return (uint32_t)in_adj[l] | ((uint32_t)in_nonadj[l] << 8); }
 };
 
 // Closed form for the LAST TWO levels (count_core.h, lane_step): when the last level's constraints do not name the level before it, the
@@ -119,16 +137,16 @@ struct Plan {
 // side that level a has: v > u > f_j makes them hold)?  Returns +1 (b > a), -1 (b < a) or 0.
 static int twin_link(const Plan &pl, bool directed, int a) {
     const int b = a + 1;
-    const uint32_t bit = 1u << a, d1 = pl.level[b], d2 = pl.level[a];
-    const bool ref_adj = (d1 & bit) != 0, ref_non = ((d1 >> 8) & bit) != 0, ref_gt = ((d1 >> 16) & bit) != 0, ref_lt = ((d1 >> 24) & bit) != 0;
+    const uint32_t bit = 1u << a;
+    const bool ref_adj = (pl.adj[b] & bit) != 0, ref_non = (pl.nonadj[b] & bit) != 0, ref_gt = (pl.gt[b] & bit) != 0, ref_lt = (pl.lt[b] & bit) != 0;
     const bool ball_ref = (pl.ball[b] >> 3) != 0 && (pl.ball[b] & 7) == a;
-    const bool in_ref = directed && ((pl.level_in[b] & bit) != 0 || ((pl.level_in[b] >> 8) & bit) != 0);
+    const bool in_ref = directed && ((pl.in_adj[b] & bit) != 0 || (pl.in_nonadj[b] & bit) != 0);
     if (ref_adj || ref_non || ball_ref || in_ref || ref_gt == ref_lt) return 0;
-    const uint32_t d1c = d1 & ~((bit << 16) | (bit << 24));
-    const bool same_adj = (d1c & 0xffffu) == (d2 & 0xffffu);
-    const uint32_t gt1 = (d1c >> 16) & 0xffu, lt1 = d1c >> 24, gt2 = (d2 >> 16) & 0xffu, lt2 = d2 >> 24;
+    const bool same_adj = pl.adj[b] == pl.adj[a] && pl.nonadj[b] == pl.nonadj[a];
+    const uint32_t gt1 = pl.gt[b] & ~bit, lt1 = pl.lt[b] & ~bit, gt2 = pl.gt[a], lt2 = pl.lt[a];
     const bool order_ok = ref_gt ? ((gt1 & ~gt2) == 0 && lt1 == lt2) : ((lt1 & ~lt2) == 0 && gt1 == gt2);
-    if (!(same_adj && order_ok && pl.ball[b] == pl.ball[a] && (!directed || pl.level_in[b] == pl.level_in[a]))) return 0;
+    const bool same_in = pl.in_adj[b] == pl.in_adj[a] && pl.in_nonadj[b] == pl.in_nonadj[a];
+    if (!(same_adj && order_ok && pl.ball[b] == pl.ball[a] && (!directed || same_in))) return 0;
     return ref_gt ? 1 : -1;
 }
 
@@ -138,11 +156,11 @@ static int plan_tail_mode(const Plan &pl, bool directed, int *twin_run) {
     *twin_run = 2;
     if (pl.k - pl.n_fixed < 2) return 0;
     const int a = pl.k - 2, b = pl.k - 1;
-    const uint32_t bit = 1u << a, d1 = pl.level[b];
-    if (!directed && (d1 & 0xffu) == bit && ((d1 >> 8) & 0xffu) == 0 && (d1 >> 16) == 0) return 3;
-    const bool ref_adj = (d1 & bit) != 0, ref_non = ((d1 >> 8) & bit) != 0, ref_gt = ((d1 >> 16) & bit) != 0, ref_lt = ((d1 >> 24) & bit) != 0;
+    const uint32_t bit = 1u << a;
+    if (!directed && pl.adj[b] == bit && pl.nonadj[b] == 0 && pl.gt[b] == 0 && pl.lt[b] == 0) return 3;
+    const bool ref_adj = (pl.adj[b] & bit) != 0, ref_non = (pl.nonadj[b] & bit) != 0, ref_gt = (pl.gt[b] & bit) != 0, ref_lt = (pl.lt[b] & bit) != 0;
     const bool ball_ref = (pl.ball[b] >> 3) != 0 && (pl.ball[b] & 7) == a;
-    const bool in_ref = directed && ((pl.level_in[b] & bit) != 0 || ((pl.level_in[b] >> 8) & bit) != 0);
+    const bool in_ref = directed && ((pl.in_adj[b] & bit) != 0 || (pl.in_nonadj[b] & bit) != 0);
     if (ref_adj || ref_non || ball_ref || in_ref) return 0;
     if (!ref_gt && !ref_lt) return 1;
     if (const int dir = twin_link(pl, directed, a)) {
@@ -158,7 +176,7 @@ static int plan_tail_mode(const Plan &pl, bool directed, int *twin_run) {
 // Matching order: fixed roots first, then greedily the unplaced vertex with most placed neighbours (ties: higher degree,
 // lower id) so candidate sets shrink as early as possible.
 static void matching_order(const Pattern &P, const int *fixed, int n_fixed, int *order) {
-    bool placed[GSN_KMAX] = {false};
+    bool placed[KW] = {false};
     for (int i = 0; i < n_fixed; ++i) { order[i] = fixed[i]; placed[fixed[i]] = true; }
     for (int l = n_fixed; l < P.k; ++l) {
         int best = -1, best_conn = -1, best_deg = -1;
@@ -179,7 +197,7 @@ static void matching_order(const Pattern &P, const int *fixed, int n_fixed, int 
 // descend to the stabiliser of v.  Exactly one map of every A-class satisfies all constraints.
 static void symmetry_constraints(const Pattern &P, const int *fixed, int n_fixed, const int *order,
                                  std::vector<std::pair<int, int>> &less /* f(first) < f(second) */) {
-    std::vector<std::array<uint8_t, GSN_KMAX>> A;
+    std::vector<std::array<uint8_t, KW>> A;
     for (auto &s : P.aut) {
         bool ok = true;
         for (int i = 0; i < n_fixed; ++i) ok = ok && s[fixed[i]] == fixed[i];
@@ -191,30 +209,32 @@ static void symmetry_constraints(const Pattern &P, const int *fixed, int n_fixed
             for (auto &s : A)
                 if (s[order[l]] != order[l]) { v = order[l]; break; }
         if (v < 0) break;
-        bool in_orbit[GSN_KMAX] = {false};
+        bool in_orbit[KW] = {false};
         for (auto &s : A) in_orbit[s[v]] = true;
         for (int u = 0; u < P.k; ++u)
             if (u != v && in_orbit[u]) less.push_back({v, u});
-        std::vector<std::array<uint8_t, GSN_KMAX>> S;
+        std::vector<std::array<uint8_t, KW>> S;
         for (auto &s : A)
             if (s[v] == v) S.push_back(s);
         A.swap(S);
     }
 }
 
-static Plan make_plan(const Pattern &P, int pattern_id, const int *fixed, int n_fixed, int out_col, bool induced) {
+// wide: a record of the wide table -- no core degree and no distance balls (pruning hints of the LDS kernel, which never sees the table),
+// so that the tail mode is decided without them
+static Plan make_plan(const Pattern &P, int pattern_id, const int *fixed, int n_fixed, int out_col, bool induced, bool wide) {
     Plan pl{};
     pl.k = P.k; pl.n_fixed = n_fixed; pl.out_col = out_col; pl.pattern = pattern_id;
     pl.root_a = fixed[0]; pl.root_b = n_fixed > 1 ? fixed[1] : 0;
     // every image has at least min-degree(H) neighbours among the images, so all images lie in that core of the target
-    pl.min_degree = GSN_KMAX;
+    pl.min_degree = KW;
     for (int v = 0; v < P.k; ++v) {
         int dv = 0;
         for (int u = 0; u < P.k; ++u) dv += (u != v && has(P, v, u)) ? 1 : 0;
         pl.min_degree = std::min(pl.min_degree, dv);
     }
-    if (P.directed) pl.min_degree = 0;   // (core and distance pruning are defined on undirected targets only)
-    int order[GSN_KMAX], pos[GSN_KMAX];
+    if (P.directed || wide) pl.min_degree = 0;   // (core and distance pruning are defined on undirected targets only)
+    int order[KW], pos[KW];
     matching_order(P, fixed, n_fixed, order);
     for (int l = 0; l < P.k; ++l) pos[order[l]] = l;
     std::vector<std::pair<int, int>> less;
@@ -231,25 +251,25 @@ static Plan make_plan(const Pattern &P, int pattern_id, const int *fixed, int n_
                 else if (induced) nonadj_in |= 1u << j;
             }
         }
-        pl.level_in[l] = adj_in | (nonadj_in << 8);
+        pl.in_adj[l] = (uint16_t)adj_in; pl.in_nonadj[l] = (uint16_t)nonadj_in;
         for (auto &c : less) {
             // f(c.first) < f(c.second)
             if (c.second == order[l] && pos[c.first] < l) gt |= 1u << pos[c.first];   // f_l > f_j
             if (c.first == order[l] && pos[c.second] < l) lt |= 1u << pos[c.second];  // f_l < f_j
         }
-        pl.level[l] = adj | (nonadj << 8) | (gt << 16) | (lt << 24);
+        pl.adj[l] = (uint16_t)adj; pl.nonadj[l] = (uint16_t)nonadj; pl.gt[l] = (uint16_t)gt; pl.lt[l] = (uint16_t)lt;
     }
     // Distance pruning: a subgraph isomorphism maps a path of the pattern onto a path of the target, so
     // dist_G(f(a), f(b)) <= dist_H(a, b).  Per level keep the tightest such bound of radius 2 or 3 against an earlier level
     // (radius 1 is the adjacency mask itself); the kernel intersects the candidates with the r-hop ball of that image.
-    int dist[GSN_KMAX][GSN_KMAX];
+    int dist[KW][KW];
     for (int a = 0; a < P.k; ++a)
         for (int b = 0; b < P.k; ++b) dist[a][b] = a == b ? 0 : (has(P, a, b) ? 1 : 99);
     for (int m = 0; m < P.k; ++m)
         for (int a = 0; a < P.k; ++a)
             for (int b = 0; b < P.k; ++b) dist[a][b] = std::min(dist[a][b], dist[a][m] + dist[m][b]);
-    for (int l = 0; l < GSN_KMAX; ++l) pl.ball[l] = 0;
-    for (int l = n_fixed; l < P.k && !P.directed; ++l) {
+    for (int l = 0; l < KW; ++l) pl.ball[l] = 0;
+    for (int l = n_fixed; l < P.k && !P.directed && !wide; ++l) {
         int best_j = -1, best_r = 99;
         for (int j = 0; j < l; ++j) {
             const int d = dist[order[l]][order[j]];
@@ -284,7 +304,7 @@ extern "C" int gsn_pattern_orbits(int64_t n_edges, const int64_t *edges, int dir
                                   int64_t *out_aut_count) {
     if (!edges || n_edges <= 0) return set_error(GSN_E_INVALID, "gsn_pattern_orbits: no edges");
     Pattern P;
-    int rc = analyse(n_edges, edges, directed_orbits, P);
+    int rc = analyse(n_edges, edges, directed_orbits, GSN_KMAX_WIDE, P);
     if (rc) return rc;
     if (out_k) *out_k = P.k;
     if (out_vertex_orbit) for (int v = 0; v < P.k; ++v) out_vertex_orbit[v] = P.vorbit[v];
@@ -384,19 +404,24 @@ extern "C" int gsn_count_plan_build(int mode, int induced, int directed_orbits, 
     const bool directed = (directed_orbits & 2) != 0;
     if (directed && mode == GSN_MODE_EDGE)
         return set_error(GSN_E_UNSUPPORTED, "directed patterns: vertex counts only (the reference's directed edge counter fails on an unbound name, utils_graph_processing.py:146 vs :164)");
-    const int stride = plan_stride((uint32_t)directed_orbits);
+    // GSN_FLAG_WIDE admits patterns of up to GSN_KMAX_WIDE vertices; the table is a wide one when one of them has more than GSN_KMAX
+    const int k_limit = (directed_orbits & GSN_FLAG_WIDE) ? GSN_KMAX_WIDE : GSN_KMAX;
+    int64_t k_list = 0;
+    for (int64_t i = 2 * pat_ptr[0]; i < 2 * pat_ptr[n_patterns]; ++i) k_list = std::max(k_list, pat_edges[i] + 1);
+    const bool wide = k_limit > GSN_KMAX && k_list > GSN_KMAX && k_list <= GSN_KMAX_WIDE;
+    const int stride = wide ? plan_stride_wide((uint32_t)directed_orbits) : plan_stride((uint32_t)directed_orbits);
     std::vector<Plan> plans;
     int col0 = 0, kmax = 0;
     for (int64_t p = 0; p < n_patterns; ++p) {
         Pattern P;
-        int rc = analyse(pat_ptr[p + 1] - pat_ptr[p], pat_edges + 2 * pat_ptr[p], directed_orbits, P);
+        int rc = analyse(pat_ptr[p + 1] - pat_ptr[p], pat_edges + 2 * pat_ptr[p], directed_orbits, k_limit, P);
         if (rc) return rc;
         kmax = std::max(kmax, P.k);
         if (mode == GSN_MODE_VERTEX) {
             for (int o = 0; o < P.n_vorbits; ++o) {
                 int rep = 0;
                 while (P.vorbit[rep] != o) ++rep;  // smallest vertex of the orbit
-                plans.push_back(make_plan(P, (int)p, &rep, 1, col0 + o, induced != 0));
+                plans.push_back(make_plan(P, (int)p, &rep, 1, col0 + o, induced != 0, wide));
             }
             col0 += P.n_vorbits;
         } else {
@@ -404,7 +429,7 @@ extern "C" int gsn_count_plan_build(int mode, int induced, int directed_orbits, 
             arc_orbits(P, reps);
             for (int r : reps) {
                 int fixed[2] = {P.arcs[r].first, P.arcs[r].second};
-                plans.push_back(make_plan(P, (int)p, fixed, 2, col0 + P.arc_class[r], induced != 0));
+                plans.push_back(make_plan(P, (int)p, fixed, 2, col0 + P.arc_class[r], induced != 0, wide));
             }
             col0 += P.n_classes;
         }
@@ -417,7 +442,7 @@ extern "C" int gsn_count_plan_build(int mode, int induced, int directed_orbits, 
     if (out_n_cols) *out_n_cols = col0;
     if (!plan) return GSN_OK;
     if (capacity < words) return set_error(GSN_E_NOSPACE, "plan buffer too small: need %lld words", (long long)words);
-    plan[0] = PLAN_MAGIC; plan[1] = (uint32_t)mode; plan[2] = (uint32_t)(induced != 0); plan[3] = (uint32_t)plans.size();
+    plan[0] = wide ? PLAN_MAGIC_WIDE : PLAN_MAGIC; plan[1] = (uint32_t)mode; plan[2] = (uint32_t)(induced != 0); plan[3] = (uint32_t)plans.size();
     plan[4] = (uint32_t)col0; plan[5] = (uint32_t)kmax; plan[6] = (uint32_t)((directed_orbits & 1) | (directed ? 2 : 0)); plan[7] = (uint32_t)plans_off;
     {   // col_ptr[c] .. col_ptr[c+1]: plan indices of column c
         uint32_t *cp = plan + PLAN_HEADER_WORDS;
@@ -435,9 +460,8 @@ extern "C" int gsn_count_plan_build(int mode, int induced, int directed_orbits, 
         for (const Plan &pl : plans) {
             double c = 1.0;
             for (int l = pl.n_fixed; l + 1 < pl.k; ++l) {
-                const uint32_t d = pl.level[l], din = pl.level_in[l];
-                const int n_adj = __builtin_popcount(d & 0xffu) + __builtin_popcount(din & 0xffu);
-                const int n_ord = __builtin_popcount(d >> 16);
+                const int n_adj = __builtin_popcount(pl.adj[l]) + __builtin_popcount(pl.in_adj[l]);
+                const int n_ord = __builtin_popcount(pl.gt[l]) + __builtin_popcount(pl.lt[l]);
                 double b = n_adj == 0 ? 24.0 : 4.0 / n_adj;
                 if (n_ord) b *= 0.5;
                 c *= b < 1.0 ? 1.0 : b;
@@ -458,11 +482,19 @@ extern "C" int gsn_count_plan_build(int mode, int induced, int directed_orbits, 
         const int tail_mode = plan_tail_mode(pl, directed != 0, &twin_run);
         w[1] = (uint32_t)pl.pattern | ((uint32_t)pl.root_a << 16) | ((uint32_t)pl.min_degree << 20) | ((uint32_t)pl.root_b << 24) |
                ((uint32_t)tail_mode << 28) | ((uint32_t)(twin_run - 2) << 30);
-        for (int l = 0; l < GSN_KMAX; ++l) w[2 + l] = pl.level[l];
+        if (wide) {
+            for (int l = 0; l < GSN_KMAX_WIDE; ++l) {
+                w[2 + l] = (uint32_t)pl.adj[l] | ((uint32_t)pl.nonadj[l] << 16);
+                w[PLAN_WIDE_ORD_OFF + l] = (uint32_t)pl.gt[l] | ((uint32_t)pl.lt[l] << 16);
+                if (directed) w[PLAN_WIDE_IN_OFF + l] = (uint32_t)pl.in_adj[l] | ((uint32_t)pl.in_nonadj[l] << 16);
+            }
+            continue;
+        }
+        for (int l = 0; l < GSN_KMAX; ++l) w[2 + l] = pl.level(l);
         for (int l = 0; l < PLAN_BALL_WORDS; ++l) w[2 + GSN_KMAX + l] = 0;
         for (int l = 0; l < GSN_KMAX; ++l) w[2 + GSN_KMAX + l / 4] |= (uint32_t)pl.ball[l] << (8 * (l % 4));
         if (directed)
-            for (int l = 0; l < GSN_KMAX; ++l) w[PLAN_STRIDE_WORDS + l] = pl.level_in[l];
+            for (int l = 0; l < GSN_KMAX; ++l) w[PLAN_STRIDE_WORDS + l] = pl.level_in(l);
     }
     return GSN_OK;
 }

@@ -61,7 +61,8 @@ def prepare_graphs(graphs, subgraph_dicts, subgraph_params, regression, dataset_
         pats.append(sg)
     dirorb = any(p.directed_orbits for p in pats) if mode == "edge" else False
     directed = counting._directed_of(pats, directed)
-    plan = counting.CountPlan.get([p.edge_list for p in pats], mode, subgraph_params["induced"], dirorb, directed)
+    # (wide=True: patterns of 10 to 16 vertices give a wide table, which count_batch sends to the sparse kernel whatever the width class)
+    plan = counting.CountPlan.get([p.edge_list for p in pats], mode, subgraph_params["induced"], dirorb, directed, wide=True)
 
     span = (0, len(graphs))
     if shard is not None:
@@ -80,7 +81,8 @@ def prepare_graphs(graphs, subgraph_dicts, subgraph_params, regression, dataset_
     # class -- one launch per class that occurs, each over a contiguous range of the regrouped batch -- and handed back in the caller's order.
     # Graphs of more than 768 vertices are a class of their own: the LDS-resident kernel does not take them, the sparse kernel
     # (gsn_count_sparse_hip) counts them in a launch of its own.  A class whose launch the LDS kernel refuses for its size all the same
-    # (tables beyond its LDS, 65 535 columns in a graph) is repeated on the sparse kernel (count_batch: large="sparse").
+    # (tables beyond its LDS, 65 535 columns in a graph) is repeated on the sparse kernel (count_batch: large="sparse").  A wide plan
+    # (patterns of 10 to 16 vertices) puts every class on the sparse kernel, still one launch per class.
     order = None
     if len(graphs) > 1:
         cls = np.searchsorted(_WIDTH_CLASSES, np.array([int(g.node_features.shape[0]) for g in graphs]), side="left")

@@ -108,6 +108,8 @@ class CountLayerStep:
     def __init__(self, plan, layer, id_classes, clamp=True, force_packs=False):
         if plan.mode != "edge":
             raise ValueError("CountLayerStep: an edge-mode plan (GSN-e identifiers)")
+        if getattr(plan, "wide", False):
+            raise ValueError("CountLayerStep: wide plans count only (patterns of at most 9 vertices here)")
         self.plan, self.layer = plan, layer
         self.id_classes = [int(c) for c in id_classes]
         if len(self.id_classes) != plan.n_cols or min(self.id_classes) < 1:

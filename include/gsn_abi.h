@@ -25,13 +25,14 @@ extern "C" {
 #endif
 
 #define GSN_ABI_VERSION 1
-#define GSN_KMAX 9 /* max pattern vertices the counting kernel handles: --k 8 of star_graph is a 9-vertex pattern (utils.py:59-62) */
+#define GSN_KMAX 9 /* max pattern vertices the LDS-resident counting kernels handle: --k 8 of star_graph is a 9-vertex pattern (utils.py:59-62) */
+#define GSN_KMAX_WIDE 16 /* max pattern vertices of a wide plan table (GSN_FLAG_WIDE; gsn_count_sparse_hip only) and of gsn_pattern_orbits */
 #define GSN_SEG_RANGE_ROWS 16 /* rows one thread reduces in the fused scatter-add epilogue (see gsn_segsum_prepare_hip) */
 
 enum {
     GSN_OK = 0,
     GSN_E_INVALID = -1,     /* bad argument */
-    GSN_E_UNSUPPORTED = -2, /* valid in the reference but outside this build or this entry (e.g. k > GSN_KMAX; n > 768 in gsn_count_hip: INTEGRATION.md 11) */
+    GSN_E_UNSUPPORTED = -2, /* valid in the reference but outside this build or this entry (e.g. k > GSN_KMAX without GSN_FLAG_WIDE; n > 768 in gsn_count_hip: INTEGRATION.md 11) */
     GSN_E_HIP = -3,         /* HIP runtime error (message has hipGetErrorString) */
     GSN_E_NOSPACE = -4,     /* caller buffer too small */
     GSN_E_NODEVICE = -5     /* no gfx950 device visible */
@@ -78,11 +79,14 @@ int gsn_fingerprint_hip(int n_tensors, const int64_t *meta, int64_t max_words, u
  *                    reference's `directed` (main.py:558, utils_graph_processing.py:14-16) -- every row (u,v) of `edges` is the
  *                    ARC u -> v, automorphisms preserve arcs, out_arcs lists the arcs themselves
  *   edges            [n_edges][2] int64, vertices 0..k-1; self loops / duplicates are dropped like the reference does
- *   out_vertex_orbit [GSN_KMAX]
- *   out_arcs         [k*(k-1)][2]  sorted directed edge list;  out_arc_orbit [k*(k-1)]
+ *   out_vertex_orbit [GSN_KMAX_WIDE]  (patterns of up to GSN_KMAX_WIDE = 16 vertices, with or without GSN_FLAG_WIDE)
+ *   out_arcs         [k*(k-1)][2]  sorted directed edge list, at most 240 rows;  out_arc_orbit [k*(k-1)]
+ *   Every automorphism is stored while the orbits are taken; a pattern with more than 2^20 of them is GSN_E_UNSUPPORTED (the message
+ *   names the count).  Every pattern of <= 9 vertices stays below (K9, star_graph(9): 362 880); star_graph(10), K10 and larger do not.
  * ---------------------------------------------------------------------------------------------------------------- */
 #define GSN_FLAG_DIRECTED_ORBITS 1
 #define GSN_FLAG_DIRECTED 2
+#define GSN_FLAG_WIDE 4 /* gsn_count_plan_build only: admit patterns of 10 .. GSN_KMAX_WIDE vertices (see there) */
 int gsn_pattern_orbits(int64_t n_edges, const int64_t *edges, int directed_orbits, int64_t *out_k,
                        int64_t *out_vertex_orbit, int64_t *out_n_vertex_orbits, int64_t *out_arcs,
                        int64_t *out_arc_orbit, int64_t *out_n_arcs, int64_t *out_n_edge_orbits,
@@ -109,6 +113,10 @@ int gsn_graph_vertex_orbits(int64_t n_vertices, int64_t n_edges, const int64_t *
  *           GSN_E_UNSUPPORTED, the reference's directed edge counter dies on an unbound name, utils_graph_processing.py:146 vs
  *           :164): patterns AND the graphs later counted with this plan are digraphs (gt.Graph(directed=True), :108-113) -- a
  *           column (u,v) of edge_index is the arc u -> v, matches preserve arcs and, induced, non-arcs in each direction
+ *           GSN_FLAG_WIDE: patterns of up to GSN_KMAX_WIDE = 16 vertices are accepted (17 and more: GSN_E_UNSUPPORTED; without the bit
+ *           ten and more are).  A list whose largest pattern has <= GSN_KMAX vertices gives the same table as without the bit.  Otherwise
+ *           the WHOLE table is emitted in the wide format (16-bit level masks, another magic word): gsn_count_sparse_hip executes it, every
+ *           other entry that takes a plan table answers GSN_E_UNSUPPORTED.  The automorphism cap of gsn_pattern_orbits applies.
  *   pat_ptr [n_patterns+1] into pat_edges [.][2]
  *   plan    caller buffer of `capacity` uint32 words (call with plan=NULL to get *out_words)
  * ---------------------------------------------------------------------------------------------------------------- */
