@@ -144,6 +144,9 @@ SIGNATURES = {
     "gsn_one_hot_hip": (c_int, [c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),
     "gsn_column_range_hip": (c_int, [c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
     "gsn_column_ranks_hip": (c_int, [c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "gsn_unique_sort_scratch_bytes": (c_i64, [c_i64, c_i64]),
+    "gsn_unique_sort_hip": (c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "gsn_lookup_codes_hip": (c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     "gsn_embed_fwd_hip": (c_int, [c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "gsn_embed_bwd_hip": (c_int, [c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "gsn_embed_bwd_flat_supported": (c_int, [c_i64, c_int, c_int, c_vp]),

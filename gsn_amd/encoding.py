@@ -3,7 +3,9 @@
 Dataset level (run once, utils_encoding.py):
     :func:`encode`, :class:`one_hot_unique`, :class:`one_hot_max` -- same call signatures and results as the reference's;
     the per-column ``np.unique(..., return_inverse=True)`` over the whole dataset runs on the device
-    (gsn_column_range_hip / gsn_column_ranks_hip).
+    (gsn_column_range_hip / gsn_column_ranks_hip: a presence table while the value ranges allow it; gsn_unique_sort_hip: a sort over
+    the full int64 range beyond).  :meth:`one_hot_unique.transform` / :func:`lookup_codes` recode rows that were not in the dataset
+    with a fitted encoder (gsn_lookup_codes_hip).
 
 Model level (every forward, utils_graph_learning.py:44-208):
     :class:`DiscreteEmbedding` with the reference's encoder names, :class:`one_hot_encoder` (gsn_one_hot_hip),
@@ -61,29 +63,128 @@ def column_range(values):
     return mn, mx
 
 
-def unique_codes(values):
+def _unique_codes_sort(v):
+    """The sort path of :func:`unique_codes` on an int64 [M, C] device tensor (M, C > 0) -> device codes, d, device uniques per column."""
+    M, C = v.shape
+    dev = v.device
+    lib = _abi.lib()
+    nbytes = int(lib.gsn_unique_sort_scratch_bytes(M, C))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    uniq = torch.empty(C * M, dtype=torch.int64, device=dev)
+    nd = torch.empty(C, dtype=torch.int64, device=dev)
+    codes = torch.empty_like(v)
+    with _abi.device_guard(dev):
+        rc = lib.gsn_unique_sort_hip(M, C, v.data_ptr(), uniq.data_ptr(), nd.data_ptr(), codes.data_ptr(), scratch.data_ptr(), nbytes,
+                                     _abi.current_stream())
+    _abi.check(rc, "gsn_unique_sort_hip")
+    d = [int(x) for x in nd.cpu().tolist()]                     # one host read: the lengths of the distinct-value lists
+    return codes, d, [uniq[c * M:c * M + d[c]] for c in range(C)]
+
+
+def unique_codes(values, wide="refuse", return_uniques=False):
     """Per-column dense ranks: ``(codes int64 [M, C], d list[int])`` with ``codes[:, c] = np.unique(values[:, c],
-    return_inverse=True)[1]`` and ``d[c]`` the number of distinct values.  ``values``: integer [M, C] tensor, any device."""
+    return_inverse=True)[1]`` and ``d[c]`` the number of distinct values.  ``values``: integer [M, C] tensor, any device.
+
+    ``wide`` says what happens when the columns' value ranges together pass ``MAX_TABLE_ELEMS`` presence-table entries:
+    ``"refuse"`` raises NotImplementedError (the table path only), ``"auto"`` takes the table path where it is allowed and the sort path
+    (gsn_unique_sort_hip: any int64 range) beyond, ``"sort"`` always sorts.  ``return_uniques``: also return the sorted distinct values
+    of every column, a list of int64 CPU tensors (``np.unique(values[:, c])``)."""
+    if wide not in ("refuse", "auto", "sort"):
+        raise ValueError("unique_codes: wide must be 'refuse', 'auto' or 'sort', not %r" % (wide,))
     dev = _device()
     v = _as_int_matrix(values).to(dev).contiguous()
     M, C = v.shape
-    if M == 0:
-        return torch.zeros((0, C), dtype=torch.int64), [0] * C
-    mn, mx = column_range(v)
-    mn_h, mx_h = mn.cpu().numpy(), mx.cpu().numpy()          # one host read: sizes the presence tables
-    sizes = (mx_h - mn_h + 1).astype(np.int64)
-    base = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    if int(base[-1]) > MAX_TABLE_ELEMS:
-        raise NotImplementedError("value range too wide for table recoding (%d entries > %d)" % (int(base[-1]), MAX_TABLE_ELEMS))
-    base_d = torch.from_numpy(base).to(dev)
-    table = torch.empty(int(base[-1]), dtype=torch.int32, device=dev)
+    if M == 0 or (C == 0 and wide == "sort"):
+        out = (torch.zeros((M, C), dtype=torch.int64), [0] * C)
+        return out + ([torch.zeros(0, dtype=torch.int64) for _ in range(C)],) if return_uniques else out
+    if wide != "sort":
+        mn, mx = column_range(v)
+        mn_h, mx_h = mn.cpu().numpy(), mx.cpu().numpy()          # one host read: sizes the presence tables
+        # (object arithmetic: max - min + 1 of a column that spans more than 2^63 does not fit int64)
+        sizes = [int(b) - int(a) + 1 for a, b in zip(mn_h.tolist(), mx_h.tolist())]
+        if sum(sizes) > MAX_TABLE_ELEMS:
+            if wide == "refuse":
+                raise NotImplementedError("value range too wide for table recoding (%d entries > %d)" % (sum(sizes), MAX_TABLE_ELEMS))
+            wide = "sort"
+    if wide == "sort":
+        codes, d, uniques = _unique_codes_sort(v)
+    else:
+        base = np.concatenate([[0], np.cumsum(np.asarray(sizes, dtype=np.int64))]).astype(np.int64)
+        base_d = torch.from_numpy(base).to(dev)
+        table = torch.empty(int(base[-1]), dtype=torch.int32, device=dev)
+        codes = torch.empty_like(v)
+        nd = torch.empty(C, dtype=torch.int64, device=dev)
+        with _abi.device_guard(dev):
+            rc = _abi.lib().gsn_column_ranks_hip(M, C, v.data_ptr(), mn.data_ptr(), base_d.data_ptr(), int(base[-1]),
+                                                 table.data_ptr(), codes.data_ptr(), nd.data_ptr(), _abi.current_stream())
+        _abi.check(rc, "gsn_column_ranks_hip")
+        d = [int(x) for x in nd.cpu().tolist()]
+        uniques = None
+        if return_uniques:
+            # values scattered to their codes: every writer of a slot writes the same value
+            uniques = [torch.empty(d[c], dtype=torch.int64, device=dev).index_put_((codes[:, c],), v[:, c]) for c in range(C)]
+    if return_uniques:
+        return codes.cpu(), d, [u.cpu() for u in uniques]
+    return codes.cpu(), d
+
+
+def lookup_tables(uniques, dev):
+    """Sorted distinct values per column (list of int64 tensors) -> (flat device tensor, col_ptr device tensor [C + 1])."""
+    lens = [int(u.numel()) for u in uniques]
+    flat = torch.cat([u.reshape(-1).to(torch.int64) for u in uniques]) if uniques else torch.zeros(0, dtype=torch.int64)
+    col_ptr = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64))
+    return flat.to(dev).contiguous(), col_ptr.to(dev)
+
+
+def _lookup(v, tables, clamp):
+    """gsn_lookup_codes_hip on an int64 [R, C] device tensor -> (codes, status int32 [1], first_unseen int64 [1]), all on the device and
+    not synchronised.  Nothing is launched for R == 0."""
+    R, C = v.shape
+    dev = v.device
+    flat, col_ptr = tables
     codes = torch.empty_like(v)
-    nd = torch.empty(C, dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    first = torch.full((1,), -1, dtype=torch.int64, device=dev)
+    if R == 0 or C == 0:
+        return codes, status, first
     with _abi.device_guard(dev):
-        rc = _abi.lib().gsn_column_ranks_hip(M, C, v.data_ptr(), mn.data_ptr(), base_d.data_ptr(), int(base[-1]),
-                                             table.data_ptr(), codes.data_ptr(), nd.data_ptr(), _abi.current_stream())
-    _abi.check(rc, "gsn_column_ranks_hip")
-    return codes.cpu(), [int(x) for x in nd.cpu().tolist()]
+        rc = _abi.lib().gsn_lookup_codes_hip(R, C, v.data_ptr(), flat.data_ptr() if flat.numel() else None, col_ptr.data_ptr(),
+                                             1 if clamp else 0, codes.data_ptr(), status.data_ptr(), first.data_ptr(),
+                                             _abi.current_stream())
+    _abi.check(rc, "gsn_lookup_codes_hip")
+    return codes, status, first
+
+
+def _unknown_flag(unknown):
+    if unknown not in ("raise", "clamp"):
+        raise ValueError("unknown must be 'raise' or 'clamp', not %r" % (unknown,))
+    return unknown == "clamp"
+
+
+def lookup_codes(values, uniques, unknown="raise", check=True):
+    """Codes of ``values`` (integer [R, C] tensor) under a fitted recoding, on the device (gsn_lookup_codes_hip): ``uniques`` is the list of
+    sorted distinct values per column (``one_hot_unique.uniques``), or the pair ``lookup_tables(uniques, device)`` made once by a caller
+    that looks up many batches.  Returns int64 device codes [R, C].
+
+    ``unknown="raise"``: a value that was not fitted gets -1 and raises ValueError; ``unknown="clamp"``: it gets the code of the nearest
+    fitted value not above it (0 below the smallest).  ``check=False`` does not synchronise: it returns ``(codes, status)`` with the int32
+    device status word (non-zero: some value was not fitted) for the caller to look at later."""
+    clamp = _unknown_flag(unknown)
+    dev = values.device if values.is_cuda else _device()
+    _abi.require_gpu()
+    v = _as_int_matrix(values).to(dev).contiguous()
+    tables = uniques if isinstance(uniques, tuple) else lookup_tables(list(uniques), dev)
+    if int(tables[1].numel()) != v.shape[1] + 1:
+        raise ValueError("lookup_codes: %d value columns, fitted values for %d" % (v.shape[1], int(tables[1].numel()) - 1))
+    codes, status, first = _lookup(v, tables, clamp)
+    if not check:
+        return codes, status
+    if not clamp and int(status.item()) != 0:
+        e = int(first.item())
+        r, c = divmod(e, v.shape[1])
+        raise ValueError("lookup_codes: value %d in row %d, column %d is not among the fitted values" % (int(v[r, c].item()), r, c))
+    return codes
+
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -91,11 +192,12 @@ def unique_codes(values):
 # ----------------------------------------------------------------------------------------------------------------------
 class one_hot_unique:
     """utils_encoding.py:37-59: ``d[c]`` = number of distinct values of column c over the whole dataset, ``fit`` hands every
-    graph its rows recoded to the ranks."""
+    graph its rows recoded to the ranks.  Any int64 range: columns too wide for the presence table are sorted.  ``uniques[c]`` holds the
+    sorted distinct values of column c, and :meth:`transform` gives rows that were not in the dataset the fitted codes."""
 
     def __init__(self, tensor_list, **kwargs):
         self._rows = [int(t.shape[0]) for t in tensor_list]
-        self.codes, self.d = unique_codes(torch.cat(list(tensor_list), 0))
+        self.codes, self.d, self.uniques = unique_codes(torch.cat(list(tensor_list), 0), wide="auto", return_uniques=True)
         self.corrs = {c: self.codes[:, c].numpy() for c in range(self.codes.shape[1])}
 
     def fit(self, tensor_list):
@@ -105,6 +207,31 @@ class one_hot_unique:
             out.append(self.codes[ptr:ptr + n].clone())
             ptr += n
         return out
+
+    def transform(self, tensor_list, unknown="raise"):
+        """One CPU int64 [n_g, C] tensor of fitted codes per input tensor; the rows need not have been in the dataset.
+        ``unknown="raise"``: ValueError naming the first value that was not fitted; ``unknown="clamp"``: the code of the nearest fitted
+        value not above it, 0 below the smallest."""
+        clamp = _unknown_flag(unknown)
+        C = len(self.d)
+        mats = [_as_int_matrix(t) for t in tensor_list]
+        for i, m in enumerate(mats):
+            if m.dim() != 2 or m.shape[1] != C:
+                raise ValueError("one_hot_unique.transform: tensor %d has shape %s, the fit has %d columns" % (i, tuple(m.shape), C))
+        if not mats:
+            return []
+        dev = _device()
+        cat = torch.cat([m.cpu() for m in mats], 0).contiguous()
+        codes, status, first = _lookup(cat.to(dev), lookup_tables(self.uniques, dev), clamp)
+        if not clamp and int(status.item()) != 0:                 # one host read; the rest only on the way to the error
+            r, c = divmod(int(first.item()), C)
+            i, r0 = 0, 0
+            while r >= r0 + int(mats[i].shape[0]):
+                r0 += int(mats[i].shape[0])
+                i += 1
+            raise ValueError("one_hot_unique.transform: value %d in column %d (tensor %d, row %d) was not seen by the fit"
+                             % (int(cat[r, c]), c, i, r - r0))
+        return list(torch.split(codes.cpu(), [int(m.shape[0]) for m in mats], 0))
 
 
 class one_hot_max:

@@ -48,8 +48,12 @@ enum {
     GSN_ST_TOO_LARGE = 2, /* graph exceeds max_nodes / max_edges given to the call */
     GSN_ST_BAD_INDEX = 3, /* a vertex id outside [0, num_nodes) */
     GSN_ST_ASYMMETRIC = 4,     /* gsn_laplacian_eig_hip: the graph's arc set is not symmetric (A != A^T) */
-    GSN_ST_NO_CONVERGENCE = 5  /* gsn_laplacian_eig_hip: not converged after max_sweeps sweeps (the rows hold the last iterate) */
+    GSN_ST_NO_CONVERGENCE = 5, /* gsn_laplacian_eig_hip: not converged after max_sweeps sweeps (the rows hold the last iterate) */
+    GSN_ST_UNSEEN = 6          /* gsn_lookup_codes_hip (strict): a value that is not among its column's fitted values */
 };
+
+/* gsn_lookup_codes_hip: what a value outside its column's fitted values becomes */
+enum { GSN_LOOKUP_STRICT = 0, GSN_LOOKUP_CLAMP = 1 };
 
 const char *gsn_last_error(void);
 /* what the last propagate / segment-sum / CSR entry point called on this thread launched: "kernel<template arguments> grid=G" per launch,
@@ -713,6 +717,49 @@ int gsn_column_range_hip(int64_t m_rows, int n_cols, const int64_t *values, int6
 int gsn_column_ranks_hip(int64_t m_rows, int n_cols, const int64_t *values, const int64_t *col_min,
                          const int64_t *col_base, int64_t table_elems, int32_t *table, int64_t *codes,
                          int64_t *n_distinct, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The same recoding over the FULL int64 range, by sorting (device): utils_encoding.one_hot_unique (utils_encoding.py:37-59) for
+ * columns whose ranges are too wide for the presence table above -- counts of cliques, paths and stars in graphs that are not
+ * molecules pass 2^28.  Order is signed int64 order (keys are compared as value ^ 2^63, never through value - min): a column may
+ * hold INT64_MIN and INT64_MAX.
+ *   values      int64 device [M][C]
+ *   uniques     int64 device [C][M]: the first n_distinct[c] entries of uniques + c*M are the distinct values of column c in
+ *               increasing order (np.unique(values[:, c])); the rest of the row is not written
+ *   n_distinct  int64 device [C]
+ *   codes       int64 device [M][C]: codes[r][c] = index of values[r][c] in that column's distinct values (return_inverse)
+ *   scratch     device, 8-byte aligned, scratch_bytes >= gsn_unique_sort_scratch_bytes(M, C) (GSN_E_NOSPACE below): the sorted
+ *               keys and one counter per 1024 keys -- 8 C (1 + 1/1024) bytes per row, rounded up to 256 bytes twice.
+ *               gsn_unique_sort_scratch_bytes takes host arguments only, makes no GPU call and is 0 for an empty shape.
+ * A keys-only bitonic sort (tiles of 4096 keys in 32 KiB of LDS, wave64, 256 threads), a compaction of the run starts and one
+ * binary search per element: no payload, no order-dependent scatter -- two runs give the same bytes in all three outputs.  M == 0
+ * or C == 0: nothing is launched, GSN_OK.  Null pointers with a non-empty shape: GSN_E_INVALID.  More than 65535 columns or 2^40
+ * elements: GSN_E_UNSUPPORTED.  Asynchronous on `stream`.
+ * ---------------------------------------------------------------------------------------------------------------- */
+int64_t gsn_unique_sort_scratch_bytes(int64_t m_rows, int64_t n_cols);
+int gsn_unique_sort_hip(int64_t m_rows, int64_t n_cols, const int64_t *values, int64_t *uniques, int64_t *n_distinct,
+                        int64_t *codes, void *scratch, int64_t scratch_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Codes of further rows under a FITTED recoding (device): what utils_encoding.one_hot_unique (utils_encoding.py:37-59) cannot
+ * do in the reference, which encodes train and test together -- rows that were not in the dataset get the codes the model was
+ * trained with.
+ *   values        int64 device [R][C]
+ *   uniques       int64 device, flat: column c's sorted distinct values are uniques[col_ptr[c] .. col_ptr[c+1])
+ *   col_ptr       int64 device [C+1]
+ *   mode          GSN_LOOKUP_STRICT: codes[r][c] = index of values[r][c] among column c's values; a value that is not among
+ *                 them (every value of a column with none) gets -1, raises *status to GSN_ST_UNSEEN and lowers *first_unseen
+ *                 to r*C + c.  status: int32 device [1], zeroed by the caller; first_unseen: int64 device [1], set to -1 by the
+ *                 caller (compared as unsigned), so it ends as the smallest r*C + c of an unseen value -- row first_unseen / C.
+ *                 GSN_LOOKUP_CLAMP: codes[r][c] = max(0, (number of column c's values <= values[r][c]) - 1): the nearest
+ *                 fitted value not above, 0 below the smallest and for a column with no values (the analogue of the step's
+ *                 `clamp`); status and first_unseen are not touched and may be NULL.
+ *   codes         int64 device [R][C]
+ * R == 0 or C == 0: nothing is launched, GSN_OK.  Null pointers with a non-empty shape: GSN_E_INVALID (uniques may be NULL when
+ * every column is empty).  Asynchronous on `stream`.
+ * ---------------------------------------------------------------------------------------------------------------- */
+int gsn_lookup_codes_hip(int64_t n_rows, int64_t n_cols, const int64_t *values, const int64_t *uniques, const int64_t *col_ptr,
+                         int mode, int64_t *codes, int32_t *status, int64_t *first_unseen, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Embedding of categorical columns (device): utils_graph_learning.multi_embedding.forward (:151-163), the
