@@ -193,6 +193,7 @@ SIGNATURES = {
     "gsn_laplacian_eig_hip": (c_int, [c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                                       c_i64, c_vp]),
     "gsn_laplacian_eig_scratch_floats": (c_i64, [c_int, c_i64]),
+    "gsn_adam_step_hip": (c_int, [c_int, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
 }
 
 

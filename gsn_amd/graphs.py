@@ -66,7 +66,8 @@ class GraphedTrainStep:
       * the parameters are updated in place by the captured optimizer kernels, which PyTorch's version counters do not see: the
         derived-weight caches of gsn_amd.layers are keyed on those counters, so every replay bumps them -- parameters and the BatchNorm
         buffers the captured kernels write (torch.autograd.graph.increment_version -- no launch) -- and an eager forward after a replay
-        prepares its weights and eval-mode BatchNorm vectors afresh.
+        prepares its weights and eval-mode BatchNorm vectors afresh;
+      * the learning rate, with gsn_amd.optim.Adam: its kernel reads it from device memory, uploaded here when a scheduler changed it.
     The warm-up steps are REAL steps (they update the parameters); shapes are frozen: capture one object per batch shape.
     Optimizers with a host-side step counter (Adam, AdamW ...) must be built with ``capturable=True``."""
 
@@ -123,6 +124,9 @@ class GraphedTrainStep:
         self.steps_taken = max(1, warmup)              # (a capture records, it does not execute)
 
     def __call__(self):
+        sync = getattr(self.optimizer, "sync_hyperparameters", None)      # (gsn_amd.optim.Adam: the rate a scheduler wrote since)
+        if sync is not None:
+            sync()
         self.graph.replay()
         torch.autograd.graph.increment_version(self._bump)
         self.replays += 1

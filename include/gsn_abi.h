@@ -975,6 +975,33 @@ int gsn_laplacian_eig_hip(int64_t n_graphs_total, const int64_t *node_ptr, const
                           void *stream);
 int64_t gsn_laplacian_eig_scratch_floats(int n_class, int64_t n_ids);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Adam update of every parameter of every parameter group in ONE launch (train_test_funcs.py:22: torch.optim.Adam(model.parameters(),
+ * lr, weight_decay); :106: optimizer.step()).  torch.optim.Adam with amsgrad = False, maximize = False; per element, in fp32:
+ *   g' = g + wd p            (decoupled: p <- p (1 - lr wd), g' = g)
+ *   m <- b1 m + (1 - b1) g'        v <- b2 v + (1 - b2) g'^2        p <- p - (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
+ * with bcK = 1 - bK^t, t = the tensor's step counter + 1; bc1, bc2 and lr / bc1 are taken in float64 once per chunk.
+ *   tensors   int64 device [n_tensors][GSN_ADAM_TENSOR_WORDS]: parameter pointer (fp32), gradient pointer (fp32; 0: no gradient in this
+ *             step -- parameter, moments and counter of the tensor stay as they are), offset of its exp_avg in `exp_avg` and of its
+ *             exp_avg_sq in `exp_avg_sq` (in elements), element count, group index.  Pointers need 4-byte alignment only.
+ *   chunks    int32 device [n_chunks][2]: (tensor, first element) of workgroup i, which updates elements [first, first +
+ *             GSN_ADAM_CHUNK_ELEMS) of that tensor, clipped to its size.  Every element of every tensor lies in exactly one chunk.
+ *   groups    float64 device [n_groups][GSN_ADAM_GROUP_DOUBLES]: lr, beta1, beta2, eps, weight_decay, decoupled (0 / 1), 0, 0.  Read by
+ *             the kernel at every launch: a replayed HIP graph follows what the host writes here between replays.
+ *   steps     fp32 device [n_tensors]: the step counters (fp32 as torch.optim.Adam keeps them).  The workgroup that finishes last adds 1
+ *             to the counter of every tensor that had a gradient -- no second launch, no host-side counter.
+ *   done      uint32 device, zero before the first call; the launch leaves it zero.  One optimizer = one word; calls that share it must
+ *             be ordered (one stream, or one graph).
+ *   max_elems the largest element count in `tensors` (the tables are device memory: the host cannot read them); more than 2^31 - 1 is
+ *             GSN_E_UNSUPPORTED.
+ * n_chunks == 0 launches nothing and returns GSN_OK.  Asynchronous on `stream`; two runs on the same inputs give the same bits.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define GSN_ADAM_CHUNK_ELEMS 8192
+#define GSN_ADAM_TENSOR_WORDS 6
+#define GSN_ADAM_GROUP_DOUBLES 8
+int gsn_adam_step_hip(int n_tensors, const int64_t *tensors, int64_t n_chunks, const int32_t *chunks, int n_groups, const double *groups,
+                      float *exp_avg, float *exp_avg_sq, float *steps, unsigned *done, int64_t max_elems, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

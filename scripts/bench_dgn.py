@@ -77,7 +77,7 @@ def emit(**kw):
     print(json.dumps(kw), flush=True)
 
 
-def bench(G, window, only_step):
+def bench(G, window, only_step, optimizer="adam"):
     b, ef_np, codes_np = batch(G)
     g = dgn.DGNGraph.from_batch(b, edge_field=ef_np)
     N, E, d, A = b.num_nodes, b.num_edges, 70, 5
@@ -128,7 +128,12 @@ def bench(G, window, only_step):
                           in_feat_dropout=0.0, dropout=0.3, graph_norm=False, batch_norm=True, aggregators=AGGS, scalers="identity",
                           towers=5, divide_input_first=False, divide_input_last=True, edge_dim=0, pretrans_layers=1, posttrans_layers=1,
                           pos_enc_dim=0, avg_d={"log": 1.0}, device="cuda")).cuda().train()
-    opt = torch.optim.Adam(net.parameters(), lr=0.01, weight_decay=3e-6, capturable=True)
+    if optimizer == "adam_native":
+        from gsn_amd import optim
+        opt = optim.Adam(net.parameters(), lr=0.01, weight_decay=3e-6)
+    else:
+        opt = torch.optim.Adam(net.parameters(), lr=0.01, weight_decay=3e-6, capturable=True)
+    common = dict(common, optimizer=optimizer)
     codes = torch.from_numpy(codes_np).cuda()
     labels = torch.from_numpy((np.arange(G) % 2).astype(np.float32)).cuda()
 
@@ -151,10 +156,11 @@ def main():
     ap.add_argument("--graphs", default="128,4096")
     ap.add_argument("--window", type=float, default=1.0)
     ap.add_argument("--only-step", action="store_true")
+    ap.add_argument("--optimizer", default="adam", choices=["adam", "adam_native"], help="adam_native: gsn_amd.optim.Adam, one HIP launch per step")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_dgn.py measures on the GPU; there is no CPU fallback"
     for G in [int(x) for x in a.graphs.split(",")]:
-        bench(G, a.window, a.only_step)
+        bench(G, a.window, a.only_step, a.optimizer)
         layers.drop_input_caches()
 
 

@@ -55,7 +55,7 @@ def main():
     ap.add_argument("--layers", type=int, default=5)
     ap.add_argument("--d", type=int, default=300)
     ap.add_argument("--graph", action="store_true", help="replay the whole step as one HIP graph (gsn_amd.graphs.GraphedTrainStep)")
-    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adam"])
+    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adam", "adam_native"])
     args = ap.parse_args()
     rank, world, local = (int(os.environ.get(k, d)) for k, d in (("RANK", "0"), ("WORLD_SIZE", "1"), ("LOCAL_RANK", "0")))
     torch.cuda.set_device(local)
@@ -91,6 +91,9 @@ def build(args, dev, rank=0, dropout=0.5):
     n_params = sum(p.numel() for p in params)
     if getattr(args, "optimizer", "sgd") == "adam":
         opt = torch.optim.Adam(params, lr=1e-3, capturable=True)
+    elif getattr(args, "optimizer", "sgd") == "adam_native":
+        from gsn_amd import optim
+        opt = optim.Adam(params, lr=1e-3)          # one HIP launch per step; a replay follows the schedulers (gsn_amd/optim.py)
     else:
         opt = torch.optim.SGD(params, lr=1e-3)
     loss_fn = torch.nn.BCEWithLogitsLoss()

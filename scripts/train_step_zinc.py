@@ -52,6 +52,9 @@ def build(args, dev, rank=0):
     params = list(model.parameters())
     if getattr(args, "optimizer", "sgd") == "adam":
         opt = torch.optim.Adam(params, lr=1e-3, capturable=True)
+    elif getattr(args, "optimizer", "sgd") == "adam_native":
+        from gsn_amd import optim
+        opt = optim.Adam(params, lr=1e-3)          # one HIP launch per step; a replay follows the schedulers (gsn_amd/optim.py)
     else:
         opt = torch.optim.SGD(params, lr=1e-3)
     loss_fn = torch.nn.L1Loss()
@@ -102,7 +105,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--graph", action="store_true", help="replay the whole step as one HIP graph (gsn_amd.graphs.GraphedTrainStep)")
-    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adam"])
+    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adam", "adam_native"])
     args = ap.parse_args()
     rank, world, local = (int(os.environ.get(k, d)) for k, d in (("RANK", "0"), ("WORLD_SIZE", "1"), ("LOCAL_RANK", "0")))
     torch.cuda.set_device(local)
