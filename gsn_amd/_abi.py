@@ -194,6 +194,13 @@ SIGNATURES = {
                                       c_i64, c_vp]),
     "gsn_laplacian_eig_scratch_floats": (c_i64, [c_int, c_i64]),
     "gsn_adam_step_hip": (c_int, [c_int, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "gsn_masked_loss_scratch_bytes": (c_i64, [c_int, c_i64, c_i64]),
+    "gsn_masked_loss_fwd_hip": (c_int, [c_int, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "gsn_masked_loss_bwd_hip": (c_int, [c_int, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "gsn_eval_accumulate_scratch_bytes": (c_i64, [c_int, c_i64, c_i64]),
+    "gsn_eval_accumulate_hip": (c_int, [c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "gsn_rank_metrics_scratch_bytes": (c_i64, [c_i64, c_i64]),
+    "gsn_rank_metrics_hip": (c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
 }
 
 

@@ -2,7 +2,7 @@
 // np.unique(values[:, c], return_inverse=True) by a keys-only sort, and the lookup of further rows in the sorted distinct values a fit left
 // behind.  The presence-table kernels of encode.hip index a table by value - min and stop at 2^28 entries; nothing here depends on the range.
 //
-//   gsn_unique_sort_hip:   keys = values ^ 2^63 per column            (tile kernel: loads, and sorts every tile of US_TILE keys in LDS)
+//   gsn_unique_sort_hip:   keys = values ^ 2^63 per column            (tile kernel of unique_sort_kernels.h: loads, sorts every tile in LDS)
 //                          bitonic merge stages in one direction      (unique_sort_core.h: global steps at distance >= US_TILE, the rest in LDS)
 //                          run starts -> counts per chunk -> scan -> compaction into `uniques`, n_distinct
 //                          codes[r][c] = position of values[r][c] in uniques[c]   (one binary search per element)
@@ -16,70 +16,15 @@
 
 #include "gsn_internal.h"
 #include "unique_sort_core.h"
+#include "unique_sort_kernels.h"
 
 namespace gsn {
 
-constexpr int64_t US_MAX_GRID_X = 1 << 20;
-
-__device__ __forceinline__ void us_cmpswap_lds(uint64_t *s, int lo, int hi) {
-    const uint64_t a = s[lo], b = s[hi];
-    if (a > b) { s[lo] = b; s[hi] = a; }
-}
-
-// FIRST: keys from `values`, stages 1 .. US_LOG_TILE (a full sort of the tile).  Otherwise: the steps US_LOG_TILE-1 .. 0 of a later stage.
-// Positions >= m hold the largest key in LDS: they never move (every pair leaves its smaller key low) and are not written back.
-template <bool FIRST>
-__global__ __launch_bounds__(256) void us_tile_kernel(int64_t m, int64_t n_cols, const int64_t *values, uint64_t *keys, int64_t n_tiles) {
-    __shared__ uint64_t s[US_TILE];
-    const int64_t c = blockIdx.y;
-    uint64_t *kc = keys + c * m;
-    const int tid = threadIdx.x;
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int64_t base = tile * US_TILE;
-        for (int i = tid; i < US_TILE; i += 256) {
-            const int64_t g = base + i;
-            s[i] = g < m ? (FIRST ? us_key(values[g * n_cols + c]) : kc[g]) : ~0ull;
-        }
-        __syncthreads();
-        const int k_first = FIRST ? 1 : US_LOG_TILE + 1, k_last = FIRST ? US_LOG_TILE : US_LOG_TILE + 1;
-        for (int k = k_first; k <= k_last; ++k) {
-            if (FIRST) {
-                for (int t = tid; t < US_TILE / 2; t += 256) {
-                    int64_t lo, hi;
-                    us_pair_flip(t, k, lo, hi);
-                    us_cmpswap_lds(s, (int)lo, (int)hi);
-                }
-                __syncthreads();
-            }
-            for (int j = FIRST ? k - 2 : US_LOG_TILE - 1; j >= 0; --j) {
-                for (int t = tid; t < US_TILE / 2; t += 256) {
-                    int64_t lo, hi;
-                    us_pair_step(t, j, lo, hi);
-                    us_cmpswap_lds(s, (int)lo, (int)hi);
-                }
-                __syncthreads();
-            }
-        }
-        for (int i = tid; i < US_TILE; i += 256) {
-            const int64_t g = base + i;
-            if (g < m) kc[g] = s[i];
-        }
-        __syncthreads();
-    }
-}
-
-// one step over whole columns: flip of stage kj, or step kj
-__global__ __launch_bounds__(256) void us_global_kernel(int64_t m, uint64_t *keys, int kj, int flip, int64_t n_pairs) {
-    uint64_t *kc = keys + (int64_t)blockIdx.y * m;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n_pairs; t += (int64_t)gridDim.x * 256) {
-        int64_t lo, hi;
-        if (flip) us_pair_flip(t, kj, lo, hi); else us_pair_step(t, kj, lo, hi);
-        if (hi < m) {
-            const uint64_t a = kc[lo], b = kc[hi];
-            if (a > b) { kc[lo] = b; kc[hi] = a; }
-        }
-    }
-}
+// the key load of the first tile pass (unique_sort_kernels.h): signed int64 order as unsigned words
+struct UsValueLoad {
+    const int64_t *values;
+    __device__ __forceinline__ uint64_t operator()(int64_t row, int64_t n_cols, int64_t col) const { return us_key(values[row * n_cols + col]); }
+};
 
 // exclusive prefix of v over the 256 threads of a workgroup, *total = the sum (all threads call; ends with a barrier)
 __device__ __forceinline__ int64_t us_block_scan(int64_t v, int64_t *total) {
@@ -170,23 +115,6 @@ __global__ __launch_bounds__(256) void us_lookup_kernel(int64_t n_rows, int64_t 
     }
 }
 
-static unsigned us_grid(int64_t blocks) { return (unsigned)(blocks < 1 ? 1 : (blocks > US_MAX_GRID_X ? US_MAX_GRID_X : blocks)); }
-
-struct UsLaunches {
-    int64_t m, n_cols;
-    const int64_t *values;
-    uint64_t *keys;
-    hipStream_t s;
-    int64_t n_tiles() const { return (m + US_TILE - 1) / US_TILE; }
-    void tile_sort() { hipLaunchKernelGGL(us_tile_kernel<true>, dim3(us_grid(n_tiles()), (unsigned)n_cols), dim3(256), 0, s, m, n_cols, values, keys, n_tiles()); }
-    void tile_merge() { hipLaunchKernelGGL(us_tile_kernel<false>, dim3(us_grid(n_tiles()), (unsigned)n_cols), dim3(256), 0, s, m, n_cols, values, keys, n_tiles()); }
-    void global(int kj, int flip, int64_t n_pairs) {
-        hipLaunchKernelGGL(us_global_kernel, dim3(us_grid((n_pairs + 255) / 256), (unsigned)n_cols), dim3(256), 0, s, m, keys, kj, flip, n_pairs);
-    }
-    void global_flip(int k) { global(k, 1, us_pair_count(m, k - 1)); }
-    void global_step(int j) { global(j, 0, us_pair_count(m, j)); }
-};
-
 static int64_t us_chunks(int64_t m) { return (m + US_CHUNK - 1) / US_CHUNK; }
 static int64_t us_keys_bytes(int64_t m, int64_t c) { return (8 * m * c + 255) / 256 * 256; }
 
@@ -214,7 +142,7 @@ extern "C" int gsn_unique_sort_hip(int64_t m_rows, int64_t n_cols, const int64_t
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     uint64_t *keys = reinterpret_cast<uint64_t *>(scratch);
     int64_t *chunk_count = reinterpret_cast<int64_t *>(reinterpret_cast<char *>(scratch) + us_keys_bytes(m_rows, n_cols));
-    UsLaunches ops{m_rows, n_cols, values, keys, s};
+    UsLaunches<UsValueLoad> ops{m_rows, n_cols, UsValueLoad{values}, keys, s};
     us_schedule(m_rows, ops);
     const int64_t n_chunks = us_chunks(m_rows);
     const dim3 cgrid(us_grid(n_chunks), (unsigned)n_cols);

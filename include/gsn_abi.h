@@ -1002,6 +1002,67 @@ int64_t gsn_laplacian_eig_scratch_floats(int n_class, int64_t n_ids);
 int gsn_adam_step_hip(int n_tensors, const int64_t *tensors, int64_t n_chunks, const int32_t *chunks, int n_groups, const double *groups,
                       float *exp_avg, float *exp_avg_sq, float *steps, unsigned *done, int64_t max_elems, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Evaluation on the device (train_test_funcs.py:94-103, :177-259; utils.py:164-187; utils_graph_learning.py:11-21).  Common to the
+ * entries below: no float atomics, every reduction in a fixed order (two runs give the same bytes), workspaces from the caller, nothing
+ * allocates, copies synchronously or synchronises -- every entry can be captured into a HIP graph.
+ *
+ * Masked mean loss -- train_test_funcs.py:98-101: is_labeled = (y == y); loss_fn(y_hat[is_labeled], y[is_labeled]) -- without the
+ * boolean index.  Kinds after utils.py:164-175.  Element-wise kinds (BCE, L1, MSE): y_hat fp32 [rows, cols], y fp32 with the same element
+ * count, a NaN target = unlabelled.  GSN_LOSS_CE: y_hat fp32 [rows, cols = classes], y int64 [rows]; a target outside [0, cols) makes the
+ * loss NaN and that row's gradient zero.  Per-element values are fp32; they are summed in float64 over chunks of 1 024 consecutive elements
+ * (rows for CE), the partials in chunk order, and the mean is rounded once: loss fp32 [1], count int64 [1] = the labelled elements (rows
+ * for CE), both device memory.  No labelled element (an empty shape included): NaN loss, zero gradient (as torch); GSN_LOSS_CE with
+ * rows > 0 and cols == 0 is GSN_E_INVALID.  rows * cols <= 65 536: ONE launch of one
+ * workgroup, no scratch; beyond, a partial and a combine launch and gsn_masked_loss_scratch_bytes(kind, rows, cols) bytes of scratch.
+ * Backward (one launch): grad_y_hat [rows, cols] = grad_loss[0] * d loss / d y_hat, recomputed from y_hat and y, with grad_loss (fp32)
+ * and count (as the forward left it) READ FROM DEVICE MEMORY; zeros at unlabelled positions.
+ * ---------------------------------------------------------------------------------------------------------------- */
+enum { GSN_LOSS_BCE = 0, GSN_LOSS_L1 = 1, GSN_LOSS_MSE = 2, GSN_LOSS_CE = 3 };
+int64_t gsn_masked_loss_scratch_bytes(int kind, int64_t rows, int64_t cols);
+int gsn_masked_loss_fwd_hip(int kind, int64_t rows, int64_t cols, const float *y_hat, const void *y, float *loss, int64_t *count,
+                            void *scratch, int64_t scratch_bytes, void *stream);
+int gsn_masked_loss_bwd_hip(int kind, int64_t rows, int64_t cols, const float *y_hat, const void *y, const float *grad_loss,
+                            const int64_t *count, float *grad_y_hat, void *stream);
+
+/* One batch of an evaluation epoch (train_test_funcs.py:193-202 and :234-251 per batch, without their .item() / .cpu()), in the launches
+ * of the masked loss: the batch loss through the same device functions and partition (the same bits), then
+ *   acc_f64[GSN_EVAL_WEIGHTED_LOSS] += (double)loss * num_graphs      acc_f64[GSN_EVAL_BATCH_LOSS] += (double)loss
+ *   acc_f64[GSN_EVAL_METRIC]        += the fp32 reduction='sum' of L1Loss / MSELoss over every element (GSN_METRIC_L1 / _MSE; utils.py:177-183)
+ *   acc_i64[GSN_EVAL_CORRECT]       += rows whose arg-max (first index of the row maximum) equals the target (GSN_METRIC_ACCURACY; CE only)
+ *   acc_i64[GSN_EVAL_BATCHES]       += 1
+ * and the batch's rows appended to pred_buf fp32 [capacity, cols] and true_buf [capacity, y_cols] (fp32, or int64 for GSN_LOSS_CE where
+ * y_cols = 1) at row acc_i64[GSN_EVAL_CURSOR], which the call advances by `rows`: the cursor lives on the device, so a replayed capture
+ * appends.  A batch that would pass `capacity` changes nothing but acc_i64[GSN_EVAL_STATUS] |= GSN_EVAL_OVERFLOW.  acc_f64 / acc_i64 have
+ * GSN_EVAL_ACC_WORDS entries each, zeroed by the caller to start an epoch.  loss_out (fp32 [1], device) may be NULL.  Either buffer may be
+ * NULL: nothing is appended to it.  Scratch as gsn_masked_loss_fwd_hip: gsn_eval_accumulate_scratch_bytes.
+ * ---------------------------------------------------------------------------------------------------------------- */
+enum { GSN_METRIC_NONE = 0, GSN_METRIC_L1 = 1, GSN_METRIC_MSE = 2, GSN_METRIC_ACCURACY = 3 };
+enum { GSN_EVAL_WEIGHTED_LOSS = 0, GSN_EVAL_BATCH_LOSS = 1, GSN_EVAL_METRIC = 2 };                          /* acc_f64 */
+enum { GSN_EVAL_CURSOR = 0, GSN_EVAL_BATCHES = 1, GSN_EVAL_CORRECT = 2, GSN_EVAL_STATUS = 3 };              /* acc_i64 */
+#define GSN_EVAL_ACC_WORDS 4
+#define GSN_EVAL_OVERFLOW 1
+int64_t gsn_eval_accumulate_scratch_bytes(int kind, int64_t rows, int64_t cols);
+int gsn_eval_accumulate_hip(int kind, int metric, int64_t rows, int64_t cols, int64_t y_cols, const float *y_hat, const void *y,
+                            int64_t num_graphs, double *acc_f64, int64_t *acc_i64, float *pred_buf, void *true_buf, int64_t capacity,
+                            float *loss_out, void *scratch, int64_t scratch_bytes, void *stream);
+
+/* ROC-AUC and average precision per column of y_pred fp32 [m_rows, n_cols] against y_true fp32 [m_rows, n_cols] (labels 0, 1, NaN =
+ * unlabelled) -- what ogb's Evaluator computes through sklearn.metrics.roc_auc_score / average_precision_score (train_test_funcs.py:257-259)
+ * -- from exact integer rank statistics.  Key of an element: (monotone uint32 image of the score, -0.0 as +0.0) << 1 | label; columns are
+ * sorted by the network of gsn_unique_sort_hip; equal-score runs give, per column c,
+ *   out_i64[c][0 .. 3) = { n_labelled, n_pos, U2 = sum over runs of pos * (2 * negatives below + negatives in the run) }
+ *   out_f64[c][0 .. 2) = { auc = U2 / (2 n_pos n_neg),  ap = sum over runs, highest score first, of (pos / n_pos) * tp / (tp + fp) }
+ *   status[c] (int32): GSN_RANK_ONE_CLASS (auc undefined: NaN), GSN_RANK_NO_POSITIVE (ap undefined: NaN), GSN_RANK_NONFINITE (a NaN or
+ *   infinite prediction in a labelled row), GSN_RANK_BAD_LABEL (a label other than 0, 1, NaN); with either of the last two the numbers of
+ *   the column are those of its remaining rows and the caller raises.
+ * m_rows < 2^31, n_cols <= 65 535 (GSN_E_UNSUPPORTED beyond).  scratch: gsn_rank_metrics_scratch_bytes(m_rows, n_cols), 8-byte aligned.
+ * ---------------------------------------------------------------------------------------------------------------- */
+enum { GSN_RANK_ONE_CLASS = 1, GSN_RANK_NO_POSITIVE = 2, GSN_RANK_NONFINITE = 4, GSN_RANK_BAD_LABEL = 8 };
+int64_t gsn_rank_metrics_scratch_bytes(int64_t m_rows, int64_t n_cols);
+int gsn_rank_metrics_hip(int64_t m_rows, int64_t n_cols, const float *y_pred, const float *y_true, int64_t *out_i64, double *out_f64,
+                         int32_t *status, void *scratch, int64_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,10 @@ def main():
     ap.add_argument("--d", type=int, default=300)
     ap.add_argument("--graph", action="store_true", help="replay the whole step as one HIP graph (gsn_amd.graphs.GraphedTrainStep)")
     ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adam", "adam_native"])
+    ap.add_argument("--loss", default="bce", choices=["bce", "masked", "masked_reference"],
+                    help="masked: gsn_amd.evaluation.MaskedLoss over labels of which --nan-share are NaN (one capturable node); "
+                         "masked_reference: the reference's loss_fn(y_hat[is_labeled], y[is_labeled]) on the same labels (eager only)")
+    ap.add_argument("--nan-share", type=float, default=0.2)
     args = ap.parse_args()
     rank, world, local = (int(os.environ.get(k, d)) for k, d in (("RANK", "0"), ("WORLD_SIZE", "1"), ("LOCAL_RANK", "0")))
     torch.cuda.set_device(local)
@@ -97,7 +101,24 @@ def build(args, dev, rank=0, dropout=0.5):
     else:
         opt = torch.optim.SGD(params, lr=1e-3)
     loss_fn = torch.nn.BCEWithLogitsLoss()
-    return model, data, params, opt, (lambda: loss_fn(model(data), data.y)), N, E
+    loss_kind = getattr(args, "loss", "bce")
+    if loss_kind == "bce":
+        return model, data, params, opt, (lambda: loss_fn(model(data), data.y)), N, E
+    # unlabelled entries as the multi-task OGB sets have them (train_test_funcs.py:98-101)
+    g = torch.Generator().manual_seed(7 + rank)
+    data.y[(torch.rand(data.y.shape, generator=g) < getattr(args, "nan_share", 0.2)).to(dev)] = float("nan")
+    if loss_kind == "masked":
+        from gsn_amd.evaluation import MaskedLoss
+        masked = MaskedLoss("BCEWithLogitsLoss")
+        return model, data, params, opt, (lambda: masked(model(data), data.y)), N, E
+    if getattr(args, "graph", False):
+        raise SystemExit("--loss masked_reference cannot be captured: its boolean index reads the device (use --loss masked)")
+
+    def reference_loss():
+        y_hat, y = model(data).view(-1, 1), data.y.view(-1, 1)
+        is_labeled = (y == y)
+        return loss_fn(y_hat[is_labeled], y[is_labeled])
+    return model, data, params, opt, reference_loss, N, E
 
 
 def run(args, dev, dist=None, rank=0, world=1):
@@ -140,6 +161,7 @@ def run(args, dev, dist=None, rank=0, world=1):
             "ms_per_step": round(dt / args.steps * 1e3, 3), "parameters": n_params,
             "grad_bucket_MB": round(n_params * 4 / 1e6, 2), "loss": float(loss.item()),
             "launch": "hip_graph" if getattr(args, "graph", False) else "eager", "optimizer": getattr(args, "optimizer", "sgd"),
+            "loss_fn": getattr(args, "loss", "bce"),
             "note": "forward and backward on HIP kernels (native adjoints of every stage, DESIGN.md 4); SGD update and glue in PyTorch"}
 
 
