@@ -60,6 +60,7 @@ struct CountArgs {
     int ids_are_global;
     const int32_t *graph_ids;  // or null
     int n_cap, e_cap;          // LDS capacities (rows of A, columns)
+    int last_cap;              // entries of last[] (edge mode): the slots of the CSR rank a workgroup may address, >= e_cap
     int n_decl, e_decl;        // the caller's max_nodes / max_edges: a single graph beyond them is reported (GSN_ST_TOO_LARGE)
     int stack_skip;            // frames of the candidate stack that are never addressed (the smallest n_fixed of the plans)
     int pair;                  // 1: a workgroup takes the graphs 2 i, 2 i + 1 -- as ONE graph, their disjoint union, when that fits n_cap / e_cap
@@ -132,12 +133,26 @@ __device__ __forceinline__ int side_byte(const unsigned w0, const unsigned w1, c
 // utils_graph_learning.py:170-187), the edge codes' columns of the edge pack.  Loads and stores are kept apart because gfx9 counts them in one
 // counter: a load issued behind a store waits for the store's acknowledgement too.  Statuses stay with the counting workgroups (they test every
 // column's endpoints against their graph); a code outside its classes ORs 1 into *code_status.
-template <int T>
+// FL: the launch-uniform flags as a type (CycAny / CycKeys, in front of count_body).  With CycKeys the side outputs are the headline step's
+// and nothing else: CSR with sorted targets and sources, ONE node code column as key bytes, ONE edge code column in the key words, global
+// vertex ids, no row pack -- the arms of every other form are not compiled in (launch<>() sends every other launch to CycAny).
+struct CycAny { static constexpr bool KEYS = false; };
+struct CycKeys { static constexpr bool KEYS = true; };
+template <int T, class FL = CycAny>
 __device__ __forceinline__ void side_block(const CountArgs &a, unsigned char *smem, const int g_lo, const int g_hi) {
     typedef unsigned u4v __attribute__((ext_vector_type(4)));
+    constexpr bool KEYS = FL::KEYS;
     const side_ptr_t sd = side_late();
     const int tid = threadIdx.x;
-    const bool do_csr = (a.side_mask & 1) != 0, do_np = (a.side_mask & 2) != 0, do_ec = (a.side_mask & 4) != 0;
+    const bool do_csr = KEYS || (a.side_mask & 1) != 0, do_np = KEYS || (a.side_mask & 2) != 0, do_ec = KEYS || (a.side_mask & 4) != 0;
+    const bool ids_global = KEYS || a.ids_are_global != 0;
+    // the code status is this launch's.  The first side workgroup clears it -- an atomic, so that the clear and the ORs below meet
+    // at the same place whichever XCD issues them -- as its first memory operation.  ASSUMPTION, by timing and not by a dependency: no other
+    // workgroup ORs before that clear lands.  An OR comes behind the workgroup's pointer reads and the loads of its codes (part (C): also
+    // behind three barriers and the sort; the plain loops of a graph that does not fit LDS: behind the code load alone), and workgroups are
+    // handed out in grid order, round-robin over the XCDs, and the first side workgroup is the fifth of the grid.  The
+    // alternative that needs no assumption, a memset on the stream in front of the launch, is one more node in the captured step.
+    if (g_lo == 0 && tid == 0 && sd->code_status) atomicExch(sd->code_status, 0);
     const int64_t *trow = sd->csr_row ? a.dst : a.src, *orow = sd->csr_row ? a.src : a.dst;
     auto need = [&](int64_t n, int64_t E) { return (n + 1) * 8 + n * 4 + E * 7 + 16; };
     if (do_csr) {
@@ -151,7 +166,7 @@ __device__ __forceinline__ void side_block(const CountArgs &a, unsigned char *sm
         int g2 = g + 1;
         int64_t n64 = a.node_ptr[g2] - n0, E64 = a.edge_ptr[g2] - e0;
         const bool fits = n64 >= 0 && E64 >= 0 && n64 < 65535 && E64 < 65535 && need(n64, E64) <= a.lds_bytes;
-        if (fits && a.ids_are_global)
+        if (fits && ids_global)
             while (g2 < g_hi) {                          // (graph-local ids: one graph per chunk -- the offset of a column depends on its graph)
                 const int64_t n2 = a.node_ptr[g2 + 1] - n0, E2 = a.edge_ptr[g2 + 1] - e0;
                 if (n2 < n64 || E2 < E64 || n2 >= 65535 || E2 >= 65535 || need(n2, E2) > a.lds_bytes) break;
@@ -252,7 +267,7 @@ __device__ __forceinline__ void side_block(const CountArgs &a, unsigned char *sm
         for (int v = tid; v <= n; v += T) cstart[v] = 0;
         __syncthreads();
         // ---- (A) loads: four per lane in flight --------------------------------------------------------------------------
-        const int64_t off = a.ids_are_global ? n0 : 0;   // (graph-local ids: the chunk is one graph)
+        const int64_t off = ids_global ? n0 : 0;         // (graph-local ids: the chunk is one graph)
         bool bad_code = false;
         if (do_csr)
             for (int c0 = 0; c0 < E; c0 += 4 * T) {
@@ -263,8 +278,8 @@ __device__ __forceinline__ void side_block(const CountArgs &a, unsigned char *sm
                 for (int j = 0; j < 4; ++j) {
                     const int c = c0 + j * T + tid;
                     if (c < E) {
-                        const int64_t t = tq[j] - off, o = oq[j] - off;
-                        const int tl = (t >= 0 && t < n) ? (int)t : 0, ol = (o >= 0 && o < n) ? (int)o : 0;     // (a column that leaves its graph: the counting workgroup reports it)
+                        uint32_t td, od;                 // (a column that leaves its graph: the counting workgroup reports it)
+                        const int tl = endpoint_local(tq[j], off, (uint32_t)n, td) ? (int)td : 0, ol = endpoint_local(oq[j], off, (uint32_t)n, od) ? (int)od : 0;
                         tloc[c] = (uint16_t)tl; oloc[c] = (uint16_t)ol;
                         atomicAdd(&cstart[tl], 1);
                     }
@@ -272,8 +287,8 @@ __device__ __forceinline__ void side_block(const CountArgs &a, unsigned char *sm
             }
         if (do_np) {
             const unsigned w0 = sd->ncode_ptr_w[0], w1 = sd->ncode_ptr_w[1];
-            const int nc = sd->ncode_cols;
-            const bool as_key = sd->nkey != nullptr;
+            const int nc = KEYS ? 1 : sd->ncode_cols;
+            const bool as_key = KEYS || sd->nkey != nullptr;
             for (int v0 = 0; v0 < n; v0 += 4 * T) {
                 if (nc == 1) {
                     int64_t xq[4];
@@ -308,7 +323,7 @@ __device__ __forceinline__ void side_block(const CountArgs &a, unsigned char *sm
         }
         if (do_ec) {
             const unsigned w0 = sd->ecode_ptr_w[0], w1 = sd->ecode_ptr_w[1];
-            const int nc = sd->ecode_cols, c00 = sd->ecode_col0;
+            const int nc = KEYS ? 1 : sd->ecode_cols, c00 = sd->ecode_col0;
             for (int r0 = 0; r0 < E; r0 += 4 * T) {
                 if (nc == 1) {
                     int64_t xq[4];
@@ -348,14 +363,24 @@ __device__ __forceinline__ void side_block(const CountArgs &a, unsigned char *sm
                     const int v = base + tid;
                     const int cnt = v <= n ? cstart[v] : 0;
                     int incl = cnt;
+                    if constexpr (KEYS && T == 64) {     // (one wave, every lane active: the six DPP adds of count_body's phase 2)
+                        incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xf, 0xf, false);      // row_shr:1
+                        incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xf, 0xf, false);      // row_shr:2
+                        incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xf, 0xf, false);      // row_shr:4
+                        incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xf, 0xf, false);      // row_shr:8
+                        incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xa, 0xf, false);      // row_bcast:15 into rows 1 and 3
+                        incl += __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xc, 0xf, false);      // row_bcast:31 into rows 2 and 3
+                    } else {
 #pragma unroll
                     for (int o = 1; o < 64; o <<= 1) {
                         const int t = __shfl_up(incl, o);
                         if (tid >= o) incl += t;
                     }
+                    }
                     const int ex = carry + incl - cnt;
                     if (v <= n) { cstart[v] = ex; ccur[v] = ex; }
-                    carry += __shfl(incl, 63);
+                    if constexpr (KEYS && T == 64) carry += __builtin_amdgcn_readlane(incl, 63);
+                    else carry += __shfl(incl, 63);
                 }
             }
             __syncthreads();
@@ -378,22 +403,23 @@ __device__ __forceinline__ void side_block(const CountArgs &a, unsigned char *sm
             for (int v = tid; v < n; v += T) sd->csr_seg[n0 + v] = (int32_t)(e0 + cstart[v]);
             for (int i = tid; i < E; i += T) {
                 const int le = pl[i];
+                const int tl = tloc[le], ol = oloc[le];  // (read once: the sorted endpoints and the key word share them)
                 sd->csr_perm[e0 + i] = (int32_t)(e0 + le);
-                if (sd->csr_tgt) sd->csr_tgt[e0 + i] = (int32_t)(n0 + tloc[le]);
-                if (sd->csr_oth) sd->csr_oth[e0 + i] = (int32_t)(n0 + oloc[le]);
-                if (sd->ekeys)
-                    sd->ekeys[e0 + i] = (do_np ? nmask[tloc[le]] | (nmask[oloc[le]] << 8) : 0u) | (do_ec ? (unsigned)ecls[le] << 16 : 0u);
+                if (KEYS || sd->csr_tgt) sd->csr_tgt[e0 + i] = (int32_t)(n0 + tl);
+                if (KEYS || sd->csr_oth) sd->csr_oth[e0 + i] = (int32_t)(n0 + ol);
+                if (KEYS || sd->ekeys)
+                    sd->ekeys[e0 + i] = (do_np ? nmask[tl] | (nmask[ol] << 8) : 0u) | (do_ec ? (unsigned)ecls[le] << 16 : 0u);
             }
         }
-        if (do_np && sd->nkey) for (int v = tid; v < n; v += T) sd->nkey[n0 + v] = (uint8_t)nmask[v];
-        if (do_np && sd->npack)
+        if (do_np && (KEYS || sd->nkey)) for (int v = tid; v < n; v += T) sd->nkey[n0 + v] = (uint8_t)nmask[v];
+        if (!KEYS && do_np && sd->npack)
             for (int i = tid; i < 4 * n; i += T) {
                 const int v = i >> 2, q = i & 3;
                 const unsigned hot = nmask[v] >> (8 * q);
                 auto word = [&](int kk) { return ((hot >> kk) & 1u ? 0x3c00u : 0u) | ((hot >> (kk + 1)) & 1u ? 0x3c000000u : 0u); };
                 *reinterpret_cast<u4v *>(sd->npack + (n0 + v) * 32 + 8 * q) = u4v{word(0), word(2), word(4), word(6)};
             }
-        if (do_ec && sd->epack) {
+        if (!KEYS && do_ec && sd->epack) {
             const int q0 = sd->ecode_col0 >> 2, nq = 4 - q0;      // the 4-column groups from ecode_col0 to the end of the row
             for (int i = tid; i < E * nq; i += T) {
                 const int r = nq == 1 ? i : i / nq;
@@ -435,9 +461,8 @@ __device__ unsigned long long *g_count_prof2;  // [12] wave-level sums over the 
 // FL (CYC only): the flags that are the same for every workgroup of a launch, as a type.  CycAny tests them where they are used (scalar
 // loads and branches in every workgroup); CycKeys is the headline step's combination (gsn_count_encode_keys_side_hip on staged rows),
 // selected by the launcher when all of it holds: int64 rows staged in LDS as 16-bit counts, class indices taken from those counts, the
-// identifier masks the only encoded form (no fp32 rows, no fp16 pack).  Same body, the other arms are not compiled in.
-struct CycAny { static constexpr bool KEYS = false; };
-struct CycKeys { static constexpr bool KEYS = true; };
+// identifier masks the only encoded form (no fp32 rows, no fp16 pack), global vertex ids, a grid with side workgroups, status words zeroed
+// by their own workgroups.  Same body, the other arms are not compiled in.  (The types stand in front of side_block, which takes them too.)
 template <int W, int T, bool DIR, bool TAIL, bool MOL, int CYC = 0, class FL = CycAny, class Args = CountArgs>
 __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, const int item, const int part, const int g, const int ng, const bool report) {
     constexpr bool KEYS = CYC > 0 && FL::KEYS;
@@ -627,27 +652,42 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
     // and this path reads that set only to start the 2-core, which lies inside the vertices with a neighbour whatever the largest id is.
     // Its endpoint loads: the graph's first column as a scalar base, the lane's column as a 32-bit byte offset.
     bool bad_lane = false;
+    if constexpr (CYC > 0) {
+        // CYC: an endpoint is tested against its graph's range by count_core.h's endpoint_local -- one 64-bit subtraction of the range's first
+        // id (global ids: n0, n0 + nA for the second graph; graph-local ids: 0 for both), then 32-bit tests; its id inside the pair is the
+        // difference plus the second graph's nA.
+        const uint32_t wA = endpoint_width(0, nA), wB = endpoint_width(nA, n);
+        const bool ids_global = KEYS || a.ids_are_global != 0;
+        for (int c = tid; c < E; c += T) {
+            const bool second = c >= EA;                // (a column of the pair's second graph: its vertices are nA .. n - 1)
+            const uint32_t cb = (uint32_t)c * 8u;
+            const int64_t ur = *reinterpret_cast<const int64_t *>(reinterpret_cast<const char *>(a.src + e0) + cb);
+            const int64_t vr = *reinterpret_cast<const int64_t *>(reinterpret_cast<const char *>(a.dst + e0) + cb);
+            const int64_t base = ids_global ? (second ? n0 + nA : n0) : 0;
+            const uint32_t width = second ? wB : wA, first = second ? (uint32_t)nA : 0u;
+            uint32_t ud, vd;
+            const bool u_ok = endpoint_local(ur, base, width, ud), v_ok = endpoint_local(vr, base, width, vd);
+            if (!(u_ok && v_ok)) { bad_lane = true; eu[c] = 0; ev[c] = 0; continue; }
+            const int u = (int)(first + ud), v = (int)(first + vd);
+            eu[c] = (vid_t)u; ev[c] = (vid_t)v;
+            if (u != v) {
+                atomicOr(reinterpret_cast<unsigned long long *>(&A[u]), 1ull << v);
+                atomicOr(reinterpret_cast<unsigned long long *>(&A[v]), 1ull << u);
+            }
+        }
+    } else
     for (int c = tid; c < E; c += T) {
         const bool second = c >= EA;                    // (a column of the pair's second graph: its vertices are nA .. n - 1)
         const int64_t off = a.ids_are_global ? n0 : (second ? -(int64_t)nA : 0);
-        int64_t u64, v64;
-        if constexpr (CYC > 0) {
-            const uint32_t cb = (uint32_t)c * 8u;
-            u64 = *reinterpret_cast<const int64_t *>(reinterpret_cast<const char *>(a.src + e0) + cb) - off;
-            v64 = *reinterpret_cast<const int64_t *>(reinterpret_cast<const char *>(a.dst + e0) + cb) - off;
-        } else {
-            u64 = a.src[e0 + c] - off; v64 = a.dst[e0 + c] - off;
-        }
+        const int64_t u64 = a.src[e0 + c] - off, v64 = a.dst[e0 + c] - off;
         const int64_t lo = second ? nA : 0, hi = second ? n : nA;
         if (u64 < lo || v64 < lo || u64 >= hi || v64 >= hi) {
-            if constexpr (CYC > 0) bad_lane = true;
-            else atomicMax(&misc[2], (int)GSN_ST_BAD_INDEX);
+            atomicMax(&misc[2], (int)GSN_ST_BAD_INDEX);
             if (edge_mode) { eu[c] = 0; ev[c] = 0; }
             continue;
         }
         const int u = (int)u64, v = (int)v64;
         if (edge_mode) { eu[c] = (vid_t)u; ev[c] = (vid_t)v; }
-        if constexpr (CYC == 0)
         atomicMax(&misc[second ? 5 : 1], (u > v ? u : v) + 1);  // graph-tool creates vertices 0..max id, self-loop columns included
         if (u != v) {
             atomicOr(reinterpret_cast<unsigned long long *>(&A[u * W + (v >> 6)]), 1ull << (v & 63));
@@ -737,6 +777,7 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
     COUNT_T(3);
     // ---- phase 2 (edge mode): CSR rank of every directed pair, last-duplicate-wins column, the rows that search ---------
     if (edge_mode) {
+        int n_slots;                             // slots of the CSR rank = the sum of the degrees (wave-uniform; CYC: from the scan's last lane)
         if (W == 1 && T == 64) {                 // one wave, n <= 64: the row starts are a wave prefix sum of the degrees
             const int d = tid < n ? popc64(A[tid]) : 0;
             int incl = d;
@@ -759,6 +800,8 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
             }
             if (tid <= n) rowstart[tid] = (rs_t)(incl - d);
             if (tid == 63 && n == 64) rowstart[64] = (rs_t)incl;
+            if constexpr (CYC > 0) n_slots = __builtin_amdgcn_readlane(incl, 63);      // (lanes from n on add nothing: the total)
+            else n_slots = 0;
         } else {
             for (int u = tid; u <= n; u += T) {
                 int s = 0;
@@ -768,9 +811,32 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
                 }
                 rowstart[u] = (rs_t)s;
             }
+            n_slots = 0;
         }
-        for (int i = tid; i < E; i += T) last[i] = -1;
+        // last[] is addressed by SLOT, not by column: a graph has two slots per undirected pair, which is more than its columns where pairs
+        // come in one direction only.  Every slot in use is cleared (cleared up to E only, the slots beyond held whatever the pass before
+        // left there: a stale column id made a live column lose its atomicMax, and rows of graphs with one-way pairs came out zero now and
+        // then), and every slot lies inside last[]: the launcher sizes it for a single graph's slots (count_launch: last_cap >= 2 e_decl or
+        // n_decl (n_decl - 1)), and a pair with more slots than that is redone graph by graph.
+        if constexpr (!(CYC > 0)) {                      // (the total is rowstart[n]: behind a barrier where more than one wave wrote the row starts)
+            __syncthreads();
+            n_slots = (int)rowstart[n];
+        }
+        if (ng > 1 && n_slots > a.last_cap) return 1;
+        for (int i = tid; i < (n_slots > E ? n_slots : E); i += T) last[i] = -1;
         __syncthreads();
+        if constexpr (CYC > 0) {
+            // CYC: the column's own slot AND the slot of its reverse pair in this one visit, both staged as 16-bit values -- the own slot
+            // where revof[c] will stand, the reverse slot in prim[c] (the compaction below writes prim[k] only for k <= c, behind the trip's
+            // reads) -- so that the pass below reads last[] twice and ranks nothing again.
+            for (int c = tid; c < E; c += T) {
+                const int u = eu[c], v = ev[c];
+                if (u == v) continue;
+                const int r = rowstart[u] + popc64(A[u] & ((1ull << v) - 1ull)), rr = rowstart[v] + popc64(A[v] & ((1ull << u) - 1ull));
+                revof[c] = (uint16_t)r; prim[c] = (uint16_t)rr;
+                atomicMax(&last[r], c);
+            }
+        } else
         for (int c = tid; c < E; c += T) {
             const int u = eu[c], v = ev[c];
             if (u == v) continue;
@@ -798,9 +864,13 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
                     int rev = -1;
                     if (u != v) {
                         live = last[revof[c]] == c;
-                        int rr = rowstart[v];
+                        int rr;
+                        if constexpr (CYC > 0) rr = prim[c];      // (staged by the visit above)
+                        else {
+                        rr = rowstart[v];
 #pragma unroll
                         for (int w = 0; w < W; ++w) rr += popc64(A[v * W + w] & below_word(u, w));
+                        }
                         rev = last[rr];
                     }
                     revof[c] = rev < 0 ? (uint16_t)0xffffu : (uint16_t)rev;
@@ -1046,10 +1116,27 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
         const uint32_t ncls_w = (uint32_t)a.enc_n[0] | ((uint32_t)a.enc_n[1] << 8) | ((uint32_t)a.enc_n[2] << 16) | ((uint32_t)a.enc_n[3] << 24);
         const bool clamp = a.enc_clamp != 0;
         const int col0 = a.enc16_col0;
+        // The int64 rows leave through a buffer resource over this pass's rows (scalar base, the lane's byte offset, the second half of a row
+        // as the instruction's immediate: no 64-bit vector add per trip; a store past the pass's last row would be dropped by the hardware).
+        // The rare row with a cell that went out by itself takes count_core.h's cell-by-cell arm through a pointer.
+        typedef unsigned st16_t __attribute__((ext_vector_type(4)));
+        typedef unsigned st8_t __attribute__((ext_vector_type(2)));
+        const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(orow, 0, rows * 32, 0x00020000);
+        const __amdgpu_buffer_rsrc_t mrs = __builtin_amdgcn_make_buffer_rsrc(mrow, 0, rows * 2, 0x00020000);      // (the masks of the same rows)
         for (int r = tid; r < rows; r += T) {
             const uint2 q = *reinterpret_cast<const uint2 *>(out_lds + 4 * r);
-            cyc_row_store(reinterpret_cast<int64_t *>(orow + (uint32_t)r * 32u), q.x, q.y, wide);
-            *reinterpret_cast<uint16_t *>(mrow + (uint32_t)r * 2u) = (uint16_t)(cyc_row_mask(q.x, q.y, ncls_w, clamp) << col0);
+            const int ob = r * 32;
+            if (cyc_row_has_direct(q.x, q.y)) cyc_row_store(reinterpret_cast<int64_t *>(orow + (uint32_t)ob), q.x, q.y, wide);
+            else if (wide) {
+                __builtin_amdgcn_raw_buffer_store_b128(st16_t{q.x & 0xffffu, 0u, q.x >> 16, 0u}, ors, ob, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(st16_t{q.y & 0xffffu, 0u, q.y >> 16, 0u}, ors, ob + 16, 0, 0);
+            } else {
+                __builtin_amdgcn_raw_buffer_store_b64(st8_t{q.x & 0xffffu, 0u}, ors, ob, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b64(st8_t{q.x >> 16, 0u}, ors, ob + 8, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b64(st8_t{q.y & 0xffffu, 0u}, ors, ob + 16, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b64(st8_t{q.y >> 16, 0u}, ors, ob + 24, 0, 0);
+            }
+            __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(cyc_row_mask(q.x, q.y, ncls_w, clamp) << col0), mrs, r * 2, 0, 0);
         }
     }
     // ---- phase 4: coalesced write of the staged rows --------------------------------------------------------------
@@ -1176,13 +1263,14 @@ template <int W, int T, bool DIR, bool TAIL, bool MOL = false, int CYC = 0, clas
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(CYC > 0 ? COUNT_CYC_WAVES : DIR ? 1 : (W == 1 ? COUNT_W1_WAVES : (W == 2 ? COUNT_W2_WAVES : (W == 4 ? COUNT_W4_WAVES : 1))))))
 void count_kernel(CountArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr bool KEYS = CYC > 0 && FL::KEYS;           // (the headline launch: side workgroups, pairs, status words zeroed here -- launch<>())
     int bid = (int)blockIdx.x;
-    if (a.side_mask) {                                   // (launches with side workgroups: one workgroup per item, no graph list)
+    if (KEYS || a.side_mask) {                           // (launches with side workgroups: one workgroup per item, no graph list)
         const int grp = bid / (SIDE_EVERY + 1), j = bid - grp * (SIDE_EVERY + 1);
         if (j == SIDE_EVERY) {
             const int i0 = grp * SIDE_EVERY, i1 = i0 + SIDE_EVERY < a.n_items ? i0 + SIDE_EVERY : a.n_items;
             const int per = (MOL || a.pair) ? 2 : 1;
-            side_block<T>(a, smem, per * i0, per * i1 < a.n_graphs ? per * i1 : a.n_graphs);
+            side_block<T, FL>(a, smem, per * i0, per * i1 < a.n_graphs ? per * i1 : a.n_graphs);
             return;
         }
         bid = grp * SIDE_EVERY + j;
@@ -1193,7 +1281,7 @@ void count_kernel(CountArgs a) {
     // one when it did not fit or held an error
     const int g0 = (MOL || a.pair) ? 2 * item : (a.graph_ids ? a.graph_ids[item] : item);
     const bool two = (MOL || a.pair) && g0 + 1 < a.n_graphs;
-    if (a.zero_status && threadIdx.x == 0) {           // (the thread that raises them later: same address, program order)
+    if ((KEYS || a.zero_status) && threadIdx.x == 0) {   // (the thread that raises them later: same address, program order)
         a.status[g0] = 0;
         if (two) a.status[g0 + 1] = 0;
     }
@@ -1320,7 +1408,14 @@ static int launch(CountArgs &a, int n_items, size_t lds, hipStream_t stream) {
             // every column a cycle of length <= 6 (count_launch: the launch's LDS was laid out for it, under these very conditions): the walk
             if (a.cyc_len) {
                 // (the headline step's flag combination as compile-time constants: count_body, CycKeys)
-                const bool keys = a.out && a.stage_out && a.enc_stage && a.enc_from_counts && a.enc_no32 && !a.enc16 && a.idmask && a.split == 1;
+                // -- and the launch-uniform rest of it: global vertex ids, pairs, status words zeroed by their workgroups, and side workgroups that
+                // leave the CSR with both sorted endpoint arrays, one node code column as key bytes and one edge code column in the key words
+                // (side_block<T, CycKeys>).  Anything else is CycAny's.
+                const SideArgs &sd = a.side;
+                const bool side_keys = a.side_mask == 7 && sd.csr_tgt && sd.csr_oth && sd.nkey && sd.ekeys && !sd.npack && !sd.epack && sd.ncode_cols == 1 && sd.ecode_cols == 1;
+                const bool keys = a.out && a.stage_out && a.enc_stage && a.enc_from_counts && a.enc_no32 && !a.enc16 && a.idmask && a.split == 1 &&
+                                  a.ids_are_global && a.pair && a.zero_status && side_keys;
+                trace("gsn count: cycle flags %s\n", keys ? "CycKeys" : "CycAny");
                 return keys ? launch_d<1, 64, false, false, true, 6, CycKeys>(a, n_items, lds, stream) : launch_d<1, 64, false, false, true, 6>(a, n_items, lds, stream);
             }
             if (mol) {
@@ -1531,7 +1626,13 @@ static int count_launch(const uint32_t *plan_host, const uint32_t *plan_dev, int
     a.off_eu = o; o += edge_mode ? align_up((int)max_edges * vid_bytes, 16) : 0;
     a.off_ev = o; o += edge_mode ? align_up((int)max_edges * vid_bytes, 16) : 0;
     a.off_rowstart = o; o += edge_mode ? align_up(((int)max_nodes + 1) * (W == 1 ? 2 : 4), 16) : 0;
-    a.off_last = o; o += edge_mode ? align_up((int)max_edges * 4, 16) : 0;
+    // last[] holds one entry per SLOT of the CSR rank (two per undirected pair): a single graph has at most min(2 e_decl, n_decl (n_decl - 1)) of
+    // them, which a pair's 2 e_decl columns already cover; a pair with more is redone graph by graph (count_body, phase 2)
+    {
+        const int64_t one = 2 * (int64_t)a.e_decl < (int64_t)a.n_decl * (a.n_decl - 1) ? 2 * (int64_t)a.e_decl : (int64_t)a.n_decl * (a.n_decl - 1);
+        a.last_cap = (int)(one > max_edges ? one : max_edges);
+    }
+    a.off_last = o; o += edge_mode ? align_up(a.last_cap * 4, 16) : 0;
     if (edge_mode && max_edges >= 65535) return set_error(GSN_E_UNSUPPORTED, "gsn_count_hip: %lld columns per workgroup (16-bit column tables; LDS ends far earlier)", (long long)max_edges);
     a.off_prim = o; o += edge_mode ? align_up((int)max_edges * 2, 16) : 0;
     a.off_revof = o; o += edge_mode ? align_up((int)max_edges * 2, 16) : 0;

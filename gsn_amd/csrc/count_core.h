@@ -47,6 +47,19 @@ GSN_HD uint64_t below_word(int p, int wi) {
     return wi < pw ? ~0ull : (wi == pw ? ((1ull << (p & 63)) - 1ull) : 0ull);
 }
 
+// A column endpoint against its graph's vertex range: is  base <= x < base + width ?  d = x - base where it is.  One 64-bit subtraction,
+// then the high word against zero and ONE unsigned 32-bit compare -- not two 64-bit compares (a 64-bit compare is two vector instructions
+// and a carry chain on gfx9).  The subtraction wraps (unsigned): an x below base, INT64_MIN included, leaves 2^64 - (base - x), whose high
+// word is not zero for every base a batch can have (0 <= base < 2^62); an x of base + 2^32 and more leaves a high word >= 1.  width 0:
+// nothing is inside.
+GSN_HD bool endpoint_local(const int64_t x, const int64_t base, const uint32_t width, uint32_t &d) {
+    const uint64_t diff = (uint64_t)x - (uint64_t)base;
+    d = (uint32_t)diff;
+    return (uint32_t)(diff >> 32) == 0u && d < width;
+}
+// the width of [lo, hi) for endpoint_local: an empty or inverted range (a pointer array that is not monotone) holds nothing
+GSN_HD uint32_t endpoint_width(const int64_t lo, const int64_t hi) { return hi > lo ? (uint32_t)(hi - lo) : 0u; }
+
 // bit planes of the vertices' degrees inside each d-core: plane p of core d has bit v set iff bit p of |N(v) & core_d| is set (v in core_d);
 // layout [CORE_MAX + 1][DEG_PLANES][W] words (n <= 768 < 2^10).  sum_{v in S} deg(v) = sum_p 2^p popc(S & plane_p).
 constexpr int DEG_PLANES = 10;

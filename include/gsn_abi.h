@@ -215,7 +215,7 @@ int gsn_count_encode_pack16_hip(const uint32_t *plan_host, const uint32_t *plan_
  * node_ptr[0] must be 0, node_ptr[n_graphs] = n_nodes, edge_ptr[n_graphs] = n_edges (a collated batch).  Statuses: a column that leaves
  * its graph raises GSN_ST_BAD_INDEX on that graph (its CSR entries are then unspecified but inside the batch's ranges), a graph
  * beyond max_nodes / max_edges GSN_ST_TOO_LARGE (sorted all the same when it fits the launch's LDS, else its vertices own no columns and
- * its columns map to themselves: as gsn_csr_build_graphs_hip); *code_status (device int32, caller-zeroed, may be NULL) gets 1 ORed in when a code lies outside its
+ * its columns map to themselves: as gsn_csr_build_graphs_hip); *code_status (device int32, may be NULL; set to 0 by the launch's first side workgroup: the word is this launch's) gets 1 ORed in when a code lies outside its
  * column's classes and clamp is 0 (that column's segment stays zero, as gsn_one_hot_pack16_hip). */
 typedef struct {
     int csr_row;                 /* which row of edge_index is the aggregation target (1: flow = source_to_target) */
