@@ -101,6 +101,11 @@ SIGNATURES = {
                                                c_i64, ctypes.POINTER(gsn_count_side), ctypes.POINTER(gsn_count_keys), c_vp]),
     "gsn_count_layer_step_keys_hip": (c_int, [ctypes.POINTER(gsn_count_call), ctypes.POINTER(gsn_layer_pack16_call), ctypes.POINTER(gsn_count_keys),
                                               c_vp, c_i64, c_vp, c_vp]),
+    "gsn_count_layer_step_tabs_hip": (c_int, [ctypes.POINTER(gsn_count_call), ctypes.POINTER(gsn_layer_pack16_call), ctypes.POINTER(gsn_count_keys),
+                                              c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "gsn_layer_key_tables_words": (c_i64, []),
+    "gsn_layer_key_tables_max_rows": (c_i64, []),
+    "gsn_layer_key_tables_hip": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "gsn_layer_keys_byte_table": (c_int, [c_vp]),
     "gsn_pack16_rows_hip": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
     "gsn_one_hot_pack16_hip": (c_int, [c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),

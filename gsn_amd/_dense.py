@@ -257,7 +257,7 @@ def _prep_key(st):
     if bn is not None:
         bk = (bn.running_mean._version, bn.running_var._version, bn.running_mean.data_ptr(),
               (bn.weight._version, bn.bias._version) if bn.affine else None)
-    return (st.weight.data_ptr(), st.weight._version, tuple(st.weight.shape), bk)
+    return (st.weight.data_ptr(), st.weight._version, tuple(st.weight.shape), bk, None if st.bias is None else st.bias._version)
 
 
 def _prepared(kind, ge, g0, g1, d_x, dev, owner=None, attr=None, key=None):

@@ -126,6 +126,12 @@ extern "C" int gsn_count_layer_step_hip(const gsn_count_call *c, const gsn_layer
 // gathers its operand rows from the node dictionary and the byte table through them -- no row pack is written or read
 extern "C" int gsn_count_layer_step_keys_hip(const gsn_count_call *c, const gsn_layer_pack16_call *l, const gsn_count_keys *keys, const uint16_t *node_dict,
                                              int64_t dict_rows, void *event_between, void *stream) {
+    return gsn_count_layer_step_tabs_hip(c, l, keys, node_dict, dict_rows, nullptr, event_between, stream);
+}
+
+// ... and with the x_i tables of gsn_layer_key_tables_hip (`tabs`, may be null): the edge stage starts from a table row per edge row
+extern "C" int gsn_count_layer_step_tabs_hip(const gsn_count_call *c, const gsn_layer_pack16_call *l, const gsn_count_keys *keys, const uint16_t *node_dict,
+                                             int64_t dict_rows, const float *tabs, void *event_between, void *stream) {
     if (!c || !l || !keys || !c->side) return gsn::set_error(GSN_E_INVALID, "gsn_count_layer_step_keys_hip: null call struct / keys / side");
     if (!keys->nkey || !keys->ekeys || !keys->idmask || !node_dict) return gsn::set_error(GSN_E_INVALID, "gsn_count_layer_step_keys_hip: null key array / node dictionary");
     if (!c->side->node_codes || !c->side->edge_codes) return gsn::set_error(GSN_E_INVALID, "gsn_count_layer_step_keys_hip: node and edge codes are both needed");
@@ -143,7 +149,7 @@ extern "C" int gsn_count_layer_step_keys_hip(const gsn_count_call *c, const gsn_
     if (rc != GSN_OK) return rc;
     if (event_between && hipEventRecord(reinterpret_cast<hipEvent_t>(event_between), reinterpret_cast<hipStream_t>(stream)) != hipSuccess)
         return gsn::set_error(GSN_E_HIP, "gsn_count_layer_step_keys_hip: hipEventRecord(event_between)");
-    const gsn::RpKeys k{keys->ekeys, keys->nkey, keys->idmask, node_dict, dict_rows, c->side->edge_col0};
+    const gsn::RpKeys k{keys->ekeys, keys->nkey, keys->idmask, node_dict, dict_rows, c->side->edge_col0, tabs};
     rc = gsn::rp_forward(l->n_nodes, l->n_edges, l->seg_ptr, l->edge, l->x, l->d_x, l->node0, l->node1, l->prepared, nullptr, l->edge_rows, l->out,
                          reinterpret_cast<hipStream_t>(stream), &k);
     if (rc == 1) return gsn::set_error(GSN_E_UNSUPPORTED, "gsn_count_layer_step_keys_hip: key arrays beyond 2 GiB (32-bit buffer offsets)");

@@ -53,6 +53,7 @@ struct RpArgs {
     const uint32_t *ekeys;             // per sorted edge row: dictionary row of x_i | that of x_j << 8 | edge-code class mask << 16
     const uint8_t *nkey;               // per node: its dictionary row
     int edge_col0;                     // first pack column of the edge-code classes
+    const float *tabs;                 // TABS arm: the x_i tables TE fp32 [4][RP_TAB_ROWS][32] (rp_key_tables_kernel), else null
 };
 
 // KEYS: r[0] = the edge key word, r[2] = perm (r[1] unused); nk = the dictionary row of node m0 + li
@@ -85,6 +86,26 @@ __device__ __forceinline__ void rp_idx_load(const RpArgs &a, const RrDesc &d, in
 constexpr int RP_BYTE_TAB_BYTES = 256 * 16;
 __device__ __host__ __forceinline__ unsigned rp_byte_tab_word(unsigned b, int q) {
     return ((b >> (2 * q)) & 1u ? 0x3c00u : 0u) | ((b >> (2 * q + 1)) & 1u ? 0x3c000000u : 0u);
+}
+
+// TABS: the x_i part of the edge stage -- chunks 0 and 1 of a row, its bias on column 31 -- is a function of the dictionary row of the row's
+// TARGET alone, and it stands at the front of the accumulation chain (from C = 0).  rp_key_tables_kernel runs those very products once per
+// dictionary row (the same helper, rp_edge_chunk, the same operand roles and order) and leaves the accumulator state as TE[fb][k][32]
+// (feature block, dictionary row, feature); a block's accumulators then START from TE[key of the row's target] and only chunks 2 .. 4 are
+// multiplied.  In LDS table fb lies where the fragments of chunks 0 and 1 of feature block fb lay (4 KiB each, no longer read): 31 rows of
+// 128 bytes.  An accumulator register holds ONE feature (the lane's) of one row: a lane reads 16 words per table, lanes of a half 32
+// consecutive words of one table row (no bank conflict).
+constexpr int RP_TAB_ROWS = 31;
+constexpr int RP_TAB_WORDS = 4 * RP_TAB_ROWS * 32;
+
+// one chunk of the edge stage for a PAIR of feature blocks: low plane before high plane, the two accumulator chains issued alternately
+template <class U>
+__device__ __forceinline__ void rp_edge_chunk(const rr_u4 &A, const rr_u4 &f0h, const rr_u4 &f0l, const rr_u4 &f1h, const rr_u4 &f1l, f32x16 &acc0, f32x16 &acc1, U &&under) {
+    RR_MFH(A, f0l, acc0);
+    RR_MFH(A, f1l, acc1);
+    under();
+    RR_MFH(A, f0h, acc0);
+    RR_MFH(A, f1h, acc1);
 }
 
 #define RP_LOAD(RS, VOFF, IMM) __builtin_bit_cast(rr_u4, __builtin_amdgcn_raw_buffer_load_b128(RS, (int)((VOFF) + (IMM)), 0, 0))
@@ -127,7 +148,7 @@ __device__ __forceinline__ unsigned rp_pk_max_u16(unsigned a, unsigned b) { unsi
 #define RP_S1E 1           // node stage 1: the first pair's output rows leave under the second pair's products
 #endif
 
-template <int WB, int NKX, bool PROF, bool KEYS = false>
+template <int WB, int NKX, bool PROF, bool KEYS = false, bool TABS = false>
 __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_NW / 4, RR_NW / 4))) void layer_fused_kernel_rp(RpArgs a, unsigned long long *prof) {
     auto clk = [&]() -> unsigned {
         if (!PROF) return 0u;
@@ -140,6 +161,7 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
     using SH = RrShape<WB, NKX>;
     constexpr int NKS = SH::NKS, NK0 = SH::NK0;
     static_assert(WB == 4 && NKX == 2, "two pairs of feature blocks; the node pack is two chunks wide");
+    static_assert(!TABS || KEYS, "the tables are indexed by the key words");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int tid = threadIdx.x;
@@ -154,6 +176,16 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
     {
         const rr_u4 *src = reinterpret_cast<const rr_u4 *>(a.prep + RR_HDR);
         rr_u4 *dst = reinterpret_cast<rr_u4 *>(smem);
+        if constexpr (TABS) {
+            // (fragments 10 fb .. + 4 = chunks 0 and 1 of feature block fb, both planes: not read; table fb takes their room)
+            static_assert(SH::F_WE == 0 && RP_TAB_ROWS * 128 <= 4096, "a table fits the room of the four fragments it replaces");
+            for (int i = tid; i < SH::F_LDS * 64; i += 64 * RR_NW) {
+                const int f = i >> 6;
+                if (!(f < 2 * WB * RR_NKE && f % (2 * RR_NKE) < 4)) dst[i] = src[i];
+            }
+            float *te = reinterpret_cast<float *>(smem);
+            for (int i = tid; i < RP_TAB_WORDS; i += 64 * RR_NW) te[(i / (RP_TAB_ROWS * 32)) * (2 * RR_NKE * 256) + i % (RP_TAB_ROWS * 32)] = a.tabs[i];
+        } else
         for (int i = tid; i < SH::F_LDS * 64; i += 64 * RR_NW) dst[i] = src[i];
         const float *tsrc = reinterpret_cast<const float *>(a.prep + RR_HDR + SH::F_ALL * 256);
         float *tdst = reinterpret_cast<float *>(smem + SH::F_LDS * 1024);
@@ -243,7 +275,7 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
             // row only its identifier mask, 2 bytes through perm -- the row itself is looked up at the block's top
             const unsigned k = (unsigned)r[0];
             const unsigned vt = ((k & 0xffu) << 6) | ((unsigned)lh << 4), vs = (((k >> 8) & 0xffu) << 6) | ((unsigned)lh << 4);
-            g[0] = RP_LOAD(rs_n, vt, 0); g[1] = RP_LOAD(rs_n, vt, 32);
+            if constexpr (!TABS) { g[0] = RP_LOAD(rs_n, vt, 0); g[1] = RP_LOAD(rs_n, vt, 32); }
             g[2] = RP_LOAD(rs_n, vs, 0); g[3] = RP_LOAD(rs_n, vs, 32);
             g[4][0] = (unsigned)__builtin_amdgcn_raw_buffer_load_b16(rs_e, (int)((unsigned)r[2] << 1), 0, 0);
         } else {
@@ -296,7 +328,8 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
             // ---- the gathered rows ARE the operand fragments; the next block's gathers fly beside them in the other set -------------------
             rr_u4 Ah[RR_NKE];
 #pragma unroll
-            for (int c = 0; c < RR_NKE; ++c) Ah[c] = gc[c];
+            for (int c = TABS ? 2 : 0; c < RR_NKE; ++c) Ah[c] = gc[c];
+            const unsigned ko = (kc & 0xffu) << 7;        // TABS: byte offset of this lane's ROW (block row li) in a table
             if constexpr (KEYS) {
                 // the edge-level fragment: lane (e, h) takes byte h of the row's hot-column mask (identifier classes | edge-code classes behind
                 // them) and reads its eight fp16 values from the byte table -- used ~16 products later (chunk 4 of the first pair)
@@ -374,18 +407,54 @@ __global__ __launch_bounds__(64 * RR_NW) __attribute__((amdgpu_waves_per_eu(RR_N
                     for (int c = 0; c < RR_NKE; ++c) {
                         rr_u4 n0h = f0h, n0l = f0l, n1h = f1h, n1l = f1l;
                         if (c + 1 < RR_NKE) frag4(fp, c + 1, n0h, n0l, n1h, n1l);
-                        RR_MFH(Ah[c], f0l, acc0);
-                        RR_MFH(Ah[c], f1l, acc1);
-                        under(c);
-                        RR_MFH(Ah[c], f0h, acc0);
-                        RR_MFH(Ah[c], f1h, acc1);
+                        rp_edge_chunk(Ah[c], f0h, f0l, f1h, f1l, acc0, acc1, [&]() { under(c); });
+                        RR_SB();
+                        f0h = n0h; f0l = n0l; f1h = n1h; f1l = n1l;
+                    }
+                };
+                // TABS: chunks 2 .. 4 on accumulators that hold the table rows; six slots for work under the products (two per chunk)
+                auto products_t = [&](int fp, f32x16 &acc0, f32x16 &acc1, auto &&under) {
+                    rr_u4 f0h, f0l, f1h, f1l;
+                    frag4(fp, 2, f0h, f0l, f1h, f1l);
+#pragma unroll
+                    for (int c = 2; c < RR_NKE; ++c) {
+                        rr_u4 n0h = f0h, n0l = f0l, n1h = f1h, n1l = f1l;
+                        if (c + 1 < RR_NKE) frag4(fp, c + 1, n0h, n0l, n1h, n1l);
+                        rp_edge_chunk(Ah[c], f0h, f0l, f1h, f1l, acc0, acc1, [&]() { under(2 * (c - 2)); });
+                        under(2 * (c - 2) + 1);
                         RR_SB();
                         f0h = n0h; f0l = n0l; f1h = n1h; f1l = n1l;
                     }
                 };
                 f32x16 qa0, qa1, ra0, ra1;
+                if constexpr (TABS) {
+                    // row crow(r, lh) of the block is register r of an accumulator tile: its table row offset comes from the lane that holds the
+                    // row's key word, the lane's own feature is the word in the row; the four tables lie 10 fragments apart
+                    typedef const volatile __attribute__((address_space(3))) float *ldsf;      // (volatile: left alone the compiler pairs the reads of two tables into one
+                    //  two-word read and moves every word to its accumulator register afterwards)
+                    const unsigned tb = ldsb[0] - 16u * (unsigned)lane + 4u * (unsigned)li;
+                    unsigned ta[16];
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) ta[r] = (unsigned)__builtin_amdgcn_ds_bpermute(4 * rr_crow(r, lh), (int)ko) + tb;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        qa0[r] = *reinterpret_cast<ldsf>(ta[r]);
+                        qa1[r] = *reinterpret_cast<ldsf>(ta[r] + 2 * RR_NKE * 1024);
+                    }
+                    RR_SB();
+                    // (the second pair's table rows arrive under the first pair's products)
+                    products_t(0, qa0, qa1, [&](int s) {
+#pragma unroll
+                        for (int r = 3 * s; r < 3 * s + 3 && r < 16; ++r) {
+                            ra0[r] = *reinterpret_cast<ldsf>(ta[r] + 2 * 2 * RR_NKE * 1024);
+                            ra1[r] = *reinterpret_cast<ldsf>(ta[r] + 3 * 2 * RR_NKE * 1024);
+                        }
+                    });
+                    products_t(2, ra0, ra1, [&](int s) { if (s < RR_NKE) ep_step(s, qa0, qa1, sacc[0], sacc[1], M); });
+                } else {
                 products(0, qa0, qa1, [&](int) {});
                 products(2, ra0, ra1, [&](int c) { ep_step(c, qa0, qa1, sacc[0], sacc[1], M); });
+                }
                 t2 = clk();
                 // the second pair's epilogue behind its own products
                 load_x();
@@ -817,6 +886,38 @@ __global__ void pack16_rows_kernel(const float *src, int64_t rows, int width, ui
     if (bad) atomicOr(status, 1);
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// The x_i tables of the TABS arm: TE[fb][k][f] = accumulator (row k, feature 32 fb + f) of the edge stage after chunks 0 and 1 on dictionary
+// row k, from C = 0.  One wave per pair of feature blocks; the dictionary rows stand where a block's edge rows stand (lane (k, h): bytes
+// 32 c + 16 h of row k; rows past the dictionary read as zeros through the buffer's range check), the weight fragments are the prepared
+// buffer's, read as the layer kernel reads them from LDS, and the products are rp_edge_chunk's: the layer kernel's own.
+__global__ __launch_bounds__(128) void rp_key_tables_kernel(const unsigned *prep, const uint16_t *dict, int dict_rows, float *tabs) {
+    using SH = RrShape<4, 2>;
+    const int lane = threadIdx.x & 63, fp = 2 * (int)(threadIdx.x >> 6);
+    const int li = lane & 31, lh = lane >> 5;
+    const __amdgpu_buffer_rsrc_t rs_n = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(dict), 0, dict_rows * 64, 0x00020000);
+    const rr_u4 *frags = reinterpret_cast<const rr_u4 *>(prep + RR_HDR);
+    auto frag = [&](int f) { return frags[f * 64 + lane]; };
+    f32x16 acc0, acc1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
+    const unsigned vt = ((unsigned)li << 6) | ((unsigned)lh << 4);
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const rr_u4 A = RP_LOAD(rs_n, vt, 32 * c);
+        rp_edge_chunk(A, frag(SH::F_WE + 2 * (fp * RR_NKE + c)), frag(SH::F_WE + 2 * (fp * RR_NKE + c) + 1), frag(SH::F_WE + 2 * ((fp + 1) * RR_NKE + c)),
+                      frag(SH::F_WE + 2 * ((fp + 1) * RR_NKE + c) + 1), acc0, acc1, []() {});
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int k = rr_crow(r, lh);
+        if (k < RP_TAB_ROWS) {
+            tabs[(fp * RP_TAB_ROWS + k) * 32 + li] = acc0[r];
+            tabs[((fp + 1) * RP_TAB_ROWS + k) * 32 + li] = acc1[r];
+        }
+    }
+}
+
 static int rp_blocks(const gsn_chain_stage *edge, int64_t d_x, const float *x, int *edge_cols) {
     // blocks: x through one index, x through another, then the edge-level blocks through one common index; <= 16 columns of those
     if (edge->n_blocks < 2 || edge->n_blocks > 6 || !edge->blocks) return 0;
@@ -853,6 +954,8 @@ int rp_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const g
             return set_error(GSN_E_INVALID, "gsn_count_layer_step_keys_hip: node dictionary of %lld rows (1 .. 256), %d edge-level columns (>= 1), edge codes at column %d, %lld edge rows",
                              (long long)keys->dict_rows, cols, keys->edge_col0, (long long)edge_rows);
         if (edge_rows * 2 > 0x7fffffffll) return 1;
+        if (keys->tabs && (keys->dict_rows > RP_TAB_ROWS || (reinterpret_cast<uintptr_t>(keys->tabs) & 3)))
+            return set_error(GSN_E_INVALID, "gsn_count_layer_step_tabs_hip: x_i tables with a node dictionary of %lld rows (<= %d)", (long long)keys->dict_rows, RP_TAB_ROWS);
     } else {
     if (!pack || !pack->node_rows || (cols > 0 && !pack->edge_rows)) return set_error(GSN_E_INVALID, "gsn_layer_fused_fwd_pack16_hip: null pack");
     if ((reinterpret_cast<uintptr_t>(pack->node_rows) | reinterpret_cast<uintptr_t>(pack->edge_rows)) & 15) return set_error(GSN_E_INVALID, "gsn_layer_fused_fwd_pack16_hip: packs must be 16-byte aligned");
@@ -867,6 +970,7 @@ int rp_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const g
         a.node16 = keys->node_dict; a.node_bytes = (unsigned)(keys->dict_rows * 64);
         a.edge16 = keys->idmask; a.edge_bytes = (unsigned)(edge_rows * 2); a.edge_shift = 1;
         a.ekeys = keys->ekeys; a.nkey = keys->nkey; a.edge_col0 = keys->edge_col0;
+        a.tabs = sw_on(SW_RP_TABLES, true) ? keys->tabs : nullptr;
     } else {
         a.node16 = pack->node_rows; a.node_bytes = (unsigned)(n_nodes * 64);
     }
@@ -890,6 +994,12 @@ int rp_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const g
     // (the KEYS variant's byte table lies behind the shared layout: its launch alone is sized for it)
     const int lds_bytes = SH::LDS_BYTES + (keys ? RP_BYTE_TAB_BYTES : 0);
     static_assert(SH::LDS_BYTES % 16 == 0 && SH::LDS_BYTES + RP_BYTE_TAB_BYTES <= 160 * 1024, "the byte table fits behind the weights");
+    const bool tabs = a.tabs != nullptr;
+    if (tabs) {
+        // (no profiling build of this arm: GSN_FUSED_PROF takes the KEYS arm)
+        static DeviceOnce attr_set_tabs;
+        if (int rc = lds_limit(&attr_set_tabs, {reinterpret_cast<const void *>(&layer_fused_kernel_rp<4, 2, false, true, true>)}, "layer_fused_kernel_rp tabs", lds_bytes)) return rc;
+    }
     if (keys) {
         const void *fn = prof_on ? reinterpret_cast<const void *>(&layer_fused_kernel_rp<4, 2, true, true>) : reinterpret_cast<const void *>(&layer_fused_kernel_rp<4, 2, false, true>);
         static DeviceOnce attr_set_keys;
@@ -899,7 +1009,8 @@ int rp_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const g
         static DeviceOnce attr_set;
         if (int rc = lds_limit(&attr_set, {fn}, "layer_fused_kernel_rp")) return rc;
     }
-    trace("gsn chain: layer_fused_kernel_rp<4,2>%s nodes %d edges %d grid %lld ranges %d\n", keys ? " keys" : "", a.n_nodes, a.n_edges, (long long)gx, a.n_ranges);
+    trace("gsn chain: layer_fused_kernel_rp<4,2>%s nodes %d edges %d grid %lld ranges %d%s\n", keys ? " keys" : "", a.n_nodes, a.n_edges, (long long)gx, a.n_ranges,
+          tabs && !prof_on ? " x_i tables" : "");
     if (prof_on) {
         ProfCounters prof(32 + 2 * (size_t)a.n_ranges, st);
         if (keys) hipLaunchKernelGGL((layer_fused_kernel_rp<4, 2, true, true>), dim3((unsigned)gx), dim3(64 * RR_NW), lds_bytes, st, a, prof.ptr());
@@ -929,6 +1040,8 @@ int rp_forward(int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, const g
                 fprintf(stderr, "rpprof range %s: blocks %llu tiles %llu total %llu cycles | per block: top %.0f edge %.0f | per tile: exposed edge epilogue %.0f stage0 %.0f split %.0f stage1 %.0f\n",
                         w ? "mid" : "0", o[6], o[7], o[8], o[0] / nb, o[1] / nb, o[2] / nt, o[3] / nt, o[4] / nt, o[5] / nt);
             }
+    } else if (tabs) {
+        hipLaunchKernelGGL((layer_fused_kernel_rp<4, 2, false, true, true>), dim3((unsigned)gx), dim3(64 * RR_NW), lds_bytes, st, a, (unsigned long long *)nullptr);
     } else if (keys) {
         hipLaunchKernelGGL((layer_fused_kernel_rp<4, 2, false, true>), dim3((unsigned)gx), dim3(64 * RR_NW), lds_bytes, st, a, (unsigned long long *)nullptr);
     } else {
@@ -953,6 +1066,19 @@ extern "C" int gsn_pack16_rows_hip(const float *src, int64_t rows, int64_t width
     hipLaunchKernelGGL(pack16_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, rows, (int)width, dst,
                        (int)dst_stride, (int)col0, (int)(one_col < 0 ? -1 : one_col), status);
     return launch_check("pack16_rows_kernel");
+}
+
+// the x_i tables of the TABS arm (include/gsn_abi.h): `prepared` is gsn_layer_fused_pack16_prepare_hip's buffer
+extern "C" int64_t gsn_layer_key_tables_words(void) { return RP_TAB_WORDS; }
+extern "C" int64_t gsn_layer_key_tables_max_rows(void) { return RP_TAB_ROWS; }
+extern "C" int gsn_layer_key_tables_hip(const void *prepared, const uint16_t *node_dict, int64_t dict_rows, float *tabs, void *stream) {
+    if (!prepared || !node_dict || !tabs || ((reinterpret_cast<uintptr_t>(prepared) | reinterpret_cast<uintptr_t>(node_dict)) & 15) || (reinterpret_cast<uintptr_t>(tabs) & 3))
+        return set_error(GSN_E_INVALID, "gsn_layer_key_tables_hip: null / misaligned prepared buffer, node dictionary or tables");
+    if (dict_rows < 1 || dict_rows > RP_TAB_ROWS)
+        return set_error(GSN_E_UNSUPPORTED, "gsn_layer_key_tables_hip: node dictionary of %lld rows (1 .. %d)", (long long)dict_rows, RP_TAB_ROWS);
+    hipLaunchKernelGGL(rp_key_tables_kernel, dim3(1), dim3(128), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const unsigned *>(prepared), node_dict,
+                       (int)dict_rows, tabs);
+    return launch_check("rp_key_tables_kernel");
 }
 
 // the byte table of the KEYS variant as the kernel's prologue fills it (fp16 bits [256][8]): for hosts and tests

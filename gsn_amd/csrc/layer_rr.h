@@ -36,6 +36,7 @@ struct RpKeys {
     const uint16_t *node_dict;
     int64_t dict_rows;
     int edge_col0;
+    const float *tabs = nullptr;      // the x_i tables of gsn_layer_key_tables_hip (dict_rows <= 31): the TABS arm; null: the KEYS arm
 };
 
 }  // namespace gsn

@@ -46,6 +46,7 @@ enum SwitchLife { ONCE, LIVE };
     X(FUSED_W, ONCE, "int, default 1: 0 refuses layer_fused_kernel_w")                                                                     \
     X(FUSED_G, ONCE, "int, default 1: 0 refuses layer_fused_kernel_g")                                                                     \
     X(RP_OLD_SHARE, ONCE, "float, default 0.6: share of the grid that layer_fused_kernel_rp gives to its first range")                     \
+    X(RP_TABLES, LIVE, "on/off, default on: 0 keeps layer_fused_kernel_rp on its KEYS arm where the step hands it x_i tables")             \
     /* linear layers */                                                                                                                    \
     X(LINEAR_SPLITK_RANGES, ONCE, "int, default -1 (automatic): forced split-k range count of the small bf16x6 linear, 0 = never")         \
     X(LINEAR_SMALL_MAX, ONCE, "int, default 96: most 128-row tiles that still take the 32-row-tile kernel, 0 = never")                     \

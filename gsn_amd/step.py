@@ -13,7 +13,9 @@ Layer 0's inputs are one-hot encodings of a few integer codes, so the step does 
 (``gsn_count_layer_step_keys_hip``): the counting launch leaves one key byte per vertex, one key word per sorted column and a 16-bit mask of
 the identifier classes per column, and the layer gathers its operand rows from a node DICTIONARY (one row per code tuple, built once by
 ``gsn_one_hot_pack16_hip`` itself) and a byte table -- the same fragments bit for bit, ~0.2 GB per 65 536 molecules neither written nor
-read back.  The key path is taken when the dictionary has at most 256 rows (``keys_path_ok``); otherwise the packs, as before.
+read back.  The key path is taken when the dictionary has at most 256 rows (``keys_path_ok``); otherwise the packs, as before.  With at
+most 31 rows (``tables_path_ok``) the edge stage does not multiply the x_i chunks either: its accumulators start from a table of that product
+per dictionary row, made once per prepared weight set by the kernel's own instructions (``gsn_layer_key_tables_hip``) -- the same bits.
 
 ``CountLayerStep`` keeps the two argument structs of the C entry filled in, so a step costs one foreign call (the eager composition
 ``count_batch`` + ``layer(Codes, ...)`` costs six launches through ~0.3 ms of Python).  Results are those of the composition, bit for bit
@@ -22,6 +24,7 @@ read back.  The key path is taken when the dictionary has at most 256 rows (``ke
 from __future__ import annotations
 
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -59,6 +62,28 @@ def node_dict_tuples(n_classes, clamp):
 def keys_path_ok(n_classes, clamp):
     """The gate of the key path: one byte names a dictionary row."""
     return int(np.prod(node_key_radices(n_classes, clamp), dtype=np.int64)) <= 256
+
+
+TABLE_ROWS = 31        # rows of the layer kernel's x_i tables (gsn_layer_key_tables_max_rows): what fits the room of the fragments they replace
+
+
+def tables_path_ok(n_classes, clamp):
+    """The gate of the table arm of the key path (``gsn_count_layer_step_tabs_hip``): the node dictionary has at most TABLE_ROWS rows.  The
+    tables hold the edge stage's accumulators behind the x_i chunks, which depend on the target's dictionary row alone whatever the weights
+    are, so no property of the weights enters (a table for node stage 0's [x | deg] chunks would need the folded weight's degree column
+    W3a b2 to be zero, which it is not for a msg_fn with a bias: no such table is built)."""
+    return keys_path_ok(n_classes, clamp) and int(np.prod(node_key_radices(n_classes, clamp), dtype=np.int64)) <= TABLE_ROWS
+
+
+def _tables_switch():
+    """GSN_RP_TABLES (csrc/switches.h; read at every step): 0 keeps the layer on its KEYS arm."""
+    v = os.environ.get("GSN_RP_TABLES")
+    if v is None:
+        return True
+    try:
+        return int(v) != 0
+    except ValueError:
+        return False
 
 
 _NODE_DICTS = {}
@@ -127,6 +152,7 @@ class CountLayerStep:
         self._keys = _abi.gsn_count_keys()
         self._force_packs = bool(force_packs)      # (tests: the pack path on shapes the key path takes)
         self.on_keys = False                       # which path the last step took
+        self.on_tables = False                     # ... and whether its edge stage started from the x_i tables (tables_path_ok)
         self._dict = None
         self._bound = None
 
@@ -172,7 +198,8 @@ class CountLayerStep:
                 raise ValueError("CountLayerStep: activation %r is outside the one-launch layer kernel" % st.act)
             if st.bn is not None and (st.bn.training or st.bn.running_mean is None):
                 raise RuntimeError("CountLayerStep: a BatchNorm1d in train mode / without running statistics")
-        key = (tuple(_dense._prep_key(st) for st in stages), d_x, getattr(layer, "_fold_gen", 0), N, E, self.on_keys, 0 if self._dict is None else self._dict.data_ptr())
+        key = (tuple(_dense._prep_key(st) for st in stages), d_x, getattr(layer, "_fold_gen", 0), N, E, self.on_keys, 0 if self._dict is None else self._dict.data_ptr(),
+               self.on_tables)
         if self._lay is not None and self._lay[0] == key:
             return self._lay[1]
         for st in stages:
@@ -195,10 +222,17 @@ class CountLayerStep:
         if not L.gsn_layer_fused_pack16_supported(ctypes.byref(ge), d_x, ctypes.byref(g0), ctypes.byref(g1)):
             raise ValueError("CountLayerStep: shape outside the packed-row layer kernel (every stage 128 wide, d_x + 4 <= 32, <= 16 edge-level columns)")
         prep = _dense._prepared("_pack16", ge, g0, g1, d_x, dev)
+        tabs = None
+        if self.on_tables:
+            # the x_i tables belong to this prepared buffer and this dictionary: made with it (under capture: recorded with it)
+            tabs = torch.empty(int(L.gsn_layer_key_tables_words()), dtype=torch.float32, device=dev)
+            with _abi.device_guard(dev):
+                _abi.check(L.gsn_layer_key_tables_hip(prep.data_ptr(), self._dict.data_ptr(), self._dict.shape[0], tabs.data_ptr(), _abi.current_stream()),
+                           "gsn_layer_key_tables_hip")
         d_out = node_stages[1].weight.shape[0]
         flops = 2.0 * E * edge_stages[0].weight.shape[1] * edge_stages[0].weight.shape[0]
         flops += 2.0 * N * (node_stages[0].weight.shape[1] * node_stages[0].weight.shape[0] + node_stages[1].weight.shape[1] * d_out)
-        val = (ge, g0, g1, prep, keep, d_out, flops)
+        val = (ge, g0, g1, prep, keep, d_out, flops, tabs)
         self._lay = (key, val)
         self._bound = None
         return val
@@ -220,9 +254,10 @@ class CountLayerStep:
                              "<= 8 edge code classes)" % (d_x, w_ids, w_ef))
         keys = not self._force_packs and keys_path_ok(x_codes.n_classes, x_codes.clamp)
         self.on_keys = keys
+        self.on_tables = keys and tables_path_ok(x_codes.n_classes, x_codes.clamp) and _tables_switch()
         self._dict = node_dictionary(x_codes.n_classes, x_codes.clamp, dev) if keys else None
         b = self._buffers(N, E, G, dev, keys)
-        ge, g0, g1, prep, _keep, d_out, flops = self._layer_structs(b, N, E, d_x, w_ids + w_ef)
+        ge, g0, g1, prep, _keep, d_out, flops, tabs = self._layer_structs(b, N, E, d_x, w_ids + w_ef)
         if ids_out is None:
             ids_out = torch.empty((E, self.plan.n_cols), dtype=torch.int64, device=dev)
         y = out if out is not None else torch.empty((N, d_out), dtype=torch.float32, device=dev)
@@ -262,10 +297,11 @@ class CountLayerStep:
         L = _abi.lib()
         if keys:
             kref, dptr, drows = ctypes.byref(self._keys), self._dict.data_ptr(), self._dict.shape[0]
-            entry = "gsn_count_layer_step_keys_hip"
+            entry = "gsn_count_layer_step_tabs_hip"
+            tptr = tabs.data_ptr() if tabs is not None else None
 
             def call(ev_between):
-                return L.gsn_count_layer_step_keys_hip(ctypes.byref(c), ctypes.byref(l), kref, dptr, drows, ev_between, _abi.current_stream())
+                return L.gsn_count_layer_step_tabs_hip(ctypes.byref(c), ctypes.byref(l), kref, dptr, drows, tptr, ev_between, _abi.current_stream())
         else:
             entry = "gsn_count_layer_step_hip"
 

@@ -597,6 +597,19 @@ int gsn_count_layer_step_hip(const gsn_count_call *count, const gsn_layer_pack16
 int gsn_layer_keys_byte_table(uint16_t *dst);
 int gsn_count_layer_step_keys_hip(const gsn_count_call *count, const gsn_layer_pack16_call *layer, const gsn_count_keys *keys,
                                   const uint16_t *node_dict, int64_t dict_rows, void *event_between, void *stream);
+/* The x_i tables of that step.  Chunks 0 and 1 of an edge row -- x_i, with the folded bias on column 31 -- are the dictionary row of the
+ * row's TARGET, and their products stand at the front of the edge stage's accumulation chain, so the accumulators behind them depend on
+ * that dictionary row alone.  gsn_layer_key_tables_hip runs those products (the layer kernel's own instruction sequence on the prepared
+ * fragments) once per dictionary row and writes fp32 tabs[4][gsn_layer_key_tables_max_rows()][32] (feature block, dictionary row, feature;
+ * gsn_layer_key_tables_words() words); gsn_count_layer_step_tabs_hip is gsn_count_layer_step_keys_hip whose layer starts every block's
+ * accumulators from the table row of the row's target and multiplies the remaining three chunks: 24 matrix instructions per block in place
+ * of 40, the same bits.  dict_rows <= gsn_layer_key_tables_max_rows() (31; GSN_E_UNSUPPORTED beyond); `tabs` belongs to one (prepared
+ * buffer, dictionary) pair and is made again when either changes; tabs == NULL is gsn_count_layer_step_keys_hip.  One tiny launch, capturable. */
+int64_t gsn_layer_key_tables_words(void);
+int64_t gsn_layer_key_tables_max_rows(void);
+int gsn_layer_key_tables_hip(const void *prepared, const uint16_t *node_dict, int64_t dict_rows, float *tabs, void *stream);
+int gsn_count_layer_step_tabs_hip(const gsn_count_call *count, const gsn_layer_pack16_call *layer, const gsn_count_keys *keys,
+                                  const uint16_t *node_dict, int64_t dict_rows, const float *tabs, void *event_between, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * HP-2  dense stage on DIRECT rows with fp16x3 matrix arithmetic (device): the same operation as gsn_linear_fwd_hip
