@@ -75,6 +75,12 @@ class gsn_dgn_agg(ctypes.Structure):
     _fields_ = [("kind", c_i32), ("col", c_i32), ("alpha", ctypes.c_float), ("slot", c_i32)]
 
 
+class gsn_loader_field(ctypes.Structure):
+    _fields_ = [("src", c_vp), ("row_ptr", c_vp), ("dst", c_vp), ("dst_rows", c_i64), ("row_bytes", c_i64), ("src_stride", c_i64),
+                ("dst_stride", c_i64), ("elem_bytes", c_i32), ("ptr_class", c_i32), ("kind", c_i32), ("inc_class", c_i32), ("flags", c_i32),
+                ("reserved", c_i32)]
+
+
 SIGNATURES = {
     "gsn_last_error": (ctypes.c_char_p, []),
     "gsn_propagate_last_route": (ctypes.c_char_p, []),
@@ -206,6 +212,7 @@ SIGNATURES = {
     "gsn_eval_accumulate_hip": (c_int, [c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "gsn_rank_metrics_scratch_bytes": (c_i64, [c_i64, c_i64]),
     "gsn_rank_metrics_hip": (c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "gsn_loader_collate_hip": (c_int, [c_int, ctypes.POINTER(gsn_loader_field), c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
 }
 
 

@@ -1076,6 +1076,52 @@ int64_t gsn_rank_metrics_scratch_bytes(int64_t m_rows, int64_t n_cols);
 int gsn_rank_metrics_hip(int64_t m_rows, int64_t n_cols, const float *y_pred, const float *y_true, int64_t *out_i64, double *out_f64,
                          int32_t *status, void *scratch, int64_t scratch_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * One collated batch of a device-resident dataset in ONE launch (gsn_amd/loader.py; the reference's `for data in loader` over
+ * torch_geometric's DataLoader, train_test_funcs.py:48-174).  The dataset lives on the device as one concatenation per attribute (a
+ * FIELD) with an int64 row pointer [G + 1] over its graphs; a batch is positions [first, first + batch) of an epoch's `order` (int64
+ * device [n_graphs_total]: the graph at every position).  `plan` (int64 device [n_classes][n_graphs_total]) holds, per pointer class c
+ * and position i, the rows of class c in front of position i INSIDE ITS OWN BATCH: the destination row of that graph's segment.
+ *   fields   host array of n_fields <= GSN_LOADER_MAX_FIELDS records; the table travels BY VALUE in the launch (no device copy of it):
+ *     src, row_ptr   the field's storage and its row pointer (device); graph g owns rows [row_ptr[g], row_ptr[g + 1])
+ *     dst, dst_rows  this batch's output and its row count (columns for GSN_LOADER_EDGE_INDEX); dst_rows == 0: nothing is read or
+ *                    written for the field (dst may be NULL)
+ *     row_bytes, elem_bytes   bytes of a row (a multiple of elem_bytes) and of the unit it is moved in (4 or 8; src and dst aligned to it)
+ *     ptr_class      the row of `plan` that holds the field's destination rows
+ *     kind           GSN_LOADER_COPY: rows copied unchanged.  GSN_LOADER_EDGE_INDEX: int64 [2, *] with graph-local vertex ids, source
+ *                    row stride src_stride and destination row stride dst_stride (elements); both rows are copied and
+ *                    plan[inc_class][position] -- the vertices in front of the graph in its batch -- is added to every value
+ *     flags          GSN_LOADER_F_NODES marks the field whose rows are the vertices (`x`): its wave also writes batch_vec[row] = slot
+ *                    for its rows, node_ptr_out[slot] and, for the last slot, node_ptr_out[batch]; the GSN_LOADER_EDGE_INDEX field
+ *                    does the same for edge_ptr_out.  Either output may be NULL (not written).
+ * One wave per (field, slot) pair, pairs handed out by a grid-stride loop; every output byte has exactly one writer: no atomics, no
+ * LDS, no dependency between workgroups.  A segment that would pass its destination (dst_rows) is not copied -- plan and row pointers
+ * come from the same host sizes, so this never happens with a loader's own tables.  All offsets are int64.
+ * batch == 0, or no field with rows and no pointer output: nothing is launched, GSN_OK.  More than GSN_LOADER_MAX_FIELDS fields, element
+ * bytes other than 4 / 8, a null pointer where rows are expected, or positions outside [0, n_graphs_total]: GSN_E_INVALID.  Asynchronous
+ * on `stream`, allocates nothing, can be captured into a HIP graph.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define GSN_LOADER_MAX_FIELDS 16
+enum { GSN_LOADER_COPY = 0, GSN_LOADER_EDGE_INDEX = 1 };
+#define GSN_LOADER_F_NODES 1
+typedef struct gsn_loader_field {
+    const void *src;
+    const int64_t *row_ptr;
+    void *dst;
+    int64_t dst_rows;
+    int64_t row_bytes;
+    int64_t src_stride, dst_stride;
+    int32_t elem_bytes;
+    int32_t ptr_class;
+    int32_t kind;
+    int32_t inc_class;
+    int32_t flags;
+    int32_t reserved;
+} gsn_loader_field;
+int gsn_loader_collate_hip(int n_fields, const gsn_loader_field *fields, const int64_t *order, const int64_t *plan,
+                           int64_t n_graphs_total, int64_t first, int64_t batch, int64_t *batch_vec, int64_t *node_ptr_out,
+                           int64_t *edge_ptr_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

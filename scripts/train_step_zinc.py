@@ -4,6 +4,7 @@ one-hot atom / bond / identifier encoders, cycle counts k<=6 (GSN-e, local), sum
 data parallel with one flat RCCL gradient all-reduce per step.  Forward and backward run on the HIP kernels.
 
     python scripts/train_step_zinc.py [--batch 128] [--steps 20]
+    python scripts/train_step_zinc.py --loader native          # eager steps over batches of a device-resident DataLoader (gsn_amd.loader)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 scripts/train_step_zinc.py"""
 import argparse
 import json
@@ -21,8 +22,31 @@ from gsn_amd import dist as gdist, encoding, models, synth  # noqa: E402
 from gsn_amd.counting import CountPlan, count_batch  # noqa: E402
 
 
+def native_loader(args, dev, rank, plan):
+    """``--loader native``: a prepared ZINC-shaped dataset of ``--loader-graphs`` graphs on the device and a shuffled DataLoader over it
+    (gsn_amd.loader: one HIP launch per batch).  -> (loader, d_id)"""
+    from gsn_amd.data import Data
+    from gsn_amd.loader import DataLoader, DeviceDataset
+    b = synth.zinc_shape_batch(max(args.loader_graphs, args.batch), seed=200 + rank)
+    ids, _ = count_batch(plan, b.node_ptr, b.edge_ptr, torch.from_numpy(b.edge_index), ids_are_global=True, device=dev)
+    codes, d_id = encoding.unique_codes(ids)
+    codes = codes.cpu()
+    rng = np.random.default_rng(rank)
+    graphs = []
+    for g in range(b.num_graphs):
+        n0, n1, e0, e1 = int(b.node_ptr[g]), int(b.node_ptr[g + 1]), int(b.edge_ptr[g]), int(b.edge_ptr[g + 1])
+        graphs.append(Data(edge_index=torch.from_numpy(b.edge_index[:, e0:e1] - n0), x=torch.from_numpy(b.atom_type[n0:n1]).unsqueeze(1),
+                           graph_size=n1 - n0, degrees=torch.zeros(n1 - n0), edge_features=torch.from_numpy(b.bond_type[e0:e1]).unsqueeze(1),
+                           y=torch.from_numpy(rng.standard_normal(1).astype(np.float32)), identifiers=codes[e0:e1].clone()))
+    gen = torch.Generator()
+    gen.manual_seed(rank)
+    return DataLoader(DeviceDataset(graphs, device=dev), batch_size=args.batch, shuffle=True, drop_last=True, generator=gen), d_id
+
+
 def build(args, dev, rank=0):
     """(model, data, params, optimizer, loss closure, N, E) of the step."""
+    if getattr(args, "loader", "static") == "native":
+        return build_native(args, dev, rank)
     b = synth.zinc_shape_batch(args.batch, seed=200 + rank)
     N, E = b.num_nodes, b.num_edges
     plan = CountPlan.get([list(nx.cycle_graph(k).edges) for k in range(3, 7)], "edge", False)
@@ -38,6 +62,34 @@ def build(args, dev, rank=0):
         # direction (gsn_csr_build_graphs_hip) instead of the generic build, the readout needs none (models._register_partition)
         data.graph_partition = (torch.from_numpy(b.node_ptr.astype(np.int64)).to(dev), torch.from_numpy(b.edge_ptr.astype(np.int64)).to(dev),
                                 int(np.diff(b.node_ptr).max()), int(np.diff(b.edge_ptr).max()), False)
+    model, params, opt = make_model(args, dev, d_id)
+    loss_fn = torch.nn.L1Loss()
+    return model, data, params, opt, (lambda: loss_fn(model(data), data.y)), N, E
+
+
+def build_native(args, dev, rank):
+    """The same model stepping over the batches of a DataLoader: every step draws the next batch (a new epoch when one runs out)."""
+    if getattr(args, "graph", False):
+        raise SystemExit("--loader native draws batches of varying shapes: they cannot be replayed as one HIP graph (drop --graph)")
+    plan = CountPlan.get([list(nx.cycle_graph(k).edges) for k in range(3, 7)], "edge", False)
+    loader, d_id = native_loader(args, dev, rank, plan)
+    model, params, opt = make_model(args, dev, d_id)
+    loss_fn = torch.nn.L1Loss()
+    state = {"it": iter(loader)}
+
+    def loss_of():
+        batch = next(state["it"], None)
+        if batch is None:
+            state["it"] = iter(loader)
+            batch = next(state["it"])
+        return loss_fn(model(batch), batch.y.view(-1, 1))
+
+    sizes = loader.dataset.host_sizes
+    per_batch = args.batch / max(len(loader.dataset), 1)
+    return model, None, params, opt, loss_of, int(sizes("x").sum() * per_batch), int(sizes("edge_index").sum() * per_batch)
+
+
+def make_model(args, dev, d_id):
     L, d = 4, 128
     act = getattr(args, "activation", "relu")      # (the tests of replay == eager use elu: no ReLU kink for last-bit noise to flip)
     kw = dict(seed=0, model_name="GSN_edge_sparse", readout="sum", dropout_features=[0.0] * (L + 1), bn=[True] * L,
@@ -57,8 +109,7 @@ def build(args, dev, rank=0):
         opt = optim.Adam(params, lr=1e-3)          # one HIP launch per step; a replay follows the schedulers (gsn_amd/optim.py)
     else:
         opt = torch.optim.SGD(params, lr=1e-3)
-    loss_fn = torch.nn.L1Loss()
-    return model, data, params, opt, (lambda: loss_fn(model(data), data.y)), N, E
+    return model, params, opt
 
 
 def run(args, dev, dist=None, rank=0, world=1):
@@ -93,10 +144,13 @@ def run(args, dev, dist=None, rank=0, world=1):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     n_params = sum(p.numel() for p in params)
-    return ({"workload": "ZINC-shaped GNNSubstructures training step (4 x GSN_edge_sparse general d=128), batch %d graphs/GPU (N=%d, E=%d)" % (args.batch, N, E),
+    res = ({"workload": "ZINC-shaped GNNSubstructures training step (4 x GSN_edge_sparse general d=128), batch %d graphs/GPU (N=%d, E=%d)" % (args.batch, N, E),
             "n_gpus": world, "graphs_per_s": round(world * args.batch * args.steps / dt, 1),
             "ms_per_step": round(dt / args.steps * 1e3, 3), "parameters": n_params, "loss": float(loss.item()),
             "launch": "hip_graph" if getattr(args, "graph", False) else "eager", "optimizer": getattr(args, "optimizer", "sgd")})
+    if getattr(args, "loader", "static") != "static":
+        res["loader"] = args.loader          # (N, E of the workload line: the dataset's mean per batch)
+    return res
 
 
 def main():
@@ -106,6 +160,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--graph", action="store_true", help="replay the whole step as one HIP graph (gsn_amd.graphs.GraphedTrainStep)")
     ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adam", "adam_native"])
+    ap.add_argument("--loader", default="static", choices=["static", "native"],
+                    help="static: one batch built by hand, every step on it; native: batches of a device-resident gsn_amd.loader.DataLoader")
+    ap.add_argument("--loader-graphs", type=int, default=1024, help="graphs of the dataset behind --loader native")
     args = ap.parse_args()
     rank, world, local = (int(os.environ.get(k, d)) for k, d in (("RANK", "0"), ("WORLD_SIZE", "1"), ("LOCAL_RANK", "0")))
     torch.cuda.set_device(local)
