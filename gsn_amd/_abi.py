@@ -213,6 +213,9 @@ SIGNATURES = {
     "gsn_rank_metrics_scratch_bytes": (c_i64, [c_i64, c_i64]),
     "gsn_rank_metrics_hip": (c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "gsn_loader_collate_hip": (c_int, [c_int, ctypes.POINTER(gsn_loader_field), c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "gsn_dropout_fwd_hip": (c_int, [c_i64, c_vp, c_vp, c_vp, ctypes.c_uint32, ctypes.c_float, c_vp, c_vp, c_vp, c_vp]),
+    "gsn_dropout_bwd_hip": (c_int, [c_i64, c_vp, c_vp, ctypes.c_uint32, ctypes.c_float, c_vp, c_vp]),
+    "gsn_dropout_chunk_elems": (c_i64, []),
 }
 
 

@@ -475,9 +475,12 @@ class DGNLayerSimple(nn.Module):
     """dgn_layer.py:10-82: aggregate (HIP) -> posttrans -> [* snorm_n] -> [BatchNorm] -> relu -> [+ h_in] -> dropout.
     ``aggregators`` / ``scalers``: lists of names (or space-separated strings) -- the keys of the reference's AGGREGATORS / SCALERS."""
 
-    def __init__(self, in_dim, out_dim, dropout, graph_norm, batch_norm, aggregators, scalers, residual, avg_d, posttrans_layers=1):
+    def __init__(self, in_dim, out_dim, dropout, graph_norm, batch_norm, aggregators, scalers, residual, avg_d, posttrans_layers=1,
+                 dropout_impl=None):
         super().__init__()
+        from .dropout import resolve_impl
         self.dropout = dropout
+        self.dropout_impl = resolve_impl(dropout_impl)      # "torch": F.dropout; "native": gsn_amd.dropout (None: flags.DROPOUT_NATIVE)
         self.graph_norm = graph_norm
         self.batch_norm = batch_norm
         self.residual = residual
@@ -503,6 +506,9 @@ class DGNLayerSimple(nn.Module):
             h = self.posttrans(agg, post=(self.batchnorm_h if self.batch_norm else None, "relu"))
         if self.residual:
             h = h_in + h
+        if self.dropout_impl == "native":
+            from .dropout import dropout as native_dropout
+            return native_dropout(h, self.dropout, self.training)
         return F.dropout(h, self.dropout, training=self.training)
 
 
@@ -510,7 +516,7 @@ class DGNLayer(nn.Module):
     """dgn_layer.py:85-109.  Only ``type_net='simple'`` names a class the reference defines; ``.model`` is the layer."""
 
     def __init__(self, in_dim, out_dim, dropout, graph_norm, batch_norm, aggregators, scalers, avg_d, type_net, residual, towers=5,
-                 divide_input=True, edge_features=None, edge_dim=None, pretrans_layers=1, posttrans_layers=1):
+                 divide_input=True, edge_features=None, edge_dim=None, pretrans_layers=1, posttrans_layers=1, dropout_impl=None):
         super().__init__()
         aggregators, scalers = aggregators.split(), scalers.split()
         parse_aggregators(aggregators)           # (KeyError on a name the reference does not know, as its dict lookups raise)
@@ -518,7 +524,7 @@ class DGNLayer(nn.Module):
         if type_net == "simple":
             self.model = DGNLayerSimple(in_dim=in_dim, out_dim=out_dim, dropout=dropout, graph_norm=graph_norm, batch_norm=batch_norm,
                                         residual=residual, aggregators=aggregators, scalers=scalers, avg_d=avg_d,
-                                        posttrans_layers=posttrans_layers)
+                                        posttrans_layers=posttrans_layers, dropout_impl=dropout_impl)
         else:
             raise NotImplementedError("DGNLayer type_net=%r: 'complex' and 'towers' name classes the reference never defines "
                                       "(dgn_layer.py:97-109)" % (type_net,))
@@ -572,14 +578,16 @@ class DGNNet(nn.Module):
         pretrans_layers = net_params["pretrans_layers"]
         posttrans_layers = net_params["posttrans_layers"]
         self.device = net_params.get("device")
-        self.in_feat_dropout = nn.Dropout(in_feat_dropout)
+        from .dropout import Dropout as NativeDropout, resolve_impl
+        self.dropout_impl = resolve_impl(net_params.get("dropout_impl"))      # "torch": nn.Dropout / F.dropout; "native": gsn_amd.dropout
+        self.in_feat_dropout = NativeDropout(in_feat_dropout) if self.dropout_impl == "native" else nn.Dropout(in_feat_dropout)
         self.embedding_h = AtomEncoder(emb_dim=hidden_dim)
         if self.edge_feat:
             self.embedding_e = BondEncoder(emb_dim=edge_dim)
         mk = lambda o: DGNLayer(in_dim=hidden_dim, out_dim=o, dropout=dropout, graph_norm=self.graph_norm, batch_norm=self.batch_norm,
                                 residual=self.residual, aggregators=self.aggregators, scalers=self.scalers, avg_d=self.avg_d,
                                 type_net=self.type_net, edge_features=self.edge_feat, edge_dim=edge_dim, pretrans_layers=pretrans_layers,
-                                posttrans_layers=posttrans_layers).model
+                                posttrans_layers=posttrans_layers, dropout_impl=self.dropout_impl).model
         self.layers = nn.ModuleList([mk(hidden_dim) for _ in range(n_layers - 1)])
         self.layers.append(mk(out_dim))
         self.MLP_layer = MLPReadout(out_dim, 1)

@@ -88,4 +88,9 @@ FUSE_EDGE_ENCODERS = os.environ.get("GSN_FUSE_EDGE_ENCODERS", "1") != "0"
 # relu-sum layers whose own term is their gathered block (the ogb layers): the self term's adjoint inside the node pass of the propagate adjoint
 FOLD_SELF_ADJOINT = os.environ.get("GSN_FOLD_SELF_ADJOINT", "1") != "0"
 
+# the models' dropout (GNN_OGB, GNNSubstructures, DGNLayerSimple, DGNNet) when they are built without an explicit ``dropout_impl``:
+# "native" -- gsn_amd.dropout: one HIP launch with the residual add, masks rebuilt in backward, the call counter on the device (a replayed HIP
+# graph draws what an eager step at that state would draw); anything else -- F.dropout as in the reference
+DROPOUT_NATIVE = os.environ.get("GSN_DROPOUT", "torch") == "native"
+
 CODE_STATUS_CHECK = True   # read the out-of-range flag back after every code-gather launch (one host sync)

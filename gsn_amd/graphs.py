@@ -62,7 +62,9 @@ class GraphedTrainStep:
 
     What stays correct across replays, and why:
       * BatchNorm running statistics and ``num_batches_tracked`` live on the device and are advanced by the captured kernels;
-      * dropout draws from PyTorch's generator, whose Philox offset the graph advances per replay (a replay is not a repeat);
+      * dropout draws from PyTorch's generator, whose Philox offset the graph advances per replay (a replay is not a repeat); native
+        dropout (gsn_amd.dropout) reads its call counter from device memory, so a replay draws the masks an eager step at the same state
+        would draw;
       * the parameters are updated in place by the captured optimizer kernels, which PyTorch's version counters do not see: the
         derived-weight caches of gsn_amd.layers are keyed on those counters, so every replay bumps them -- parameters and the BatchNorm
         buffers the captured kernels write (torch.autograd.graph.increment_version -- no launch) -- and an eager forward after a replay

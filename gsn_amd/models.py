@@ -15,6 +15,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import flags, layers
+from .dropout import dropout as native_dropout, resolve_impl
 from .encoding import DiscreteEmbedding
 from .layers import (Codes, GSN_edge_sparse, GSN_edge_sparse_ogb, GSN_sparse, MPNN_edge_sparse, MPNN_edge_sparse_ogb, MPNN_sparse,
                      add_by_graph, choose_activation, global_add_pool_sparse, global_mean_pool_sparse, mlp, run_linear_module)
@@ -114,6 +115,7 @@ class GNNSubstructures(nn.Module):
         self.model_name = kwargs["model_name"]
         self.readout = kwargs["readout"] if kwargs["readout"] is not None else "sum"
         self.dropout_features = kwargs["dropout_features"]
+        self.dropout_impl = resolve_impl(kwargs.get("dropout_impl"))      # "torch": F.dropout; "native": gsn_amd.dropout (flags.DROPOUT_NATIVE)
         self.bn = kwargs["bn"]
         self.final_projection = kwargs["final_projection"]
         self.inject_ids = kwargs["inject_ids"]
@@ -234,7 +236,13 @@ class GNNSubstructures(nn.Module):
                 x_global = self.global_pool(x_interm[i], data.batch)
                 jk = self.lin_proj[i]
                 y = jk(x_global) if isinstance(jk, mlp) else run_linear_module(jk, x_global)
-                prediction = prediction + F.dropout(y, p=self.dropout_features[i], training=self.training)
+                if self.dropout_impl == "native":
+                    # the jumping-knowledge sum rides in the dropout launch from the second term on (0 + y of the first term stays: -0 -> +0)
+                    first = not isinstance(prediction, torch.Tensor)
+                    y = native_dropout(y, self.dropout_features[i], self.training, None if first else prediction)
+                    prediction = prediction + y if first else y
+                else:
+                    prediction = prediction + F.dropout(y, p=self.dropout_features[i], training=self.training)
         if return_intermediate:
             if isinstance(x_interm[0], Codes):
                 x_interm[0] = x_interm[0].dense()           # (the encoder's rows, for whoever asks for them)
@@ -255,6 +263,7 @@ class GNN_OGB(nn.Module):
         self.model_name = kwargs["model_name"]
         self.readout = kwargs["readout"] if kwargs["readout"] is not None else "sum"
         self.dropout_features = kwargs["dropout_features"]
+        self.dropout_impl = resolve_impl(kwargs.get("dropout_impl"))      # "torch": F.dropout; "native": gsn_amd.dropout (flags.DROPOUT_NATIVE)
         self.bn = kwargs["bn"]
         self.final_projection = kwargs["final_projection"]
         self.residual = kwargs["residual"]
@@ -362,14 +371,23 @@ class GNN_OGB(nn.Module):
             # BatchNorm1d (+ activation on all but the last layer) fused into the layer's last stage (:241-246)
             x = self.conv[i](x_interm[i], edge_index, post_bn=self.batch_norms[i] if self.bn[i] else None,
                              post_act="identity" if last else self.activation_name, **kwargs)
-            x = F.dropout(x, self.dropout_features[i], training=self.training)
-            if self.residual:
-                x = x + x_interm[-1]
+            if self.dropout_impl == "native":
+                x = native_dropout(x, self.dropout_features[i], self.training, x_interm[-1] if self.residual else None)      # one launch with the residual
+            else:
+                x = F.dropout(x, self.dropout_features[i], training=self.training)
+                if self.residual:
+                    x = x + x_interm[-1]
             x_interm.append(x)
             if not last and self.vn:
                 vn_temp = self.global_vn_pool(x_interm[i], data.batch) + vn_embedding
                 # the activation after mlp_vn rides in its last stage unless the residual form needs the raw output
-                if self.residual:
+                if self.dropout_impl == "native":
+                    if self.residual:
+                        vn_embedding = self.mlp_vn[i](vn_temp)
+                        vn_embedding = native_dropout(self.activation(vn_embedding), self.dropout_features[i], self.training, vn_embedding)
+                    else:
+                        vn_embedding = native_dropout(self.mlp_vn[i](vn_temp, post=(None, self.activation_name)), self.dropout_features[i], self.training)
+                elif self.residual:
                     vn_embedding = self.mlp_vn[i](vn_temp)
                     vn_embedding = vn_embedding + F.dropout(self.activation(vn_embedding), self.dropout_features[i], training=self.training)
                 else:

@@ -1122,6 +1122,35 @@ int gsn_loader_collate_hip(int n_fields, const gsn_loader_field *fields, const i
                            int64_t n_graphs_total, int64_t first, int64_t batch, int64_t *batch_vec, int64_t *node_ptr_out,
                            int64_t *edge_ptr_out, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Dropout with the residual add in ONE launch, and its adjoint, without a mask tensor (models_graph_classification_ogb_original.py:243-245:
+ * x = F.dropout(x, p, training) followed by x += x_interm[-1] at :247-248; :257-259: the virtual node's vn + F.dropout(act(vn));
+ * models_graph_classification.py:240: prediction += F.dropout(lin_proj(x_global)); directional_gsn/nets/dgn_layer.py:81: h = F.dropout(h);
+ * dgn_net.py:58: in_feat_dropout).
+ * The mask is drawn from Philox4x32-10 (multipliers D2511F53, CD9E8D57; Weyl constants 9E3779B9, BB67AE85).  For element e of the tensor
+ * -- counted from its first element, never from an address -- of a call with state (seed, calls), both 64 bits:
+ *   group q = e >> 2; counter = (lo32 q, hi32 q, lo32 calls, hi32 calls); key = (lo32 seed, hi32 seed); r = output word e & 3;
+ *   KEEP iff r >= thr, with thr = min(2^32 - 1, round(p 2^32)) and scale = float32(1 / (1 - p)) from the caller.
+ * Forward:  v = keep ? x * scale : +0 (a select: a NaN or Inf in a dropped element does not propagate); out = v, or res + v when res is
+ *           not NULL -- product and sum rounded separately, never one fused multiply-add: bit for bit res + mask * x * scale in fp32.
+ * Backward: grad_x = keep ? grad_out * scale : +0 from the (seed, calls) the forward left in `used`.  The residual's gradient is grad_out.
+ *   n         elements of x, res, out (grad_out, grad_x); fp32, contiguous, 4-byte aligned.  When every tensor of the call is 16-byte aligned
+ *             the groups move as 16 bytes, else as four words of the SAME group: the mask does not depend on alignment, grid or shape.
+ *   state     int64 device [2]: seed, calls.  Read by every workgroup in front of its elements; the workgroup that finishes last writes
+ *             calls + 1 -- no second launch, no host-side counter: a replayed HIP graph draws what an eager call at that state would draw.
+ *   done      uint32 device, zero before the first call; the launch leaves it zero.  One state = one word; calls that share it must be
+ *             ordered (one stream, or one graph).
+ *   used      int64 device [2], written by the forward: the (seed, calls) of this call.  The backward reads it and never touches `state`.
+ * A workgroup takes GSN_DROPOUT_CHUNK_ELEMS consecutive elements, a lane one Philox call per group of four; more than (2^31 - 1) chunks:
+ * GSN_E_UNSUPPORTED.  n == 0 launches nothing, leaves the state as it is and returns GSN_OK.  Asynchronous on `stream`, allocates nothing,
+ * can be captured into a HIP graph.  gsn_dropout_chunk_elems() returns GSN_DROPOUT_CHUNK_ELEMS of the built library.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define GSN_DROPOUT_CHUNK_ELEMS 8192
+int gsn_dropout_fwd_hip(int64_t n, const float *x, const float *res /* may be NULL */, float *out, uint32_t thr, float scale,
+                        int64_t *state /* [2]: seed, calls */, unsigned *done, int64_t *used /* [2], written */, void *stream);
+int gsn_dropout_bwd_hip(int64_t n, const float *grad_out, float *grad_x, uint32_t thr, float scale, const int64_t *used, void *stream);
+int64_t gsn_dropout_chunk_elems(void);
+
 #ifdef __cplusplus
 }
 #endif

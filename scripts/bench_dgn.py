@@ -77,7 +77,15 @@ def emit(**kw):
     print(json.dumps(kw), flush=True)
 
 
-def bench(G, window, only_step, optimizer="adam"):
+def make_net(dropout_impl=None, dropout=0.3, in_feat_dropout=0.0):
+    """The DGNNet of the HIV config (4 layers, d = 70); ``dropout_impl``: "torch", "native" (gsn_amd.dropout) or None (GSN_DROPOUT)."""
+    return dgn.DGNNet(dict(L=4, hidden_dim=70, out_dim=70, type_net="simple", residual=True, edge_feat=False, readout="mean",
+                           in_feat_dropout=in_feat_dropout, dropout=dropout, graph_norm=False, batch_norm=True, aggregators=AGGS, scalers="identity",
+                           towers=5, divide_input_first=False, divide_input_last=True, edge_dim=0, pretrans_layers=1, posttrans_layers=1,
+                           pos_enc_dim=0, avg_d={"log": 1.0}, device="cuda", dropout_impl=dropout_impl)).cuda().train()
+
+
+def bench(G, window, only_step, optimizer="adam", dropout_impl=None):
     b, ef_np, codes_np = batch(G)
     g = dgn.DGNGraph.from_batch(b, edge_field=ef_np)
     N, E, d, A = b.num_nodes, b.num_edges, 70, 5
@@ -124,16 +132,13 @@ def bench(G, window, only_step, optimizer="adam"):
         t = timed(layer_step_composed, window)
         emit(what="layer_train_step", native=False, us=t * 1e6, **common)
     # the DGNNet train step: forward, BCE loss, backward, Adam
-    net = dgn.DGNNet(dict(L=4, hidden_dim=70, out_dim=70, type_net="simple", residual=True, edge_feat=False, readout="mean",
-                          in_feat_dropout=0.0, dropout=0.3, graph_norm=False, batch_norm=True, aggregators=AGGS, scalers="identity",
-                          towers=5, divide_input_first=False, divide_input_last=True, edge_dim=0, pretrans_layers=1, posttrans_layers=1,
-                          pos_enc_dim=0, avg_d={"log": 1.0}, device="cuda")).cuda().train()
+    net = make_net(dropout_impl)
     if optimizer == "adam_native":
         from gsn_amd import optim
         opt = optim.Adam(net.parameters(), lr=0.01, weight_decay=3e-6)
     else:
         opt = torch.optim.Adam(net.parameters(), lr=0.01, weight_decay=3e-6, capturable=True)
-    common = dict(common, optimizer=optimizer)
+    common = dict(common, optimizer=optimizer, dropout=net.dropout_impl)
     codes = torch.from_numpy(codes_np).cuda()
     labels = torch.from_numpy((np.arange(G) % 2).astype(np.float32)).cuda()
 
@@ -157,10 +162,12 @@ def main():
     ap.add_argument("--window", type=float, default=1.0)
     ap.add_argument("--only-step", action="store_true")
     ap.add_argument("--optimizer", default="adam", choices=["adam", "adam_native"], help="adam_native: gsn_amd.optim.Adam, one HIP launch per step")
+    ap.add_argument("--dropout", default=None, choices=["torch", "native"],
+                    help="native: gsn_amd.dropout in the net's layers, one HIP launch per call (default: GSN_DROPOUT, else torch)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_dgn.py measures on the GPU; there is no CPU fallback"
     for G in [int(x) for x in a.graphs.split(",")]:
-        bench(G, a.window, a.only_step, a.optimizer)
+        bench(G, a.window, a.only_step, a.optimizer, a.dropout)
         layers.drop_input_caches()
 
 

@@ -60,6 +60,9 @@ def main():
                     help="masked: gsn_amd.evaluation.MaskedLoss over labels of which --nan-share are NaN (one capturable node); "
                          "masked_reference: the reference's loss_fn(y_hat[is_labeled], y[is_labeled]) on the same labels (eager only)")
     ap.add_argument("--nan-share", type=float, default=0.2)
+    ap.add_argument("--dropout", default=None, choices=["torch", "native"],
+                    help="native: gsn_amd.dropout -- one HIP launch with the residual add, the call counter on the device (default: GSN_DROPOUT, else torch)")
+    ap.add_argument("--residual", action="store_true", help="the model's residual connections (README.md:121 runs without)")
     args = ap.parse_args()
     rank, world, local = (int(os.environ.get(k, d)) for k, d in (("RANK", "0"), ("WORLD_SIZE", "1"), ("LOCAL_RANK", "0")))
     torch.cuda.set_device(local)
@@ -82,7 +85,8 @@ def build(args, dev, rank=0, dropout=0.5):
     L, dm = args.layers, args.d
     act = getattr(args, "activation", "relu")      # (the tests of replay == eager use elu in the MLPs; the ogb message keeps its relu)
     kw = dict(seed=0, model_name="GSN_edge_sparse_ogb", readout="mean", dropout_features=[dropout] * (L + 1), bn=[True] * L,
-              final_projection=[False] * L + [True], residual=False, inject_ids=True, vn=True, id_scope="local",
+              final_projection=[False] * L + [True], residual=bool(getattr(args, "residual", False)), inject_ids=True, vn=True, id_scope="local",
+              dropout_impl=getattr(args, "dropout", None),
               d_msg=[dm] * L, d_out=[dm] * L, d_h=[[2 * dm]] * L, aggr="add", flow="source_to_target", msg_kind="ogb",
               train_eps=[True] * L, activation_mlp=act, bn_mlp=True, jk_mlp=False, degree_embedding="None",
               degree_as_tag=[False] * L, retain_features=[True] * L, multi_embedding_aggr="sum", features_scope="full",
@@ -161,7 +165,7 @@ def run(args, dev, dist=None, rank=0, world=1):
             "ms_per_step": round(dt / args.steps * 1e3, 3), "parameters": n_params,
             "grad_bucket_MB": round(n_params * 4 / 1e6, 2), "loss": float(loss.item()),
             "launch": "hip_graph" if getattr(args, "graph", False) else "eager", "optimizer": getattr(args, "optimizer", "sgd"),
-            "loss_fn": getattr(args, "loss", "bce"),
+            "loss_fn": getattr(args, "loss", "bce"), "dropout": model.dropout_impl,
             "note": "forward and backward on HIP kernels (native adjoints of every stage, DESIGN.md 4); SGD update and glue in PyTorch"}
 
 

@@ -92,8 +92,10 @@ def build_native(args, dev, rank):
 def make_model(args, dev, d_id):
     L, d = 4, 128
     act = getattr(args, "activation", "relu")      # (the tests of replay == eager use elu: no ReLU kink for last-bit noise to flip)
-    kw = dict(seed=0, model_name="GSN_edge_sparse", readout="sum", dropout_features=[0.0] * (L + 1), bn=[True] * L,
-              final_projection=[False] * L + [True], inject_ids=False, inject_edge_features=True, random_features=False,
+    p_drop = float(getattr(args, "dropout_p", 0.0))      # (README.md:112 trains without dropout)
+    kw = dict(seed=0, model_name="GSN_edge_sparse", readout="sum", dropout_features=[p_drop] * (L + 1), bn=[True] * L,
+              dropout_impl=getattr(args, "dropout", None),
+              final_projection=list(getattr(args, "final_projection", None) or [False] * L + [True]), inject_ids=False, inject_edge_features=True, random_features=False,
               id_scope="local", d_msg=[d] * L, d_out=[d] * L, d_h=[[d]] * L, aggr="add", flow="source_to_target",
               msg_kind="general", train_eps=[False] * L, activation_mlp=act, bn_mlp=True, jk_mlp=True, degree_embedding="None",
               degree_as_tag=[False] * L, retain_features=[True] * L, multi_embedding_aggr="sum", input_node_encoder="one_hot_encoder",
@@ -163,6 +165,9 @@ def main():
     ap.add_argument("--loader", default="static", choices=["static", "native"],
                     help="static: one batch built by hand, every step on it; native: batches of a device-resident gsn_amd.loader.DataLoader")
     ap.add_argument("--loader-graphs", type=int, default=1024, help="graphs of the dataset behind --loader native")
+    ap.add_argument("--dropout", default=None, choices=["torch", "native"],
+                    help="native: gsn_amd.dropout on the jumping-knowledge projections (default: GSN_DROPOUT, else torch)")
+    ap.add_argument("--dropout-p", type=float, default=0.0, help="dropout probability of the projections (the reference's run uses none)")
     args = ap.parse_args()
     rank, world, local = (int(os.environ.get(k, d)) for k, d in (("RANK", "0"), ("WORLD_SIZE", "1"), ("LOCAL_RANK", "0")))
     torch.cuda.set_device(local)
