@@ -81,6 +81,11 @@ class gsn_loader_field(ctypes.Structure):
                 ("reserved", c_i32)]
 
 
+class gsn_loader_pad(ctypes.Structure):
+    _fields_ = [("n_real", c_i64), ("graph_slots", c_i64), ("n_real_nodes", c_i64), ("n_real_edges", c_i64), ("node_capacity", c_i64),
+                ("edge_capacity", c_i64), ("n_chunk", c_i64), ("e_chunk", c_i64)]
+
+
 SIGNATURES = {
     "gsn_last_error": (ctypes.c_char_p, []),
     "gsn_propagate_last_route": (ctypes.c_char_p, []),
@@ -210,9 +215,12 @@ SIGNATURES = {
     "gsn_masked_loss_bwd_hip": (c_int, [c_int, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "gsn_eval_accumulate_scratch_bytes": (c_i64, [c_int, c_i64, c_i64]),
     "gsn_eval_accumulate_hip": (c_int, [c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "gsn_eval_accumulate_counted_hip": (c_int, [c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "gsn_rank_metrics_scratch_bytes": (c_i64, [c_i64, c_i64]),
     "gsn_rank_metrics_hip": (c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "gsn_loader_collate_hip": (c_int, [c_int, ctypes.POINTER(gsn_loader_field), c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "gsn_loader_collate_padded_hip": (c_int, [c_int, ctypes.POINTER(gsn_loader_field), ctypes.POINTER(ctypes.c_uint64), c_vp, c_vp, c_i64, c_i64,
+                                              ctypes.POINTER(gsn_loader_pad), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "gsn_dropout_fwd_hip": (c_int, [c_i64, c_vp, c_vp, c_vp, ctypes.c_uint32, ctypes.c_float, c_vp, c_vp, c_vp, c_vp]),
     "gsn_dropout_bwd_hip": (c_int, [c_i64, c_vp, c_vp, ctypes.c_uint32, ctypes.c_float, c_vp, c_vp]),
     "gsn_dropout_chunk_elems": (c_i64, []),

@@ -85,7 +85,17 @@ struct EvAcc {
     void *true_buf;
     int64_t capacity, y_words;      // y_words: 4-byte words of one row of y
     float *loss_out;
+    const int64_t *n_valid;         // COUNTED kernels only: the batch's valid rows, read on the device
 };
+
+// COUNTED: the first v = clamp(*n_valid, 0, rows) rows are the batch, and its weight.  False when there is none (uniform: nothing is done).
+__device__ __forceinline__ bool ev_count_rows(EvArgs &a, EvAcc &c) {
+    int64_t v = *c.n_valid;
+    v = v < 0 ? 0 : (v > a.rows ? a.rows : v);
+    a.rows = v;
+    c.num_graphs = v;
+    return v > 0;
+}
 
 __device__ __forceinline__ bool ev_overflow(const EvAcc &c, int64_t rows) {
     const int64_t cur = c.i64[GSN_EVAL_CURSOR];
@@ -122,10 +132,11 @@ __device__ __forceinline__ void ev_finish(const EvArgs &a, const EvPart &t, floa
     }
 }
 
-template <bool ACC>
+template <bool ACC, bool COUNTED = false>
 __global__ __launch_bounds__(256) void ev_small_kernel(EvArgs a, float *loss, int64_t *count, EvAcc c) {
     __shared__ double dbuf[4];
     __shared__ int64_t ibuf[4];
+    if (COUNTED && !ev_count_rows(a, c)) return;
     if (ACC) {
         if (ev_overflow(c, a.rows)) {      // (uniform: nobody has written the cursor yet)
             if (threadIdx.x == 0) c.i64[GSN_EVAL_STATUS] |= GSN_EVAL_OVERFLOW;
@@ -140,10 +151,14 @@ __global__ __launch_bounds__(256) void ev_small_kernel(EvArgs a, float *loss, in
     if (threadIdx.x == 0) ev_finish(a, t, loss, count, ACC ? &c : nullptr);
 }
 
-template <bool ACC>
+template <bool ACC, bool COUNTED = false>
 __global__ __launch_bounds__(256) void ev_partial_kernel(EvArgs a, EvPart *parts, int64_t n_chunks, EvAcc c) {
     __shared__ double dbuf[4];
     __shared__ int64_t ibuf[4];
+    if (COUNTED) {
+        if (!ev_count_rows(a, c)) return;
+        n_chunks = (ev_units(a) + EV_CHUNK - 1) / EV_CHUNK;      // (the chunks of the valid rows: the host sized the scratch for all rows)
+    }
     if (ACC) {
         if (ev_overflow(c, a.rows)) return;      // (the combine launch sets the flag; the cursor is only written there)
         ev_append(a, c, (int64_t)blockIdx.x * 256 + threadIdx.x, (int64_t)gridDim.x * 256);
@@ -154,9 +169,13 @@ __global__ __launch_bounds__(256) void ev_partial_kernel(EvArgs a, EvPart *parts
     }
 }
 
-template <bool ACC>
+template <bool ACC, bool COUNTED = false>
 __global__ __launch_bounds__(64) void ev_combine_kernel(EvArgs a, const EvPart *parts, int64_t n_chunks, float *loss, int64_t *count, EvAcc c) {
     if (threadIdx.x != 0) return;
+    if (COUNTED) {
+        if (!ev_count_rows(a, c)) return;
+        n_chunks = (ev_units(a) + EV_CHUNK - 1) / EV_CHUNK;
+    }
     if (ACC && ev_overflow(c, a.rows)) {
         c.i64[GSN_EVAL_STATUS] |= GSN_EVAL_OVERFLOW;
         return;
@@ -299,17 +318,17 @@ static int ev_check(const char *who, int kind, int64_t rows, int64_t cols, const
     return GSN_OK;
 }
 
-template <bool ACC>
+template <bool ACC, bool COUNTED = false>
 static int ev_launch(const EvArgs &a, float *loss, int64_t *count, const EvAcc &c, void *scratch, void *stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (a.rows * a.cols <= EV_ONE_LAUNCH_ELEMS) {
-        hipLaunchKernelGGL(ev_small_kernel<ACC>, dim3(1), dim3(256), 0, s, a, loss, count, c);
+        hipLaunchKernelGGL((ev_small_kernel<ACC, COUNTED>), dim3(1), dim3(256), 0, s, a, loss, count, c);
         return launch_check("ev_small_kernel");
     }
     const int64_t n_chunks = ev_chunks(a.kind, a.rows, a.cols);
     EvPart *parts = reinterpret_cast<EvPart *>(scratch);
-    hipLaunchKernelGGL(ev_partial_kernel<ACC>, dim3(us_grid(n_chunks)), dim3(256), 0, s, a, parts, n_chunks, c);
-    hipLaunchKernelGGL(ev_combine_kernel<ACC>, dim3(1), dim3(64), 0, s, a, parts, n_chunks, loss, count, c);
+    hipLaunchKernelGGL((ev_partial_kernel<ACC, COUNTED>), dim3(us_grid(n_chunks)), dim3(256), 0, s, a, parts, n_chunks, c);
+    hipLaunchKernelGGL((ev_combine_kernel<ACC, COUNTED>), dim3(1), dim3(64), 0, s, a, parts, n_chunks, loss, count, c);
     return launch_check("ev_partial_kernel / ev_combine_kernel");
 }
 
@@ -344,10 +363,9 @@ extern "C" int gsn_masked_loss_bwd_hip(int kind, int64_t rows, int64_t cols, con
     return launch_check("ev_bwd_kernel");
 }
 
-extern "C" int gsn_eval_accumulate_hip(int kind, int metric, int64_t rows, int64_t cols, int64_t y_cols, const float *y_hat, const void *y,
+static int ev_accumulate(const char *who, const int64_t *n_valid, int kind, int metric, int64_t rows, int64_t cols, int64_t y_cols, const float *y_hat, const void *y,
                                        int64_t num_graphs, double *acc_f64, int64_t *acc_i64, float *pred_buf, void *true_buf,
                                        int64_t capacity, float *loss_out, void *scratch, int64_t scratch_bytes, void *stream) {
-    const char *who = "gsn_eval_accumulate_hip";
     const int rc = ev_check(who, kind, rows, cols, y_hat, y, true, scratch, scratch_bytes);
     if (rc != GSN_OK) return rc;
     if (metric < GSN_METRIC_NONE || metric > GSN_METRIC_ACCURACY) return set_error(GSN_E_INVALID, "%s: unknown metric %d", who, metric);
@@ -359,8 +377,23 @@ extern "C" int gsn_eval_accumulate_hip(int kind, int metric, int64_t rows, int64
         return set_error(GSN_E_INVALID, "%s: %lld target columns for %lld x %lld predictions", who, (long long)y_cols, (long long)rows, (long long)cols);
     if (!acc_f64 || !acc_i64) return set_error(GSN_E_INVALID, "%s: null accumulator pointer", who);
     EvArgs a{kind, metric, rows, cols, y_hat, y};
-    EvAcc c{num_graphs, acc_f64, acc_i64, pred_buf, true_buf, capacity, kind == GSN_LOSS_CE ? 2 : y_cols, loss_out};
-    return ev_launch<true>(a, nullptr, nullptr, c, scratch, stream);
+    EvAcc c{num_graphs, acc_f64, acc_i64, pred_buf, true_buf, capacity, kind == GSN_LOSS_CE ? 2 : y_cols, loss_out, n_valid};
+    return n_valid ? ev_launch<true, true>(a, nullptr, nullptr, c, scratch, stream) : ev_launch<true>(a, nullptr, nullptr, c, scratch, stream);
+}
+
+extern "C" int gsn_eval_accumulate_hip(int kind, int metric, int64_t rows, int64_t cols, int64_t y_cols, const float *y_hat, const void *y,
+                                       int64_t num_graphs, double *acc_f64, int64_t *acc_i64, float *pred_buf, void *true_buf,
+                                       int64_t capacity, float *loss_out, void *scratch, int64_t scratch_bytes, void *stream) {
+    return ev_accumulate("gsn_eval_accumulate_hip", nullptr, kind, metric, rows, cols, y_cols, y_hat, y, num_graphs, acc_f64, acc_i64, pred_buf, true_buf,
+                         capacity, loss_out, scratch, scratch_bytes, stream);
+}
+
+extern "C" int gsn_eval_accumulate_counted_hip(int kind, int metric, int64_t rows, int64_t cols, int64_t y_cols, const float *y_hat, const void *y,
+                                               const int64_t *n_valid, double *acc_f64, int64_t *acc_i64, float *pred_buf, void *true_buf,
+                                               int64_t capacity, float *loss_out, void *scratch, int64_t scratch_bytes, void *stream) {
+    if (!n_valid) return set_error(GSN_E_INVALID, "gsn_eval_accumulate_counted_hip: null n_valid");
+    return ev_accumulate("gsn_eval_accumulate_counted_hip", n_valid, kind, metric, rows, cols, y_cols, y_hat, y, 0, acc_f64, acc_i64, pred_buf, true_buf,
+                         capacity, loss_out, scratch, scratch_bytes, stream);
 }
 
 static int64_t ev_rank_keys_bytes(int64_t m, int64_t c) { return (8 * m * c + 255) / 256 * 256; }

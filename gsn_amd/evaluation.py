@@ -8,6 +8,9 @@
 * ``Evaluator`` -- ``rocauc`` / ``ap`` / ``acc`` with ogb's ``Evaluator`` interface, ROC-AUC and average precision from the exact integer
   rank statistics of ``gsn_rank_metrics_hip`` (no ogb, no sklearn).
 * ``test`` / ``test_ogb`` -- the reference's evaluation loops (train_test_funcs.py:177-259), same signatures and return values.
+* ``GraphedEpoch`` -- the same loops over a ``loader.PaddedDataLoader``: the eval forward and the batch's accumulation captured ONCE into
+  a HIP graph over the loader's static batch, then one collate launch and one replay per batch.  ``test`` / ``test_ogb`` use it when they
+  are handed such a loader.
 
 There is no fallback: a loss or metric object this module cannot name raises ``TypeError``; without a GPU the entries raise.
 Out of scope: the ``train()`` loop, checkpointing, wandb, ``test_isomorphism`` (already one ``pdist`` and one host read).
@@ -225,7 +228,10 @@ class EpochAccumulator:
     def reset(self):
         self._state.zero_()
 
-    def add(self, y_hat, y, num_graphs=None):
+    def add(self, y_hat, y, num_graphs=None, n_valid=None):
+        """One batch.  ``n_valid`` (int64 device tensor of one element): only the first ``clamp(n_valid, 0, rows)`` rows are the batch --
+        loss, metric, appended rows, cursor and weight are those of ``add(y_hat[:v], y[:v], v)``, with v read on the device
+        (``gsn_eval_accumulate_counted_hip``): the rest of a padded batch is never looked at.  ``num_graphs`` is then not used."""
         _abi.require_gpu()
         y_hat, y, rows, cols = _operands(self.loss, y_hat, y)
         if self.keep_rows and (cols != self.n_pred_cols or (self.kind != 3 and cols != self.n_target_cols)):
@@ -233,6 +239,16 @@ class EpochAccumulator:
         L = _abi.lib()
         nb = L.gsn_eval_accumulate_scratch_bytes(self.kind, rows, cols)
         ws = _scratch(nb, self.device)
+        if n_valid is not None:
+            if not isinstance(n_valid, torch.Tensor) or n_valid.dtype != torch.int64 or n_valid.numel() != 1 or n_valid.device != y_hat.device:
+                raise TypeError("EpochAccumulator.add: n_valid is an int64 tensor of one element on the device of y_hat")
+            with _abi.device_guard(self.device):
+                _abi.check(L.gsn_eval_accumulate_counted_hip(self.kind, self.metric_kind, rows, cols, 1 if self.kind == 3 else cols, y_hat.data_ptr(),
+                                                             y.data_ptr(), n_valid.data_ptr(), self._f64.data_ptr(), self._i64.data_ptr(),
+                                                             _abi.ptr(self.y_pred), _abi.ptr(self.y_true),
+                                                             self.capacity if self.keep_rows else _NO_CAPACITY, self.last_loss.data_ptr(), _abi.ptr(ws), nb,
+                                                             _abi.current_stream()), "gsn_eval_accumulate_counted_hip")
+            return
         with _abi.device_guard(self.device):
             _abi.check(L.gsn_eval_accumulate_hip(self.kind, self.metric_kind, rows, cols, 1 if self.kind == 3 else cols, y_hat.data_ptr(), y.data_ptr(),
                                                  rows if num_graphs is None else int(num_graphs), self._f64.data_ptr(), self._i64.data_ptr(),
@@ -337,10 +353,141 @@ def _batches(loader, n_iters):
         yield data
 
 
+class GraphedEpoch:
+    """An evaluation epoch of ``model`` over a ``loader.PaddedDataLoader`` as one collate launch plus ONE graph replay per batch.
+
+    ``run(n_iters=None)`` returns what ``test(loader, model, loss_fn, device, prediction_fn, n_iters)`` returns -- or, with an
+    ``evaluator``, what ``test_ogb(loader, model, loss_fn, device, evaluator, n_iters)`` returns: the same weighting (a batch weighs its
+    REAL graphs: the accumulation reads the loader's device-side ``n_valid``), the same single host read at the end, and no branch on
+    anything read back from the device.
+
+    On the first padded batch ``model(static_batch)`` followed by ``acc.add(pred, y, n_valid=...)`` is captured through
+    ``graphs.GraphedStep`` (``captures`` counts: once per object).  ``layers.invalidate_caches(model)`` runs in front of the captured
+    forward, so every derived tensor -- folded weights, eval-mode BatchNorm vectors, transposes, fp16 planes -- is made INSIDE the graph
+    from the live parameters and lives in its pool: a replay after optimizer steps, ``load_state_dict`` or anybody's
+    ``invalidate_caches`` computes with the parameters as they are then, without version tracking or re-capture.  The price is that every
+    replay remakes them.  A batch that did not fit the loader's capacities (an ordinary ``Batch``) runs eagerly into the same accumulator;
+    under ``test_ogb``'s rule a batch of one vertex is skipped.  Both are decided from host numbers.  A model in training mode is refused."""
+
+    def __init__(self, model, loader, loss_fn, prediction_fn=None, evaluator=None):
+        from .loader import PaddedDataLoader
+        if not isinstance(loader, PaddedDataLoader):
+            raise TypeError("GraphedEpoch: a loader.PaddedDataLoader (batches of fixed shape in static tensors), not %s" % type(loader).__name__)
+        if evaluator is not None and prediction_fn is not None:
+            raise ValueError("GraphedEpoch: prediction_fn (the loop of test) or evaluator (the loop of test_ogb), not both")
+        self.model, self.loader, self.evaluator = model, loader, evaluator
+        self.loss, self.metric = _loss_name(loss_fn), _metric_name(prediction_fn)
+        self.ppa = evaluator is not None and evaluator.name == "ogbg-ppa"
+        self.acc = self.step = None
+        self.captures = self.replays = self.eager_batches = 0
+
+    def _target(self, batch, pred):
+        if self.evaluator is None:
+            return batch.y
+        return batch.y.view(-1) if self.ppa else batch.y.view(pred.shape)
+
+    def _make_acc(self, pred):
+        cols = pred.shape[-1] if pred.dim() >= 2 else 1
+        if self.evaluator is None:
+            self.acc = EpochAccumulator(0, cols, 1, self.loss, self.metric, device=pred.device, keep_rows=False)
+        else:      # one pass over the dataset at a time: run() moves the rows out when the loader wraps round
+            self.acc = EpochAccumulator(max(len(self.loader.dataset), self.loader.batch_size), pred.shape[1], pred.shape[1], self.loss, None,
+                                        device=pred.device)
+
+    def _forward(self, batch):
+        from . import layers
+        layers.invalidate_caches(self.model)          # (host only: the forward below derives everything from the live parameters)
+        pred = self.model(batch)
+        if self.acc is None:
+            self._make_acc(pred)
+        self.acc.add(pred, self._target(batch, pred), n_valid=batch.n_valid)
+        return pred
+
+    def _capture(self, batch):
+        from . import flags, layers
+        from .graphs import GraphedStep
+        layers.invalidate_caches(self.model)
+        pred = self.model(batch)                      # (eager, with every status check: the first batch's codes are looked at)
+        if self.acc is None:
+            self._make_acc(pred)
+        keep = self.acc._state.clone()                # the warm-up runs are real runs: their sums and rows do not count
+        # nothing can be read back inside a capture: the out-of-range flag of the code-gather stages is not looked at under replay (an
+        # out-of-range code gives a zero block, as the dense encoder); the eager runs above and below this line do look
+        check, flags.CODE_STATUS_CHECK = flags.CODE_STATUS_CHECK, False
+        try:
+            self.step = GraphedStep(lambda: self._forward(batch), warmup=1, device=self.acc.device)
+        finally:
+            flags.CODE_STATUS_CHECK = check
+        self.acc._state.copy_(keep)
+        self.captures += 1
+
+    def run(self, n_iters=None):
+        if self.model.training:
+            raise RuntimeError("GraphedEpoch: the model is in training mode (padded batches are for model.eval(): their pad rows would enter the "
+                               "BatchNorm statistics)")
+        ogb = self.evaluator is not None
+        held, chunks = 0, []                          # rows behind the accumulator's cursor, counted on the host; rows moved out of it
+        if self.acc is not None:
+            self.acc.reset()
+        with torch.no_grad():
+            for batch in _batches(self.loader, n_iters):
+                padded = getattr(batch, "padded", False)
+                b = batch.num_real_graphs if padded else batch.num_graphs
+                if ogb and (batch.num_real_nodes if padded else batch.x.shape[0]) == 1:
+                    continue
+                if ogb and self.acc is not None and held + b > self.acc.capacity:
+                    chunks.append((self.acc.y_pred[:held].clone(), self.acc.y_true[:held].clone()))
+                    self.acc._i64[0:1].zero_()
+                    held = 0
+                if padded:
+                    if self.step is None:
+                        self._capture(batch)
+                    self.step()
+                    self.replays += 1
+                else:
+                    pred = self.model(batch)
+                    if self.acc is None:
+                        self._make_acc(pred)
+                    self.acc.add(pred, self._target(batch, pred), batch.num_graphs)
+                    self.eager_batches += 1
+                held += b
+        n = len(self.loader.dataset)
+        if self.acc is None:
+            if ogb:
+                raise RuntimeError("test_ogb: no batch to evaluate")
+            return 0 / n, 0 / n
+        r = self.acc.result()
+        if not ogb:
+            return r.weighted_loss_sum / n, r.metric_sum / n
+        y_pred = torch.cat([c[0] for c in chunks] + [r.y_pred]) if chunks else r.y_pred
+        y_true = torch.cat([c[1] for c in chunks] + [r.y_true]) if chunks else r.y_true
+        if self.ppa:
+            y_pred = torch.argmax(y_pred, dim=1).view(-1, 1)
+        if not isinstance(self.evaluator, Evaluator):
+            y_true, y_pred = y_true.cpu().numpy(), y_pred.cpu().numpy()
+        return r.weighted_loss_sum / n, self.evaluator.eval({"y_true": y_true, "y_pred": y_pred})[self.evaluator.eval_metric]
+
+
+def _graphed_epoch(loader, model, loss_fn, prediction_fn, evaluator):
+    """The GraphedEpoch of (model, loader) and these loss / metric objects, kept on the loader; None for a loader that is not padded."""
+    from .loader import PaddedDataLoader
+    if not isinstance(loader, PaddedDataLoader):
+        return None
+    held = loader.graphed_epochs
+    key = (id(model), _loss_name(loss_fn), _metric_name(prediction_fn), None if evaluator is None else (id(evaluator), evaluator.name))
+    ep = held.get(key)
+    if ep is None or ep.model is not model or ep.evaluator is not evaluator:
+        ep = held[key] = GraphedEpoch(model, loader, loss_fn, prediction_fn, evaluator)
+    return ep
+
+
 def test(loader, model, loss_fn, device, prediction_fn=None, n_iters=None):
     """train_test_funcs.py:177-206: ``(sum_b loss_b * num_graphs_b / len(loader.dataset), sum_b metric_b / len(loader.dataset))`` with one
-    host read, at the end."""
+    host read, at the end.  Over a ``loader.PaddedDataLoader``: the same through a :class:`GraphedEpoch` kept on the loader."""
     model.eval()
+    graphed = _graphed_epoch(loader, model, loss_fn, prediction_fn, None)
+    if graphed is not None:
+        return graphed.run(n_iters)
     loss, metric = _loss_name(loss_fn), _metric_name(prediction_fn)
     acc = None
     with torch.no_grad():
@@ -360,8 +507,12 @@ def test(loader, model, loss_fn, device, prediction_fn=None, n_iters=None):
 def test_ogb(loader, model, loss_fn, device, evaluator, n_iters=None):
     """train_test_funcs.py:209-259: ``(sum_b loss_b * num_graphs_b / len(loader.dataset), evaluator.eval(...)[evaluator.eval_metric])``.
     Rows are gathered on the device; a batch whose ``x`` has one row is skipped (:230); ``ogbg-ppa`` takes the arg-max of the
-    predictions (:236-238) and, as the training loop does (:96), ``loss_fn(pred, y.view(-1))``."""
+    predictions (:236-238) and, as the training loop does (:96), ``loss_fn(pred, y.view(-1))``.  Over a ``loader.PaddedDataLoader``: the same
+    through a :class:`GraphedEpoch` kept on the loader."""
     model.eval()
+    graphed = _graphed_epoch(loader, model, loss_fn, None, evaluator)
+    if graphed is not None:
+        return graphed.run(n_iters)
     loss = _loss_name(loss_fn)
     ppa = evaluator.name == "ogbg-ppa"
     acc = None

@@ -11,10 +11,18 @@ by ONE HIP launch (``gsn_loader_collate_hip``, csrc/loader.hip).
 * :class:`Batch`         -- what ``next()`` returns: every field under its own name plus ``batch``, ``ptr``, ``num_graphs``, the host pointers
   ``node_ptr`` / ``edge_ptr`` and ``graph_partition`` (exact sizes: ``models._register_partition`` needs no device read).
 
-Batches have variable shapes: they are not for capture into a HIP graph (padding rows would enter train-mode BatchNorm statistics).
+* :class:`PaddedDataLoader` / :class:`PaddedBatch` -- the same batches collated into ONE set of static, fixed-capacity tensors
+  (``gsn_loader_collate_padded_hip``), filled up with whole *pad graphs*: shapes and pointers never change, so an EVALUATION step over them
+  can be captured into a HIP graph once and replayed per batch (``evaluation.GraphedEpoch``).
+
+Batches of :class:`DataLoader` have variable shapes: they are not for capture into a HIP graph.  Padded batches are for ``model.eval()``
+only (padding rows would enter train-mode BatchNorm statistics; the models refuse them in training mode).
 There is no CPU path: the host code here validates, sizes and plans; the rows are moved by the kernel only.
 """
 from __future__ import annotations
+
+import ctypes
+import weakref
 
 import numpy as np
 import torch
@@ -24,7 +32,7 @@ from .data import Data
 
 GSN_LOADER_MAX_FIELDS = 16
 _KIND_COPY, _KIND_EDGE_INDEX = 0, 1
-_F_NODES = 1
+_F_NODES, _F_PAD_EDGES, _F_PAD_GRAPH = 1, 2, 4
 _DTYPES = {torch.int64: 8, torch.int32: 4, torch.float32: 4, torch.float64: 8}
 _NODE_FIELD, _EDGE_FIELD = "x", "edge_index"
 
@@ -401,4 +409,234 @@ class DataLoader:
             return _Epoch(self, perm.numpy())
         ep = _Epoch(self, perm.numpy(), self._sequential)
         self._sequential = ep.shared
+        return ep
+
+
+# ---- padded, fixed-shape batches ----------------------------------------------------------------------------------------------------
+class PaddedShape:
+    """The static shape of a padded loader: ``n_chunk`` / ``e_chunk`` (the most vertices / edge columns of a pad graph), ``node_capacity``,
+    ``edge_capacity``, ``pad_slots`` (P) and ``graph_slots`` (G_cap = batch_size + P)."""
+    __slots__ = ("batch_size", "n_chunk", "e_chunk", "node_capacity", "edge_capacity", "pad_slots", "graph_slots")
+
+    def __repr__(self):
+        return "PaddedShape(%s)" % ", ".join("%s=%d" % (k, getattr(self, k)) for k in self.__slots__)
+
+
+def _ceil_div(a, b):
+    return -(-int(a) // int(b))
+
+
+def padded_shape(n_sizes, e_sizes, batch_size, shuffle=False, drop_last=False, node_capacity=None, edge_capacity=None):
+    """Host arithmetic of a padded loader over graphs of ``n_sizes`` vertices and ``e_sizes`` edge columns (int arrays [G], in dataset
+    order).  ``n_chunk = max(n_max, 2)``, ``e_chunk = max(e_max, 1)``: a pad graph is never larger than the dataset's largest graph.
+    Default capacities hold every batch the loader can draw -- sequential: of its own batches; shuffled: of the ``batch_size`` largest
+    graphs -- and ``node_capacity`` adds the vertices of the pad graphs that use up what a smaller batch leaves:
+    ``N_cap = M + max(1, ceil(M / (n_chunk - 1)), ceil(E_cap / e_chunk))`` with M the most ``N_r + batch_size - b`` of a batch."""
+    n = np.asarray(n_sizes, dtype=np.int64).reshape(-1)
+    e = np.asarray(e_sizes, dtype=np.int64).reshape(-1)
+    G, B = int(n.shape[0]), int(batch_size)
+    if G < 1 or e.shape[0] != G or B < 1:
+        raise ValueError("padded_shape: %d graphs, %d edge counts, batch_size %d" % (G, e.shape[0], B))
+    sh = PaddedShape()
+    sh.batch_size = B
+    sh.n_chunk, sh.e_chunk = max(int(n.max()), 2), max(int(e.max()), 1)
+    if shuffle:
+        k = min(B, G)
+        m = int(np.sort(np.maximum(n, 1))[G - k:].sum()) + B - k
+        e_need = int(np.sort(e)[G - k:].sum())
+    else:
+        starts = np.arange(0, G, B)
+        b = np.minimum(B, G - starts)
+        n_tot, e_tot = np.add.reduceat(n, starts) + B - b, np.add.reduceat(e, starts)
+        if drop_last and G >= B:                      # (the partial batch is never drawn)
+            n_tot, e_tot = n_tot[b == B], e_tot[b == B]
+        m, e_need = int(n_tot.max()), int(e_tot.max())
+    sh.edge_capacity = e_need if edge_capacity is None else int(edge_capacity)
+    if sh.edge_capacity < 0:
+        raise ValueError("padded_shape: edge_capacity = %r" % (edge_capacity,))
+    if node_capacity is None:
+        sh.node_capacity = m + max(1, _ceil_div(m, sh.n_chunk - 1), _ceil_div(sh.edge_capacity, sh.e_chunk))
+    else:
+        sh.node_capacity = int(node_capacity)
+    if sh.node_capacity < 1:
+        raise ValueError("padded_shape: node_capacity = %r" % (node_capacity,))
+    sh.pad_slots = max(1, _ceil_div(sh.node_capacity, sh.n_chunk), _ceil_div(sh.edge_capacity, sh.e_chunk))
+    sh.graph_slots = B + sh.pad_slots
+    return sh
+
+
+def padded_fits(sh, b, n_real_nodes, n_real_edges):
+    """A batch of ``b`` graphs fits iff every pad slot can have its vertex and the real edge columns do not pass the capacity."""
+    return int(n_real_nodes) + sh.graph_slots - int(b) <= sh.node_capacity and int(n_real_edges) <= sh.edge_capacity
+
+
+def pad_pointers(sh, b, n_real_nodes, n_real_edges):
+    """``(node_ptr, edge_ptr)`` int64 [S + 1] of the S = graph_slots - b pad graphs of a batch that fits: pad graph k has
+    ``1 + min(n_chunk - 1, max(0, r_n - k (n_chunk - 1)))`` vertices and ``min(e_chunk, max(0, r_e - k e_chunk))`` edge columns
+    (``r_n = N_cap - N_r - S``, ``r_e = E_cap - E_r``); the last entries are the capacities."""
+    S = sh.graph_slots - int(b)
+    k = np.arange(S + 1, dtype=np.int64)
+    r_n, r_e = sh.node_capacity - int(n_real_nodes) - S, sh.edge_capacity - int(n_real_edges)
+    return int(n_real_nodes) + k + np.minimum(r_n, k * (sh.n_chunk - 1)), int(n_real_edges) + np.minimum(r_e, k * sh.e_chunk)
+
+
+class PaddedBatch(Batch):
+    """A padded batch: ``num_graphs = G_cap`` graph slots of which the first ``num_real_graphs`` are real (``num_real_nodes`` vertices,
+    ``num_real_edges`` edge columns; ``n_valid``: the same count on the device).  The tensors BELONG TO THE LOADER and are refilled by the
+    next batch: copy what must outlive it."""
+    padded = True
+
+
+_NP_OF = {torch.int64: np.int64, torch.int32: np.int32, torch.float32: np.float32, torch.float64: np.float64}
+
+
+def _fill_word(f, value):
+    a = np.zeros(1, dtype=_NP_OF[f.dtype])
+    a[0] = value
+    return int(a.view(np.uint64 if f.elem_bytes == 8 else np.uint32)[0])
+
+
+class _PaddedEpoch(_Epoch):
+    """One epoch of a padded loader: :class:`_Epoch`'s order and plan; a batch that fits goes into the loader's static tensors, one that
+    does not is an ordinary :class:`Batch` of the unpadded path."""
+
+    def __init__(self, loader, order, shared=None):
+        super().__init__(loader, order, shared)
+        st = self.st
+        self.prec = (_abi.gsn_loader_field * len(st.fields))()
+        for r, q, f in zip(self.prec, self.rec, st.fields):
+            for name, _ in _abi.gsn_loader_field._fields_:
+                setattr(r, name, getattr(q, name))
+            t = loader._static[f.name]
+            r.flags = q.flags | loader._pad_flag[f.name]
+            r.dst_rows = int(t.shape[1] if f.kind == _KIND_EDGE_INDEX else t.shape[0])
+            r.dst = t.data_ptr() if r.dst_rows else None
+            r.dst_stride = r.dst_rows if f.kind == _KIND_EDGE_INDEX else 0
+
+    def __next__(self):
+        b = self.b
+        if b >= self.n_batches:
+            raise StopIteration
+        ld, st, sh = self.loader, self.st, self.loader.shape
+        first = b * ld.batch_size
+        B = min(ld.batch_size, self.P - first)
+        totals = self.totals[:, b]
+        n_r = int(totals[st.node_cls])
+        e_r = int(totals[st.edge_cls]) if st.edge_cls >= 0 else 0
+        if not padded_fits(sh, B, n_r, e_r):
+            return super().__next__()
+        self.b = b + 1
+        pad = _abi.gsn_loader_pad(B, sh.graph_slots, n_r, e_r, sh.node_capacity, sh.edge_capacity, sh.n_chunk, sh.e_chunk)
+        out = ld._batch
+        has_edges = st.edge_cls >= 0
+        with _abi.device_guard(st.device):
+            _abi.check(_abi.lib().gsn_loader_collate_padded_hip(len(self.prec), self.prec, ld._fill_words, self.order_ptr, self.plan_ptr, self.stride,
+                                                                first, pad, out.batch.data_ptr(), out.ptr.data_ptr(),
+                                                                ld._edge_ptr_dev.data_ptr() if has_edges else None, out.n_valid.data_ptr(),
+                                                                _abi.current_stream()), "gsn_loader_collate_padded_hip")
+        # the tensors were written behind PyTorch's back: whatever is cached per input tensor and version (aggregation index, packs) is stale
+        torch.autograd.graph.increment_version(ld._tensors)
+        out.num_real_graphs, out.num_real_nodes, out.num_real_edges = B, n_r, e_r
+        pn, pe = pad_pointers(sh, B, n_r, e_r)
+        node_ptr = np.empty(sh.graph_slots + 1, dtype=np.int64)
+        node_ptr[:B] = self.plan[st.node_cls, first:first + B]
+        node_ptr[B:] = pn
+        out.node_ptr = node_ptr
+        if has_edges:
+            edge_ptr = np.empty(sh.graph_slots + 1, dtype=np.int64)
+            edge_ptr[:B] = self.plan[st.edge_cls, first:first + B]
+            edge_ptr[B:] = pe
+            out.edge_ptr = edge_ptr
+        return out
+
+
+class PaddedDataLoader(DataLoader):
+    """:class:`DataLoader` with every batch collated into ONE set of static tensors of fixed capacity, by one launch
+    (``gsn_loader_collate_padded_hip``): ``node_capacity`` vertices, ``edge_capacity`` edge columns and ``graph_slots = batch_size +
+    pad_slots`` graphs.  The real graphs come first, laid out exactly as the :class:`DataLoader` batch of the same generator state; the
+    slots behind them hold *pad graphs* of 1 .. ``n_chunk`` vertices and 0 .. ``e_chunk`` self-loop columns that use up the capacities
+    exactly (:func:`padded_shape`, :func:`pad_pointers`).  Pad rows of per-vertex and per-edge fields are zero (code 0 is valid for every
+    encoder), of per-graph fields NaN (floating) or 0 (integer); ``fill={"name": value}`` overrides a field's fill.
+
+    A field is per-vertex when it shares ``x``'s row pointer, per-edge when it shares ``edge_index``'s, per-graph when every graph has one
+    row of it (in a dataset of single-vertex graphs, where that is ambiguous: ``y`` and scalar attributes are per-graph, the rest
+    per-vertex); any other field (a ``degrees`` cut short) is refused with ``ValueError``.
+
+    UNLIKE a :class:`Batch`, the :class:`PaddedBatch` does not stay valid: every ``next()`` returns the SAME object with the SAME tensors,
+    refilled (every byte of them is rewritten by every launch).  That is what lets a step over it be captured into a HIP graph once
+    (``evaluation.GraphedEpoch``).  Hence one live iterator per loader: a second ``iter()`` while an unfinished one is alive raises
+    ``RuntimeError``.  Default capacities hold every batch; with explicit smaller ones a batch that does not fit is delivered as an
+    ordinary unpadded :class:`Batch`.  For evaluation only: the models refuse a padded batch in training mode."""
+
+    def __init__(self, dataset, batch_size=1, shuffle=False, drop_last=False, generator=None, node_capacity=None, edge_capacity=None, fill=None):
+        super().__init__(dataset, batch_size, shuffle, drop_last, generator)
+        ds = self.dataset
+        st = ds._st
+        fill = dict(fill or {})
+        unknown = sorted(set(fill) - set(st.by_name))
+        if unknown:
+            raise ValueError("PaddedDataLoader: fill names %s, the dataset has %s" % (unknown, ds.field_names))
+        self._pad_flag = {}
+        for f in st.fields:
+            one_row = bool((st.sizes[f.cls][ds._index] == 1).all())
+            if f.name == _NODE_FIELD or f.kind == _KIND_EDGE_INDEX:
+                flag = 0
+            elif f.cls == st.node_cls and not (one_row and (f.scalar or f.name == "y")):
+                flag = 0
+            elif f.cls == st.edge_cls:
+                flag = _F_PAD_EDGES
+            elif one_row:
+                flag = _F_PAD_GRAPH
+            else:
+                raise ValueError("PaddedDataLoader: field %r has rows per graph that are neither the vertices, the edge columns nor one: "
+                                 "it has no padded layout" % f.name)
+            self._pad_flag[f.name] = flag
+        n_sizes = ds.host_sizes(_NODE_FIELD)
+        e_sizes = ds.host_sizes(_EDGE_FIELD) if st.edge_cls >= 0 else np.zeros_like(n_sizes)
+        self.shape = sh = padded_shape(n_sizes, e_sizes, self.batch_size, self.shuffle, self.drop_last, node_capacity, edge_capacity)
+        self.node_capacity, self.edge_capacity, self.pad_slots, self.graph_slots = sh.node_capacity, sh.edge_capacity, sh.pad_slots, sh.graph_slots
+        dev = st.device
+        batch = PaddedBatch()
+        batch._device = dev
+        self._static = {}
+        self._fill_words = (ctypes.c_uint64 * len(st.fields))()
+        for j, f in enumerate(st.fields):
+            flag = self._pad_flag[f.name]
+            if f.kind == _KIND_EDGE_INDEX:
+                t = torch.zeros((2, sh.edge_capacity), dtype=torch.int64, device=dev)
+            else:
+                rows = sh.graph_slots if flag == _F_PAD_GRAPH else sh.edge_capacity if flag == _F_PAD_EDGES else sh.node_capacity
+                t = torch.zeros((rows,) + (() if f.scalar else f.trailing), dtype=f.dtype, device=dev)
+                default = float("nan") if flag == _F_PAD_GRAPH and f.dtype.is_floating_point else 0
+                self._fill_words[j] = _fill_word(f, fill.get(f.name, default))
+            self._static[f.name] = t
+            setattr(batch, f.name, t)
+        batch.batch = torch.zeros((sh.node_capacity,), dtype=torch.int64, device=dev)
+        ptrs = torch.zeros((2, sh.graph_slots + 1), dtype=torch.int64, device=dev)
+        batch.ptr, self._edge_ptr_dev = ptrs[0], ptrs[1]
+        batch.num_graphs = sh.graph_slots
+        batch.n_valid = torch.zeros((1,), dtype=torch.int64, device=dev)
+        batch.num_real_graphs = batch.num_real_nodes = batch.num_real_edges = 0
+        if st.edge_cls >= 0:
+            batch.graph_partition = (batch.ptr, self._edge_ptr_dev, sh.n_chunk, sh.e_chunk, False)
+        self._batch = batch
+        self._tensors = list(self._static.values()) + [batch.batch, ptrs, batch.n_valid]
+        self._live = None
+        self.graphed_epochs = {}          # evaluation.test / test_ogb keep their GraphedEpoch per (model, loss, metric) here
+
+    def static_tensors(self):
+        """Every device tensor a padded batch is made of (fields, ``batch``, the two pointers in one [2, G_cap + 1] tensor, ``n_valid``)."""
+        return list(self._tensors)
+
+    def __iter__(self):
+        live = self._live() if self._live is not None else None
+        if live is not None and live.b < live.n_batches:
+            raise RuntimeError("PaddedDataLoader: an unfinished iterator of this loader is alive, and there is one set of static tensors "
+                               "(its batch would be overwritten)")
+        perm = self._order.draw(len(self.dataset))
+        self.last_permutation = perm
+        ep = _PaddedEpoch(self, perm.numpy(), None if self.shuffle else self._sequential)
+        if not self.shuffle:
+            self._sequential = ep.shared
+        self._live = weakref.ref(ep)
         return ep

@@ -35,6 +35,13 @@ def _register_partition(data, edge_index):
             _layers.set_batch_partition(batch, part[0])           # the readout's rows are grouped by graph already
 
 
+def _refuse_padded_training(module, data):
+    """A padded batch (loader.PaddedBatch) is for evaluation: in training mode its pad rows would enter the BatchNorm batch statistics."""
+    if module.training and getattr(data, "padded", False):
+        raise RuntimeError("%s: a padded batch in training mode (its pad rows would enter the BatchNorm statistics); call model.eval(), "
+                           "or train over loader.DataLoader" % type(module).__name__)
+
+
 _PARAMETER_FREE_ENCODERS = ("one_hot_encoder", "atom_one_hot_encoder", "bond_one_hot_encoder")
 
 
@@ -196,6 +203,7 @@ class GNNSubstructures(nn.Module):
         self.activation = choose_activation(kwargs["activation"])
 
     def forward(self, data, print_flag=False, return_intermediate=False):
+        _refuse_padded_training(self, data)
         kwargs = {"degrees": self.degree_encoder(data.degrees)}
         memo = {}
         edge_index = data.edge_index
@@ -344,6 +352,7 @@ class GNN_OGB(nn.Module):
         self.activation = choose_activation(kwargs["activation"])
 
     def forward(self, data, return_intermediate=False):
+        _refuse_padded_training(self, data)
         kwargs = {"degrees": self.degree_encoder(data.degrees)}
         memo = {}
         edge_index = data.edge_index

@@ -1059,6 +1059,14 @@ int64_t gsn_eval_accumulate_scratch_bytes(int kind, int64_t rows, int64_t cols);
 int gsn_eval_accumulate_hip(int kind, int metric, int64_t rows, int64_t cols, int64_t y_cols, const float *y_hat, const void *y,
                             int64_t num_graphs, double *acc_f64, int64_t *acc_i64, float *pred_buf, void *true_buf, int64_t capacity,
                             float *loss_out, void *scratch, int64_t scratch_bytes, void *stream);
+/* The same with the row count READ FROM DEVICE MEMORY (a padded batch whose valid rows come first; gsn_loader_collate_padded_hip writes
+ * n_valid): with v = clamp(*n_valid, 0, rows) it does exactly what gsn_eval_accumulate_hip does when called with rows = v and
+ * num_graphs = v on the same pointers -- loss, metric and arg-max over the first v rows, v rows appended, cursor advanced by v, weight v,
+ * nothing at all when v == 0 -- through the same device functions and the same partition.  The host `rows` only picks the launch shape and
+ * the scratch size (gsn_eval_accumulate_scratch_bytes(kind, rows, cols)); rows behind v are never read. */
+int gsn_eval_accumulate_counted_hip(int kind, int metric, int64_t rows, int64_t cols, int64_t y_cols, const float *y_hat, const void *y,
+                                    const int64_t *n_valid, double *acc_f64, int64_t *acc_i64, float *pred_buf, void *true_buf,
+                                    int64_t capacity, float *loss_out, void *scratch, int64_t scratch_bytes, void *stream);
 
 /* ROC-AUC and average precision per column of y_pred fp32 [m_rows, n_cols] against y_true fp32 [m_rows, n_cols] (labels 0, 1, NaN =
  * unlabelled) -- what ogb's Evaluator computes through sklearn.metrics.roc_auc_score / average_precision_score (train_test_funcs.py:257-259)
@@ -1121,6 +1129,37 @@ typedef struct gsn_loader_field {
 int gsn_loader_collate_hip(int n_fields, const gsn_loader_field *fields, const int64_t *order, const int64_t *plan,
                            int64_t n_graphs_total, int64_t first, int64_t batch, int64_t *batch_vec, int64_t *node_ptr_out,
                            int64_t *edge_ptr_out, void *stream);
+
+/* The same batch collated into caller-owned STATIC buffers of fixed capacity, in ONE launch (gsn_amd/loader.py: PaddedDataLoader): shapes
+ * and pointers do not change from batch to batch, so what consumes the batch can be captured into a HIP graph once and replayed.
+ *   pad      by value: n_real = b real graphs (1 <= b < graph_slots) with n_real_nodes = N_r vertices and n_real_edges = E_r edge columns;
+ *            capacities node_capacity = N_cap, edge_capacity = E_cap, graph_slots = G_cap; n_chunk >= 2 and e_chunk >= 1, the most
+ *            vertices / edge columns a pad graph may have.
+ *   fields   as above, with dst_rows the field's CAPACITY: N_cap for a per-vertex field, E_cap with GSN_LOADER_F_PAD_EDGES (and for
+ *            edge_index, whose dst_stride is >= E_cap), G_cap with GSN_LOADER_F_PAD_GRAPH (one row per graph).
+ *   fill     host array of one 8-byte word per field, by value in the launch: every element of a pad row of the field is that word (its low
+ *            4 bytes for 4-byte elements).  Ignored for edge_index.
+ * Slots [0, b) are the real graphs, laid out exactly as gsn_loader_collate_hip lays them out.  The S = G_cap - b slots behind them are PAD
+ * GRAPHS.  With r_n = N_cap - N_r - S and r_e = E_cap - E_r, pad graph k has 1 + min(n_chunk - 1, max(0, r_n - k (n_chunk - 1))) vertices
+ * and min(e_chunk, max(0, r_e - k e_chunk)) edge columns: every slot has a vertex, and the totals are exactly N_cap and E_cap.  Column t of
+ * a pad graph with v vertices is the self loop of its vertex t mod v.  batch_vec [N_cap], node_ptr_out / edge_ptr_out [G_cap + 1] and
+ * n_valid [1] (= b) are written as well; batch_vec, edge_ptr_out and n_valid may be NULL.
+ * One wave per (field, slot) pair over all G_cap slots; EVERY byte of every output is written by every launch, by exactly one writer (the
+ * buffers are reused: nothing of the previous batch survives).  No atomics, no LDS, int64 offsets.
+ * GSN_E_INVALID when the batch does not fit -- N_r + S > N_cap, E_r > E_cap, or spare rows the S pad graphs cannot hold -- or a field's
+ * dst_rows is not its capacity, besides what gsn_loader_collate_hip refuses.  Asynchronous on `stream`, allocates nothing.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define GSN_LOADER_F_PAD_EDGES 2
+#define GSN_LOADER_F_PAD_GRAPH 4
+typedef struct gsn_loader_pad {
+    int64_t n_real, graph_slots;
+    int64_t n_real_nodes, n_real_edges;
+    int64_t node_capacity, edge_capacity;
+    int64_t n_chunk, e_chunk;
+} gsn_loader_pad;
+int gsn_loader_collate_padded_hip(int n_fields, const gsn_loader_field *fields, const uint64_t *fill, const int64_t *order, const int64_t *plan,
+                                  int64_t n_graphs_total, int64_t first, const gsn_loader_pad *pad, int64_t *batch_vec,
+                                  int64_t *node_ptr_out, int64_t *edge_ptr_out, int64_t *n_valid, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Dropout with the residual add in ONE launch, and its adjoint, without a mask tensor (models_graph_classification_ogb_original.py:243-245:

@@ -63,6 +63,10 @@ def main():
     ap.add_argument("--dropout", default=None, choices=["torch", "native"],
                     help="native: gsn_amd.dropout -- one HIP launch with the residual add, the call counter on the device (default: GSN_DROPOUT, else torch)")
     ap.add_argument("--residual", action="store_true", help="the model's residual connections (README.md:121 runs without)")
+    ap.add_argument("--eval", default="none", choices=["none", "eager", "padded"],
+                    help="after the steps, one evaluation epoch (evaluation.test_ogb, ROC-AUC) over --eval-graphs molhiv-shaped graphs: eager over "
+                         "gsn_amd.loader.DataLoader, or padded over PaddedDataLoader (one collate launch + one HIP-graph replay per batch)")
+    ap.add_argument("--eval-graphs", type=int, default=1024)
     args = ap.parse_args()
     rank, world, local = (int(os.environ.get(k, d)) for k, d in (("RANK", "0"), ("WORLD_SIZE", "1"), ("LOCAL_RANK", "0")))
     torch.cuda.set_device(local)
@@ -77,6 +81,38 @@ def main():
         print(json.dumps(res))
     if dist is not None:
         dist.destroy_process_group()
+
+
+def evaluate(args, model, d_id, dev, rank=0):
+    """``--eval``: an evaluation epoch of the trained model over a device-resident dataset of molhiv-shaped graphs (random codes within the
+    model's feature dims, 20 % NaN labels), batch size ``--batch``.  -> dict for the result line; the model is left in training mode."""
+    from gsn_amd import evaluation as ev
+    from gsn_amd.data import Data
+    from gsn_amd.loader import DataLoader, DeviceDataset, PaddedDataLoader
+    G = max(int(args.eval_graphs), args.batch)
+    b = synth.zinc_shape_batch(G, seed=900 + rank, mean_n=25.5, sd_n=8.0, n_min=4, n_max=60)
+    rng = np.random.default_rng(900 + rank)
+    x = np.stack([rng.integers(0, k, b.num_nodes) for k in encoding.ATOM_FEATURE_DIMS], 1)
+    ef = np.stack([rng.integers(0, k, b.num_edges) for k in encoding.BOND_FEATURE_DIMS], 1)
+    ids = np.stack([rng.integers(0, k, b.num_edges) for k in d_id], 1)
+    y = rng.integers(0, 2, (G, 1, 1)).astype(np.float32)
+    y[rng.random((G, 1, 1)) < 0.2] = np.nan
+    graphs = []
+    for g in range(G):
+        n0, n1, e0, e1 = int(b.node_ptr[g]), int(b.node_ptr[g + 1]), int(b.edge_ptr[g]), int(b.edge_ptr[g + 1])
+        graphs.append(Data(edge_index=torch.from_numpy(b.edge_index[:, e0:e1] - n0), x=torch.from_numpy(x[n0:n1]), degrees=torch.zeros(n1 - n0),
+                           edge_features=torch.from_numpy(ef[e0:e1]), y=torch.from_numpy(y[g]), identifiers=torch.from_numpy(ids[e0:e1])))
+    ds = DeviceDataset(graphs, device=dev)
+    loader = (PaddedDataLoader if args.eval == "padded" else DataLoader)(ds, batch_size=args.batch)
+    evaluator, loss_fn = ev.Evaluator("ogbg-molhiv"), ev.MaskedLoss("BCEWithLogitsLoss")
+    ev.test_ogb(loader, model, loss_fn, dev, evaluator)      # warm-up epoch (padded: the capture)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    loss, auc = ev.test_ogb(loader, model, loss_fn, dev, evaluator)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    model.train()
+    return {"loader": args.eval, "graphs": G, "batches": len(loader), "ms_per_batch": round(dt / len(loader) * 1e3, 4), "loss": loss, "rocauc": auc}
 
 
 def build(args, dev, rank=0, dropout=0.5):
@@ -95,6 +131,7 @@ def build(args, dev, rank=0, dropout=0.5):
               d_out_degree_embedding=dm, d_out_vn=[dm] * (L - 1), vn_pooling="sum", extend_dims=True, activation=act)
     torch.manual_seed(0)      # identical replicas
     model = models.GNN_OGB(9, 1, None, d_id, 3, None, None, None, None, **kw).to(dev).train()
+    model.identifier_dims = [int(k) for k in d_id]      # (for --eval: codes of an evaluation set must lie within the embeddings)
     params = [p for p in model.parameters()]
     n_params = sum(p.numel() for p in params)
     if getattr(args, "optimizer", "sgd") == "adam":
@@ -160,7 +197,10 @@ def run(args, dev, dist=None, rank=0, world=1):
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    return {"workload": "molhiv-shaped GNN_OGB training step (%d layers, d=%d, vn), batch %d graphs/GPU (N=%d, E=%d)" % (L, dm, args.batch, N, E),
+    extra = {}
+    if getattr(args, "eval", "none") != "none":
+        extra["eval"] = evaluate(args, model, model.identifier_dims, dev, rank)
+    return {**extra, "workload": "molhiv-shaped GNN_OGB training step (%d layers, d=%d, vn), batch %d graphs/GPU (N=%d, E=%d)" % (L, dm, args.batch, N, E),
             "n_gpus": world, "graphs_per_s": round(world * args.batch * args.steps / dt, 1),
             "ms_per_step": round(dt / args.steps * 1e3, 3), "parameters": n_params,
             "grad_bucket_MB": round(n_params * 4 / 1e6, 2), "loss": float(loss.item()),
