@@ -183,6 +183,13 @@ SIGNATURES = {
                                         c_vp, c_int, c_vp, c_vp]),
     "gsn_bn_finalize_count_hip": (c_int, [c_i64, c_i64, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                           c_vp]),
+    "gsn_bn_finalize_bounded_scratch_bytes": (c_i64, [c_i64]),
+    "gsn_bn_finalize_bounded_hip": (c_int, [c_i64, c_i64, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                            c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "gsn_bn_act_bwd_from_h_bounded_hip": (c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                                  c_vp]),
+    "gsn_masked_loss_fwd_counted_hip": (c_int, [c_int, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "gsn_masked_loss_bwd_counted_hip": (c_int, [c_int, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "gsn_column_stats_hip": (c_int, [c_i64, c_i64, c_vp, c_vp, c_vp]),
     "gsn_mlp_chain_supported": (c_int, [c_int, ctypes.POINTER(gsn_chain_stage)]),
     "gsn_layer_fused_supported": (c_int, [ctypes.POINTER(gsn_chain_stage), c_i64, ctypes.POINTER(gsn_chain_stage), ctypes.POINTER(gsn_chain_stage)]),

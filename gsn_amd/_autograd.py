@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _abi, flags
+from . import _abi, _bound, flags
 from ._caches import _note_cache
 from ._dense import _Stage, _block_array, _bn_resolve, _f16x3_takes, _linear_hip
 from ._index import _csr_for, propagate
@@ -40,6 +40,7 @@ class _DenseStagesFn(torch.autograd.Function):
         else:
             idx0 = [None] * len(blocks0)
             m_rows = blocks0[0].shape[0]
+        bound = spec[0].get("bound")      # (a _bound.RowBound: the rows are a padded batch, BatchNorm statistics over its real rows only)
         saved, meta = [], []
         y = None
         # per stage: the forward product's row scratch (fp16 planes of the stage's input rows), kept when the weight wants a gradient and the
@@ -77,9 +78,11 @@ class _DenseStagesFn(torch.autograd.Function):
                 if bn_train:
                     stats = _zeros(2 * n_out, torch.float64, w.device).view(2, n_out)
                     h = _linear_hip(blks, w, b, None, None, None, 0, m_rows, out=True, stats=stats, scratch_out=scr, presplit=pre)
-                    fused_act = 1 < m_rows <= flags.FUSE_BN_ACT_ROWS
+                    # (under a bound: the bounded finalize, then the normalise + activation pass over all rows as a launch of its own)
+                    fused_act = bound is None and 1 < m_rows <= flags.FUSE_BN_ACT_ROWS
                     yy = torch.empty_like(h) if fused_act else None
-                    _bn_resolve(st, lambda: stats, m_rows, True, fuse_act=(h, _ACT_CODE[sp["act"]], yy) if fused_act else None)
+                    _bn_resolve(st, lambda: stats, m_rows, True, fuse_act=(h, _ACT_CODE[sp["act"]], yy) if fused_act else None, bound=bound,
+                                h=h if bound is not None else None)
                 else:
                     h = _linear_hip(blks, w, b, None, None, None, 0, m_rows, out=True, scratch_out=scr, presplit=pre)
                     yy = None
@@ -123,6 +126,7 @@ class _DenseStagesFn(torch.autograd.Function):
         ctx.spec, ctx.meta, ctx.m_rows = spec, meta, m_rows
         ctx.x_scratch = x_scratch
         ctx.y_dropped = y_dropped
+        ctx.bound = bound
         ctx.n_saved = len(saved)
         ctx.save_for_backward(*saved, *tensors)
         return y
@@ -168,7 +172,9 @@ class _DenseStagesFn(torch.autograd.Function):
             # plane weight gradient: the adjoint pass writes gH's row scratch and no fp32 gH (gsn_bn_act_bwd_planes_hip)
             need_x = si > 0 or any(ctx.needs_input_grad[1 + bi] for bi in range(len(blocks0)))
             want_w = ctx.needs_input_grad[1 + ent["w_i"]]
-            planes_only = (flags.BN_BWD_PLANES and kind in ("bn", "bn_eval") and want_w and ctx.x_scratch[si] is not None and n_out % 4 == 0 and n_out <= 640
+            # (under a bound the plane-writing adjoint is not used: fp32 gH with +0 pad rows, split by gsn_linear_f16x3_split_rows_hip where wanted)
+            bound = ctx.bound if kind in ("bn", "bn_eval") else None
+            planes_only = (bound is None and flags.BN_BWD_PLANES and kind in ("bn", "bn_eval") and want_w and ctx.x_scratch[si] is not None and n_out % 4 == 0 and n_out <= 640
                            and g.data_ptr() % 16 == 0 and (not need_x or _f16x3_takes(m_rows, k_total, [n_out], aligned=saved[off].data_ptr() % 16 == 0)))
             gh = None if planes_only else torch.empty((m_rows, n_out), dtype=torch.float32, device=dev)
             gh_scratch = None
@@ -180,6 +186,13 @@ class _DenseStagesFn(torch.autograd.Function):
                     rc = L.gsn_bn_act_bwd_planes_hip(m_rows, n_out, g.data_ptr(), h.data_ptr(), mean32.data_ptr(), invstd.data_ptr(), scale.data_ptr(),
                                                      shift.data_ptr(), 1 if kind == "bn" else 2, act, sums.data_ptr(), gh_scratch.data_ptr(),
                                                      gbias.data_ptr(), _abi.current_stream())
+                elif bound is not None:
+                    h, y, mean32, invstd, scale, shift = saved[off:off + 6]
+                    sums = sums_z
+                    nv, rp, ns = bound.pointers()
+                    rc = L.gsn_bn_act_bwd_from_h_bounded_hip(m_rows, n_out, g.data_ptr(), h.data_ptr(), mean32.data_ptr(), invstd.data_ptr(),
+                                                             scale.data_ptr(), shift.data_ptr(), 1 if kind == "bn" else 2, act, sums.data_ptr(),
+                                                             gh.data_ptr(), gbias.data_ptr(), nv, rp, ns, _abi.current_stream())
                 elif kind in ("bn", "bn_eval"):
                     h, y, mean32, invstd, scale, shift = saved[off:off + 6]
                     sums = sums_z
@@ -345,16 +358,23 @@ def _dense_native_ok(stages, training=None):
     return True
 
 
-def run_stages_autograd(stages, m_rows, training, gather=None):
+def run_stages_autograd(stages, m_rows, training, gather=None, rows=None):
     """Differentiable evaluation of a dense stage list with the native adjoint.  ``gather = (edge_index, n_nodes, modes)``: block b of
     the first stage is gathered through ``edge_index[modes[b]]`` (None: one row per edge) -- the edge rows cat(x_i, x_j, ..) of
-    GSN_sparse.py:166-171 are then never assembled, neither for the product nor for the weight gradient."""
+    GSN_sparse.py:166-171 are then never assembled, neither for the product nor for the weight gradient.  ``rows``: the row class of the
+    stages' rows ("vertex", "edge", "graph"), named by the call site: under loader.masked_training() the BatchNorm stages take the
+    statistics of that class's real rows (a stage list with BatchNorm on batch statistics and no ``rows`` is refused there)."""
+    bound = None
+    if _bound.is_active() and any(st.bn is not None for st in stages):      # (column sums over rows: batch statistics, or gamma / beta gradients)
+        bound = _bound.active(rows, "run_stages_autograd")
     spec, tensors = [], []
     tensors += [d for d, _ in stages[0].blocks]
     for i, st in enumerate(stages):
         spec.append({"n_blocks": len(st.blocks) if i == 0 else 0, "has_bias": st.bias is not None, "bn": st.bn, "act": st.act})
         if i == 0 and gather is not None and any(m is not None for m in gather[2]):
             spec[0]["gather"] = gather
+        if i == 0 and bound is not None:
+            spec[0]["bound"] = bound
         tensors.append(st.weight)
         if st.bias is not None:
             tensors.append(st.bias)
@@ -407,6 +427,8 @@ def _code_stage_segsum(mf, cblocks, csr, m_rows):
         _abi.check(rc, "gsn_code_stage_fwd_hip")
 
     stage = _Stage(lin.weight, lin.bias, bn, mf.activation_name)
+    if bn is not None and (mf.training or bn.running_mean is None):
+        _bound.refuse("_code_stage_segsum (msg_fn's first stage over integer codes)")
 
     def stats_fn():
         stats = _zeros(2 * n_out, torch.float64, dev).view(2, n_out)

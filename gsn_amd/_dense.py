@@ -7,7 +7,7 @@ import os
 
 import torch
 
-from . import _abi, flags
+from . import _abi, _bound, flags
 from ._caches import _note_cache
 from ._runtime import _ACT_CODE, _MAX_BLOCKS, _f32c, _timed, _zeros
 
@@ -433,15 +433,20 @@ def _rows_forward(x, csr, ge, g0, g1, d_x, prep, fl):
     return out
 
 
-def _bn_resolve(stage, stats_fn, m_rows, training, fuse_act=None):
+def _bn_resolve(stage, stats_fn, m_rows, training, fuse_act=None, bound=None, h=None):
     """Fill stage.bn_params = (mean, scale, shift).  Train mode: batch statistics from a statistics pass (fp64 column
-    sums), running statistics updated exactly like nn.BatchNorm1d."""
+    sums), running statistics updated exactly like nn.BatchNorm1d.  ``bound`` (a _bound.RowBound, with the materialised pre-BN rows ``h``): the
+    rows are a padded batch and the statistics are those of its real rows, counted on the device (gsn_bn_finalize_bounded_hip)."""
     bn = stage.bn
     if bn is None:
         stage.bn_params = None
         return
     if training or bn.running_mean is None:
-        if training and m_rows == 1:
+        if bound is None:
+            _bound.refuse("_bn_resolve without a bound")      # (under masked_training no statistic is silently taken over all rows)
+        elif training and bound.host_rows == 1:
+            raise ValueError("Expected more than 1 value per channel when training, got input size torch.Size([1, %d])" % bn.num_features)
+        if training and m_rows == 1 and bound is None:
             raise ValueError("Expected more than 1 value per channel when training, got input size torch.Size([%d, %d])" % (m_rows, bn.num_features))
         if m_rows == 0:
             # no rows (an edge-less batch in front of an edge stage): nn.BatchNorm1d returns the empty tensor, leaves the running statistics
@@ -474,7 +479,19 @@ def _bn_resolve(stage, stats_fn, m_rows, training, fuse_act=None):
         v0, v1, v2, v3 = vec.unbind(0)           # (the four rows: one call, and their addresses by arithmetic -- this runs per BatchNorm per step)
         p0 = vec.data_ptr()
         with _abi.device_guard(dev):
-            if fuse_act is not None:
+            if bound is not None:
+                # (the launch that stands where gsn_bn_finalize_count_hip stands; its scratch -- fp64 partials and tickets -- from the zero arena)
+                if fuse_act is not None or h is None:
+                    raise RuntimeError("_bn_resolve: a row bound goes with the materialised pre-BN rows and no fused activation pass")
+                bound.used = bn.num_features     # (noted for the host-side refusal of a single real row before a replay)
+                L = _abi.lib()
+                scratch = _zeros((int(L.gsn_bn_finalize_bounded_scratch_bytes(n_out)) + 7) // 8, torch.float64, dev)
+                nv, rp, ns = bound.pointers()
+                rc = L.gsn_bn_finalize_bounded_hip(n_out, m_rows, float(bn.eps), float(mom), stats.data_ptr(), h.data_ptr(), nv, rp, ns, scratch.data_ptr(),
+                                                   _abi.ptr(gamma), _abi.ptr(beta), bn.running_mean.data_ptr() if track else None,
+                                                   bn.running_var.data_ptr() if track else None, p0, p0 + 4 * n_out, p0 + 8 * n_out, p0 + 12 * n_out,
+                                                   _abi.ptr(nbt), _abi.current_stream())
+            elif fuse_act is not None:
                 # (h, act code, out): the normalise + activate pass rides the same launch (flags.FUSE_BN_ACT_ROWS: where a launch costs more than it)
                 fh, fact, fout = fuse_act
                 rc = _abi.lib().gsn_bn_finalize_act_hip(n_out, m_rows, float(bn.eps), float(mom), stats.data_ptr(), _abi.ptr(gamma), _abi.ptr(beta),
@@ -486,7 +503,7 @@ def _bn_resolve(stage, stats_fn, m_rows, training, fuse_act=None):
                                                           bn.running_mean.data_ptr() if track else None, bn.running_var.data_ptr() if track else None,
                                                           p0, p0 + 4 * n_out, p0 + 8 * n_out, p0 + 12 * n_out,
                                                           _abi.ptr(nbt), _abi.current_stream())
-        _abi.check(rc, "gsn_bn_finalize_act_hip" if fuse_act is not None else "gsn_bn_finalize_count_hip")
+        _abi.check(rc, "gsn_bn_finalize_bounded_hip" if bound is not None else "gsn_bn_finalize_act_hip" if fuse_act is not None else "gsn_bn_finalize_count_hip")
         if track:
             # the kernel wrote the running statistics (and the counter) through raw pointers: PyTorch's version counters, on which the
             # eval-mode vectors of this module are cached, have to move with them (no launch); a step being captured into a graph notes
@@ -524,6 +541,8 @@ def run_stages(stages, m_rows, training, csr=None):
     if csr is not None and not _chain_fits(stages):
         return None
     needs_stats = any(st.bn is not None and (training or st.bn.running_mean is None) for st in stages)
+    if needs_stats:
+        _bound.refuse("run_stages (the forward without gradients)")
     if csr is None and needs_stats and not _chain_fits(stages):
         return _run_stages_materialised(stages, m_rows, training)
     for i, st in enumerate(stages):

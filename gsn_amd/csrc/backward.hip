@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "bn_bounded_core.h"
 #include "gsn_internal.h"
 
 namespace gsn {
@@ -53,9 +54,12 @@ __device__ __forceinline__ float act_grad_from_h(float hv, float mu, float sc, f
 
 // pass 1: column sums of gZ and gZ * xh (fp64 [2][C], caller zero-fills).  grid (blocks_x, ceil(C/64)); a wave covers 64
 // adjacent columns of one row, waves stride over rows.
+// BOUNDED: the rows are a padded batch, only its first v = bound_rows(bound, capacity) rows count (`bound` is not looked at otherwise).
+template <bool BOUNDED>
 __global__ __launch_bounds__(256) void bn_act_bwd_reduce_kernel(int64_t m_rows, int n_cols, const float *gy, const float *y,
                                                                 const float *h, const float *mean, const float *invstd,
-                                                                int act, double *sums, const float *zscale, const float *zshift) {
+                                                                int act, double *sums, const float *zscale, const float *zshift, RowBound bound) {
+    if constexpr (BOUNDED) m_rows = bound_rows(bound, m_rows);      // (in front of everything: the loop bound of this pass)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = blockIdx.y * 64 + lane;
     const bool cok = c < n_cols;
@@ -102,10 +106,14 @@ __global__ __launch_bounds__(256) void bn_act_bwd_reduce_kernel(int64_t m_rows, 
 
 // pass 2: gH (may alias gy).  train: coef = gamma * invstd, m1 = sums[0]/M, m2 = sums[1]/M;  otherwise gH = gZ * coef.
 // Also the column sums of gH (fp64 [C], caller zero-fills) = the bias gradient.
+// BOUNDED: divisor and loops end at v; the rows behind it get an exact +0 and their gy is not read.
+template <bool BOUNDED>
 __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(int64_t m_rows, int n_cols, const float *gy, const float *y,
                                                                const float *h, const float *mean, const float *invstd,
                                                                const float *coef, const double *sums, int act, float *gh,
-                                                               double *gbias, const float *zshift) {
+                                                               double *gbias, const float *zshift, RowBound bound) {
+    [[maybe_unused]] const int64_t capacity = m_rows;
+    if constexpr (BOUNDED) m_rows = bound_rows(bound, capacity);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = blockIdx.y * 64 + lane;
     const bool cok = c < n_cols;
@@ -141,6 +149,8 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(int64_t m_rows, i
             const int64_t i = r * n_cols + c;
             one(i, gy[i], y ? y[i] : 0.f, need_h ? h[i] : 0.f);
         }
+        if constexpr (BOUNDED)
+            for (r = m_rows + (int64_t)blockIdx.x * 4 + wave; r < capacity; r += step) gh[r * n_cols + c] = 0.f;
     }
     if (gbias) {
         __shared__ double red[4][64];
@@ -796,10 +806,11 @@ static int bn_act_bwd_launch(int64_t m_rows, int64_t n_cols, const float *grad_y
     // train_bn == 2: BatchNorm on its RUNNING statistics (eval mode) with gradients wanted for gamma / beta: the same column sums
     // (xhat from the running mean / invstd), but grad_h = gZ * coef -- the statistics are constants of the rows
     if (train_bn)
-        hipLaunchKernelGGL(bn_act_bwd_reduce_kernel, grid, dim3(256), 0, s, m_rows, (int)n_cols, grad_y, y, h, mean, invstd, act, sums, coef, shift);
+        hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<false>, grid, dim3(256), 0, s, m_rows, (int)n_cols, grad_y, y, h, mean, invstd, act, sums, coef, shift,
+                           RowBound{});
     // (y == null: both train_bn modes read the pre-BatchNorm rows for the activation derivative)
-    hipLaunchKernelGGL(bn_act_bwd_apply_kernel, grid, dim3(256), 0, s, m_rows, (int)n_cols, grad_y, y, (train_bn == 1 || !y) ? h : y, mean,
-                       invstd, coef, train_bn == 1 ? sums : nullptr, act, grad_h, grad_bias, shift);
+    hipLaunchKernelGGL(bn_act_bwd_apply_kernel<false>, grid, dim3(256), 0, s, m_rows, (int)n_cols, grad_y, y, (train_bn == 1 || !y) ? h : y, mean,
+                       invstd, coef, train_bn == 1 ? sums : nullptr, act, grad_h, grad_bias, shift, RowBound{});
     return launch_check("bn_act_bwd kernels");
 }
 
@@ -818,6 +829,28 @@ extern "C" int gsn_bn_act_bwd_from_h_hip(int64_t m_rows, int64_t n_cols, const f
                              "gsn_bn_act_bwd_from_h_hip");
 }
 
+// gsn_bn_act_bwd_from_h_hip over a padded batch: the bounded instantiations of the two passes; the launch shape follows the capacity m_rows
+extern "C" int gsn_bn_act_bwd_from_h_bounded_hip(int64_t m_rows, int64_t n_cols, const float *grad_y, const float *h, const float *mean,
+                                                 const float *invstd, const float *coef, const float *shift, int train_bn, int act, double *sums,
+                                                 float *grad_h, double *grad_bias, const int64_t *n_valid, const int64_t *row_ptr, int64_t n_slots,
+                                                 void *stream) {
+    const char *who = "gsn_bn_act_bwd_from_h_bounded_hip";
+    if (train_bn != 1 && train_bn != 2) return set_error(GSN_E_INVALID, "%s: a BatchNorm stage (train_bn 1 or 2)", who);
+    if (n_cols < 1 || n_cols > INT32_MAX || act < 0 || act > 3 || !n_valid || n_slots < 0 || (!row_ptr && n_slots != 0) ||
+        (m_rows > 0 && (!grad_y || !grad_h || !h || !sums || !mean || !invstd || !coef)))
+        return set_error(GSN_E_INVALID, "%s: bad arguments", who);
+    if (m_rows <= 0) return GSN_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(bgrid(m_rows), (unsigned)((n_cols + 63) / 64));
+    const RowBound bound{n_valid, row_ptr, n_slots};
+    const float *no_y = nullptr;
+    hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<true>, grid, dim3(256), 0, s, m_rows, (int)n_cols, grad_y, no_y, h, mean, invstd, act, sums, coef,
+                       shift, bound);
+    hipLaunchKernelGGL(bn_act_bwd_apply_kernel<true>, grid, dim3(256), 0, s, m_rows, (int)n_cols, grad_y, no_y, h, mean, invstd, coef,
+                       train_bn == 1 ? sums : (const double *)nullptr, act, grad_h, grad_bias, shift, bound);
+    return launch_check("bn_act_bwd bounded kernels");
+}
+
 // gsn_bn_act_bwd_from_h_hip for a stage whose gH is read as fp16 planes only: reduce pass as there, then bn_act_bwd_planes_kernel writes the
 // row scratch of gH (gsn_linear_f16x3_scratch_bytes(m_rows, n_cols) bytes: what gsn_linear_f16x3_fwd_presplit_hip and gsn_wgrad_f16x3_hip read)
 extern "C" int gsn_bn_act_bwd_planes_hip(int64_t m_rows, int64_t n_cols, const float *grad_y, const float *h, const float *mean, const float *invstd,
@@ -832,7 +865,8 @@ extern "C" int gsn_bn_act_bwd_planes_hip(int64_t m_rows, int64_t n_cols, const f
         return set_error(GSN_E_INVALID, "gsn_bn_act_bwd_planes_hip: grad_y, h and row_scratch must be 16-byte aligned");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid(bgrid(m_rows), (unsigned)((n_cols + 63) / 64));
-    hipLaunchKernelGGL(bn_act_bwd_reduce_kernel, grid, dim3(256), 0, s, m_rows, (int)n_cols, grad_y, (const float *)nullptr, h, mean, invstd, act, sums, coef, shift);
+    hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<false>, grid, dim3(256), 0, s, m_rows, (int)n_cols, grad_y, (const float *)nullptr, h, mean, invstd, act, sums, coef,
+                       shift, RowBound{});
     BwdPlanesArgs a{};
     a.m_rows = m_rows; a.m_pad = gsn_linear_f16x3_mpad(m_rows); a.n_cols = (int)n_cols; a.k_pad = (int)gsn_linear_f16x3_kpad(n_cols);
     a.act = act; a.train = train_bn;

@@ -11,6 +11,7 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "bn_bounded_core.h"
 #include "gsn_internal.h"
 
 namespace gsn {
@@ -1169,19 +1170,8 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(int n_cols, double m_r
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= n_cols) return;
     if (c == 0 && num_batches_tracked) *num_batches_tracked += 1;       // (nn.BatchNorm1d's counter: one tensor op per call otherwise)
-    const double mu = stats[c] / m_rows;
-    double var = stats[n_cols + c] / m_rows - mu * mu;
-    var = var > 0.0 ? var : 0.0;
-    const float is = (float)(1.0 / sqrt(var + eps));
-    mean[c] = (float)mu;
-    invstd[c] = is;
-    scale[c] = gamma ? is * gamma[c] : is;
-    shift[c] = beta ? beta[c] : 0.f;
-    if (running_mean) {
-        const double unbiased = var * (m_rows / (m_rows > 1.0 ? m_rows - 1.0 : 1.0));
-        running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * (double)(float)mu);
-        running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * (double)(float)unbiased);
-    }
+    // (the expressions live in bn_bounded_core.h: gsn_bn_finalize_bounded_hip runs the same ones on its corrected sums)
+    bn_finalize_column(c, stats[c], stats[n_cols + c], m_rows, eps, momentum, gamma, beta, running_mean, running_var, mean, invstd, scale, shift);
 }
 }  // namespace gsn
 

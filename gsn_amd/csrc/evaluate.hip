@@ -136,7 +136,7 @@ template <bool ACC, bool COUNTED = false>
 __global__ __launch_bounds__(256) void ev_small_kernel(EvArgs a, float *loss, int64_t *count, EvAcc c) {
     __shared__ double dbuf[4];
     __shared__ int64_t ibuf[4];
-    if (COUNTED && !ev_count_rows(a, c)) return;
+    if (COUNTED && !ev_count_rows(a, c) && ACC) return;      // (the plain loss of no valid row is still written: NaN, count 0)
     if (ACC) {
         if (ev_overflow(c, a.rows)) {      // (uniform: nobody has written the cursor yet)
             if (threadIdx.x == 0) c.i64[GSN_EVAL_STATUS] |= GSN_EVAL_OVERFLOW;
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256) void ev_partial_kernel(EvArgs a, EvPart *parts
     __shared__ double dbuf[4];
     __shared__ int64_t ibuf[4];
     if (COUNTED) {
-        if (!ev_count_rows(a, c)) return;
+        if (!ev_count_rows(a, c) && ACC) return;
         n_chunks = (ev_units(a) + EV_CHUNK - 1) / EV_CHUNK;      // (the chunks of the valid rows: the host sized the scratch for all rows)
     }
     if (ACC) {
@@ -173,7 +173,7 @@ template <bool ACC, bool COUNTED = false>
 __global__ __launch_bounds__(64) void ev_combine_kernel(EvArgs a, const EvPart *parts, int64_t n_chunks, float *loss, int64_t *count, EvAcc c) {
     if (threadIdx.x != 0) return;
     if (COUNTED) {
-        if (!ev_count_rows(a, c)) return;
+        if (!ev_count_rows(a, c) && ACC) return;
         n_chunks = (ev_units(a) + EV_CHUNK - 1) / EV_CHUNK;
     }
     if (ACC && ev_overflow(c, a.rows)) {
@@ -185,10 +185,29 @@ __global__ __launch_bounds__(64) void ev_combine_kernel(EvArgs a, const EvPart *
     ev_finish(a, t, loss, count, ACC ? &c : nullptr);
 }
 
-__global__ __launch_bounds__(256) void ev_bwd_kernel(EvArgs a, const float *grad_loss, const int64_t *count, float *grad) {
+// COUNTED: the units of the first v = clamp(*n_valid, 0, rows) rows are the batch; the units behind them get +0 and neither y_hat nor y is
+// read there
+template <bool COUNTED = false>
+__global__ __launch_bounds__(256) void ev_bwd_kernel(EvArgs a, const float *grad_loss, const int64_t *count, float *grad, const int64_t *n_valid) {
     const int64_t n = ev_units(a), cnt = *count;
+    [[maybe_unused]] int64_t n_in = n;
+    if constexpr (COUNTED) {
+        int64_t v = *n_valid;
+        v = v < 0 ? 0 : (v > a.rows ? a.rows : v);
+        n_in = a.kind == GSN_LOSS_CE ? (a.cols > 0 ? v : 0) : v * a.cols;
+    }
     const double scale = cnt > 0 ? (double)*grad_loss / (double)cnt : 0.0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        if constexpr (COUNTED) {
+            if (i >= n_in) {
+                if (a.kind == GSN_LOSS_CE) {
+                    for (int64_t j = 0; j < a.cols; ++j) grad[i * a.cols + j] = 0.0f;
+                } else {
+                    grad[i] = 0.0f;
+                }
+                continue;
+            }
+        }
         if (a.kind == GSN_LOSS_CE) {
             const int64_t target = reinterpret_cast<const int64_t *>(a.y)[i];
             const float *x = a.y_hat + i * a.cols;
@@ -358,9 +377,38 @@ extern "C" int gsn_masked_loss_bwd_hip(int kind, int64_t rows, int64_t cols, con
     if (!grad_loss || !count || !grad_y_hat) return set_error(GSN_E_INVALID, "gsn_masked_loss_bwd_hip: null gradient or count pointer");
     EvArgs a{kind, GSN_METRIC_NONE, rows, cols, y_hat, y};
     const int64_t units = kind == GSN_LOSS_CE ? rows : rows * cols;
-    hipLaunchKernelGGL(ev_bwd_kernel, dim3(us_grid((units + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, grad_loss, count,
-                       grad_y_hat);
+    hipLaunchKernelGGL(ev_bwd_kernel<false>, dim3(us_grid((units + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, grad_loss, count,
+                       grad_y_hat, (const int64_t *)nullptr);
     return launch_check("ev_bwd_kernel");
+}
+
+// The two launches of the masked loss with the row count READ FROM DEVICE MEMORY: rows >= clamp(*n_valid, 0, rows) are unlabelled whatever
+// they hold (the integer pad targets of CrossEntropyLoss are 0, not NaN).  The host `rows` picks the launch shape and the scratch size.
+extern "C" int gsn_masked_loss_fwd_counted_hip(int kind, int64_t rows, int64_t cols, const float *y_hat, const void *y, const int64_t *n_valid,
+                                               float *loss, int64_t *count, void *scratch, int64_t scratch_bytes, void *stream) {
+    if (!n_valid) return set_error(GSN_E_INVALID, "gsn_masked_loss_fwd_counted_hip: null n_valid");
+    const int rc = ev_check("gsn_masked_loss_fwd_counted_hip", kind, rows, cols, y_hat, y, true, scratch, scratch_bytes);
+    if (rc != GSN_OK) return rc;
+    if ((rows == 0 || cols == 0) && (!loss || !count)) return GSN_OK;
+    if (!loss || !count) return set_error(GSN_E_INVALID, "gsn_masked_loss_fwd_counted_hip: null loss or count pointer");
+    EvArgs a{kind, GSN_METRIC_NONE, rows, cols, y_hat, y};
+    EvAcc c{};
+    c.n_valid = n_valid;
+    return ev_launch<false, true>(a, loss, count, c, scratch, stream);
+}
+
+extern "C" int gsn_masked_loss_bwd_counted_hip(int kind, int64_t rows, int64_t cols, const float *y_hat, const void *y, const int64_t *n_valid,
+                                               const float *grad_loss, const int64_t *count, float *grad_y_hat, void *stream) {
+    if (!n_valid) return set_error(GSN_E_INVALID, "gsn_masked_loss_bwd_counted_hip: null n_valid");
+    const int rc = ev_check("gsn_masked_loss_bwd_counted_hip", kind, rows, cols, y_hat, y, false, nullptr, 0);
+    if (rc != GSN_OK) return rc;
+    if (rows == 0 || cols == 0) return GSN_OK;
+    if (!grad_loss || !count || !grad_y_hat) return set_error(GSN_E_INVALID, "gsn_masked_loss_bwd_counted_hip: null gradient or count pointer");
+    EvArgs a{kind, GSN_METRIC_NONE, rows, cols, y_hat, y};
+    const int64_t units = kind == GSN_LOSS_CE ? rows : rows * cols;
+    hipLaunchKernelGGL(ev_bwd_kernel<true>, dim3(us_grid((units + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, grad_loss,
+                       count, grad_y_hat, n_valid);
+    return launch_check("ev_bwd_kernel<counted>");
 }
 
 static int ev_accumulate(const char *who, const int64_t *n_valid, int kind, int metric, int64_t rows, int64_t cols, int64_t y_cols, const float *y_hat, const void *y,

@@ -27,6 +27,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _abi
+from . import _bound
 from ._autograd import run_stages_autograd
 from ._dense import _Stage
 from ._index import _csr_for, global_add_pool_sparse, global_mean_pool_sparse
@@ -468,6 +469,7 @@ class MLP(nn.Module):
 
     def forward(self, x, post=None):
         _need_cuda(x, "mlp input")
+        _bound.refuse("dgn: the MLP stages of a DGN layer")      # (DGN models are not trained on padded batches: DESIGN.md 8f)
         return run_stages_autograd(self.stages(x, post), x.shape[0], self.training)
 
 
@@ -548,6 +550,7 @@ class MLPReadout(nn.Module):
         _need_cuda(x, "readout input")
         stages = [_Stage(lin.weight, lin.bias, None, "relu" if i < self.L else "identity", [(x, None)] if i == 0 else ())
                   for i, lin in enumerate(self.FC_layers)]
+        _bound.refuse("dgn: the readout MLP")
         return run_stages_autograd(stages, x.shape[0], self.training)
 
 

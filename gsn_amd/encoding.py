@@ -589,7 +589,8 @@ class DiscreteEmbedding(nn.Module):
             raise NotImplementedError("Encoder {} is not currently supported.".format(encoder_name))
         self.d_out = d_out
 
-    def forward(self, x):
+    def forward(self, x, rows=None):
+        """``rows``: the row class of ``x`` ("vertex", "edge", "graph") for the mlp encoder's BatchNorm under loader.masked_training()."""
         x = x.unsqueeze(-1) if x.dim() == 1 else x
         if self.encoder is None:
             return x.float()
@@ -597,5 +598,5 @@ class DiscreteEmbedding(nn.Module):
             from .layers import run_linear_module
             return run_linear_module(self.encoder, x.float())
         if self.encoder_name == "mlp":
-            return self.encoder(x.float())
+            return self.encoder(x.float(), rows=rows)
         return self.encoder(x.long())

@@ -62,9 +62,14 @@ def _scratch(n_bytes, dev):
     return torch.empty(max(int(n_bytes), 8), dtype=torch.uint8, device=dev) if n_bytes > 0 else None
 
 
+def _check_n_valid(who, n_valid, device=None):
+    if not isinstance(n_valid, torch.Tensor) or n_valid.dtype != torch.int64 or n_valid.numel() != 1 or (device is not None and n_valid.device != device):
+        raise TypeError("%s: n_valid is an int64 tensor of one element on the device of y_hat" % who)
+
+
 class _MaskedLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, y_hat, y, kind):
+    def forward(ctx, y_hat, y, kind, n_valid=None):
         _abi.require_gpu()
         k = _kind_of(kind)
         y_hat, y, rows, cols = _operands(kind, y_hat, y)
@@ -74,9 +79,16 @@ class _MaskedLossFn(torch.autograd.Function):
         count = torch.empty((), dtype=torch.int64, device=dev)
         nb = L.gsn_masked_loss_scratch_bytes(k, rows, cols)
         ws = _scratch(nb, dev)
+        if n_valid is not None:
+            _check_n_valid("masked_loss", n_valid, dev)
         with _abi.device_guard(dev):
-            _abi.check(L.gsn_masked_loss_fwd_hip(k, rows, cols, y_hat.data_ptr(), y.data_ptr(), loss.data_ptr(), count.data_ptr(), _abi.ptr(ws), nb,
-                                                 _abi.current_stream()), "gsn_masked_loss_fwd_hip")
+            if n_valid is None:
+                _abi.check(L.gsn_masked_loss_fwd_hip(k, rows, cols, y_hat.data_ptr(), y.data_ptr(), loss.data_ptr(), count.data_ptr(), _abi.ptr(ws), nb,
+                                                     _abi.current_stream()), "gsn_masked_loss_fwd_hip")
+            else:       # (rows behind n_valid are unlabelled whatever they hold: the row count is read on the device)
+                _abi.check(L.gsn_masked_loss_fwd_counted_hip(k, rows, cols, y_hat.data_ptr(), y.data_ptr(), n_valid.data_ptr(), loss.data_ptr(),
+                                                             count.data_ptr(), _abi.ptr(ws), nb, _abi.current_stream()), "gsn_masked_loss_fwd_counted_hip")
+        ctx.n_valid = n_valid
         ctx.save_for_backward(y_hat, y, count)
         ctx.shape = (k, rows, cols)
         ctx.mark_non_differentiable(count)
@@ -86,23 +98,32 @@ class _MaskedLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_loss, _grad_count):
         if grad_loss is None:
-            return None, None, None
+            return None, None, None, None
         y_hat, y, count = ctx.saved_tensors
         k, rows, cols = ctx.shape
         grad = torch.empty_like(y_hat)
         g = grad_loss.to(torch.float32).contiguous()
         if rows and cols:
             with _abi.device_guard(y_hat.device):
-                _abi.check(_abi.lib().gsn_masked_loss_bwd_hip(k, rows, cols, y_hat.data_ptr(), y.data_ptr(), g.data_ptr(), count.data_ptr(), grad.data_ptr(),
-                                                              _abi.current_stream()), "gsn_masked_loss_bwd_hip")
-        return grad, None, None
+                if ctx.n_valid is None:
+                    _abi.check(_abi.lib().gsn_masked_loss_bwd_hip(k, rows, cols, y_hat.data_ptr(), y.data_ptr(), g.data_ptr(), count.data_ptr(),
+                                                                  grad.data_ptr(), _abi.current_stream()), "gsn_masked_loss_bwd_hip")
+                else:
+                    _abi.check(_abi.lib().gsn_masked_loss_bwd_counted_hip(k, rows, cols, y_hat.data_ptr(), y.data_ptr(), ctx.n_valid.data_ptr(), g.data_ptr(),
+                                                                          count.data_ptr(), grad.data_ptr(), _abi.current_stream()),
+                               "gsn_masked_loss_bwd_counted_hip")
+        return grad, None, None, None
 
 
-def masked_loss(kind, y_hat, y, return_count=False):
+def masked_loss(kind, y_hat, y, return_count=False, n_valid=None):
     """Mean of the ``kind`` loss over the labelled entries (``y`` not NaN; ``y`` is viewed to ``y_hat``'s shape as train_test_funcs.py:98-99
     does), a 0-d fp32 tensor on ``y_hat``'s device, differentiable in ``y_hat``.  ``CrossEntropyLoss``: ``y`` int64 [rows], nothing is
-    unlabelled, a target outside the classes gives a NaN loss and a zero gradient row.  No labelled entry: NaN loss, zero gradient."""
-    loss, count = _MaskedLossFn.apply(y_hat, y, kind)
+    unlabelled, a target outside the classes gives a NaN loss and a zero gradient row.  No labelled entry: NaN loss, zero gradient.
+    ``n_valid`` (int64 device tensor of one element, a padded batch's ``batch.n_valid``): rows from ``clamp(n_valid, 0, rows)`` on are
+    unlabelled whatever they hold and get zero gradient rows; the count is read on the device, so the node can be captured and replayed."""
+    if n_valid is not None:
+        _check_n_valid("masked_loss", n_valid)
+    loss, count = _MaskedLossFn.apply(y_hat, y, kind, n_valid)
     return (loss, count) if return_count else loss
 
 
@@ -114,8 +135,8 @@ class MaskedLoss(nn.Module):
         _kind_of(kind)
         self.kind = kind
 
-    def forward(self, y_hat, y):
-        return masked_loss(self.kind, y_hat, y)
+    def forward(self, y_hat, y, n_valid=None):
+        return masked_loss(self.kind, y_hat, y, n_valid=n_valid)
 
     def extra_repr(self):
         return self.kind

@@ -136,3 +136,123 @@ class GraphedTrainStep:
         return self.loss
 
     replay = __call__
+
+
+class PaddedTrainStep:
+    """Training over a ``loader.PaddedDataLoader``: one collate launch and ONE graph replay per batch.
+
+    ``step(batch)`` takes a batch of the loader.  A padded batch runs the captured step -- forward under ``loader.masked_training(batch)``
+    (BatchNorm statistics over the real rows, counted on the device), the masked loss with ``n_valid`` (pad graphs contribute nothing and
+    get zero gradient rows), backward, the gradient all-reduce and the optimizer -- captured ONCE, on the first padded batch, through
+    :class:`GraphedTrainStep` over the loader's static tensors (``captures``); every padded batch, the first included, is a replay
+    (``replays``).  A batch that did not fit the loader's capacities comes as an ordinary ``Batch`` and takes the same step eagerly
+    (``eager_batches``).  ``run_epoch()`` iterates the loader and returns the batch losses (a 1-D device tensor, no host read).
+
+    ``loss``: a kind of ``evaluation.masked_loss`` ("BCEWithLogitsLoss", "L1Loss", "MSELoss", "CrossEntropyLoss"), an
+    ``evaluation.MaskedLoss``, or a callable ``loss(y_hat, y, n_valid=None)``.  ``optimizer``: ``gsn_amd.optim.Adam`` or a capturable
+    optimizer, as for GraphedTrainStep.
+
+    The warm-up steps GraphedTrainStep takes before it captures are real steps; here they do not count: parameters, buffers and the
+    optimizer's state tensors are put back afterwards (an optimizer state that did not exist before is zeroed in place, the fresh state of
+    the Adam family), so the first replay is the first step.  What is NOT put back is random-number state: with dropout the warm-up has
+    drawn masks.
+
+    Refusals are decided from the host numbers of the batch before the replay: exactly one real row in a row class that feeds a
+    train-mode BatchNorm raises the ``ValueError`` torch raises.  The model must be in training mode."""
+
+    def __init__(self, model, loader, loss, optimizer, parameters=None, warmup: int = 1, allreduce: bool = True, average: bool = True,
+                 group=None, force_allreduce: bool = False):
+        from .loader import PaddedDataLoader
+        if not isinstance(loader, PaddedDataLoader):
+            raise TypeError("PaddedTrainStep: a loader.PaddedDataLoader (batches of fixed shape in static tensors), not %s" % type(loader).__name__)
+        from . import evaluation
+        if isinstance(loss, str):
+            evaluation._kind_of(loss)
+            self._loss = lambda y_hat, y, n_valid=None, _k=loss: evaluation.masked_loss(_k, y_hat, y, n_valid=n_valid)
+        elif callable(loss):
+            self._loss = loss
+        else:
+            raise TypeError("PaddedTrainStep: loss is a loss kind, an evaluation.MaskedLoss or a callable (y_hat, y, n_valid=None)")
+        self.model, self.loader, self.optimizer = model, loader, optimizer
+        self.params = [p for g in optimizer.param_groups for p in g["params"]] if parameters is None else list(parameters)
+        self._graph_kw = dict(warmup=max(1, int(warmup)), allreduce=allreduce, average=average, group=group, force_allreduce=force_allreduce)
+        self.graphed = None
+        self._bn_rows = {}                # row class -> width of a train-mode BatchNorm it feeds (noted by the captured forward)
+        self.captures = self.replays = self.eager_batches = 0
+
+    # ---- the step, eager -------------------------------------------------------------------------------------------------------------
+    def _forward_loss(self, batch):
+        from .loader import masked_training
+        if getattr(batch, "padded", False):
+            with masked_training(batch) as bounds:
+                pred = self.model(batch)
+            for cls, b in bounds.items():
+                if b.used:
+                    self._bn_rows[cls] = int(b.used)
+            return self._loss(pred, batch.y, n_valid=batch.n_valid)
+        return self._loss(self.model(batch), batch.y)
+
+    def _eager(self, batch):
+        from . import dist as gdist
+        kw = self._graph_kw
+        self.optimizer.zero_grad(set_to_none=True)
+        loss = self._forward_loss(batch)
+        loss.backward()
+        if kw["allreduce"]:
+            gdist.allreduce_gradients(self.params, average=kw["average"], group=kw["group"], force=kw["force_allreduce"])
+        self.optimizer.step()
+        return loss.detach()
+
+    # ---- capture -----------------------------------------------------------------------------------------------------------------------
+    def _capture(self, batch):
+        model, opt = self.model, self.optimizer
+        keep = [(t, t.detach().clone()) for t in list(model.parameters()) + list(model.buffers())]
+        known = {id(t) for t, _ in keep}
+        keep += [(p, p.detach().clone()) for p in self.params if id(p) not in known]
+        keep_state = {(id(p), k): v.detach().clone() for p, st in opt.state.items() for k, v in st.items() if isinstance(v, torch.Tensor)}
+        try:
+            self.graphed = GraphedTrainStep(lambda: self._forward_loss(batch), opt, self.params, device=batch.n_valid.device, **self._graph_kw)
+        finally:
+            # put back whatever the warm-up steps moved -- also when one of them raised (a refusal inside the first forward): the steps
+            # before it must not stay applied
+            with torch.no_grad():
+                for t, v in keep:
+                    t.copy_(v)
+                for p, st in opt.state.items():
+                    for k, v in st.items():
+                        if isinstance(v, torch.Tensor):
+                            old = keep_state.get((id(p), k))
+                            v.copy_(old) if old is not None else v.zero_()
+        self.captures += 1
+
+    def _refuse(self, batch):
+        rows = {"graph": batch.num_real_graphs, "vertex": batch.num_real_nodes, "edge": batch.num_real_edges}
+        for cls, width in self._bn_rows.items():
+            if int(rows[cls]) == 1:
+                raise ValueError("Expected more than 1 value per channel when training, got input size torch.Size([1, %d])" % width)
+
+    # ---- the public loop ---------------------------------------------------------------------------------------------------------------
+    def step(self, batch):
+        if not self.model.training:
+            raise RuntimeError("PaddedTrainStep: the model is in evaluation mode (call model.train(); evaluation.GraphedEpoch is the replayed "
+                               "evaluation epoch)")
+        if not getattr(batch, "padded", False):
+            loss = self._eager(batch)
+            self.eager_batches += 1
+            return loss
+        if batch is not self.loader._batch:
+            raise ValueError("PaddedTrainStep: the padded batch of another loader (the captured step reads this loader's static tensors)")
+        self._refuse(batch)
+        if self.graphed is None:
+            self._capture(batch)
+        loss = self.graphed()
+        self.replays += 1
+        return loss
+
+    __call__ = step
+
+    def run_epoch(self):
+        """One pass over the loader; the losses of its batches in order (1-D fp32 device tensor; empty for an empty loader)."""
+        losses = [self.step(batch).clone() for batch in self.loader]
+        dev = self.loader._batch.n_valid.device
+        return torch.stack(losses) if losses else torch.empty(0, dtype=torch.float32, device=dev)

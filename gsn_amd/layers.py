@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _abi, flags, packs
+from . import _abi, _bound, flags, packs
 # The host side is split by concern -- _runtime (timers, zero arenas), _index (Codes, CSR, partitions, readouts, propagate), _caches
 # (derived-weight caches and their validation), _dense (forward dispatch of the dense stages and one-launch layers), _autograd (native
 # adjoints) -- and this module keeps the reference's classes.  The names below are what models, encoders, tests and bench.py have always
@@ -102,6 +102,8 @@ class mlp(nn.Module):
     # -- differentiable PyTorch twin (used to back-propagate through the dense stages)
     def torch_forward(self, x, upto=None, post=None):
         n = len(self.fc) if upto is None else upto
+        if (self.batch_norm and self.training) or (post is not None and post[0] is not None and post[0].training):
+            _bound.refuse("mlp.torch_forward (F.batch_norm)")
         for i in range(n):
             x = self.fc[i](x)
             if i != len(self.fc) - 1:
@@ -118,11 +120,12 @@ class mlp(nn.Module):
                 x = choose_activation(act)(x)
         return x
 
-    def forward(self, x, post=None):
+    def forward(self, x, post=None, rows=None):
+        """``rows``: the row class of ``x`` ("vertex", "edge", "graph"), named by the caller for loader.masked_training()."""
         _need_cuda(x, "mlp input")
         native = _dense_native_ok(self.stages([(x, None)], post=post))
         if torch.is_grad_enabled() and self.training and native:
-            return run_stages_autograd(self.stages([(x, None)], post=post), x.shape[0], self.training)
+            return run_stages_autograd(self.stages([(x, None)], post=post), x.shape[0], self.training, rows=rows)
         # eval mode: the fused forward; if a gradient is asked for after all, the stages are re-run on the kernels that keep what
         # their HIP adjoints need (no PyTorch twin: BatchNorm on running statistics is a per-column affine map there)
         again = (lambda x_: run_stages_autograd(self.stages([(x_, None)], post=post), x_.shape[0], self.training)) if native and not self.training \
@@ -597,10 +600,10 @@ class _SparseLayer(nn.Module):
         if flags.GATHER_CAT_TRAIN or len(tensors) > _MAX_BLOCKS:      # (the assembled-rows form: A/B switch)
             eblocks, gather = [(_GatherCatFn.apply(edge_index, n, modes, *tensors), None)], None
         if len(mf.fc) < 2:      # a single Linear as msg_fn: nothing to fold (GSN_sparse.py:166-171 with d_h = [])
-            msgs = run_stages_autograd(mf.stages(eblocks), E, True, gather=gather)
+            msgs = run_stages_autograd(mf.stages(eblocks), E, True, gather=gather, rows="edge")
             agg = propagate(0, edge_index, sel, n, b=msgs)
-            return run_stages_autograd(uf.stages([(x, None), (agg, None)], post=post), n, True)
-        r = run_stages_autograd(mf.stages(eblocks, upto=len(mf.fc) - 1), E, True, gather=gather)
+            return run_stages_autograd(uf.stages([(x, None), (agg, None)], post=post), n, True, rows="vertex")
+        r = run_stages_autograd(mf.stages(eblocks, upto=len(mf.fc) - 1), E, True, gather=gather, rows="edge")
         s_agg = propagate(0, edge_index, sel, n, b=r)
         csr = _csr_for(edge_index, sel, n)
         last, w3 = mf.fc[-1], uf.fc[0].weight
@@ -611,7 +614,7 @@ class _SparseLayer(nn.Module):
             #  as float4 -- K = d_x + d_h + 1 is odd otherwise)
             w_first = _FoldWeightsFn.apply(w3, last.weight, last.bias, d_x, 3)
             stages = uf.stages([(x, None), (s_agg, None), (csr.deg4, None)], first_weight=w_first, post=post)
-            return run_stages_autograd(stages, n, True)
+            return run_stages_autograd(stages, n, True, rows="vertex")
         else:
             # ... as two dense stages with their own adjoints (rows = W3a; no library GEMM in the step)
             w3x, w3a = w3[:, :d_x], w3[:, d_x:].contiguous()
@@ -619,7 +622,7 @@ class _SparseLayer(nn.Module):
             b_fold = run_stages_autograd([_Stage(last.bias.unsqueeze(0), None, None, "identity", [(w3a, None)])], w3a.shape[0], True)
             w_first = torch.cat([w3x, w_fold, b_fold], 1)
         stages = uf.stages([(x, None), (s_agg, None), (csr.deg, None)], first_weight=w_first, post=post)
-        return run_stages_autograd(stages, n, True)
+        return run_stages_autograd(stages, n, True, rows="vertex")
 
     def _split_edge_stage(self, x, ids, ef, csr, n, E):
         """S[t] = sum_{e -> t} act(bn(cat(x_i, x_j, z_e) W1^T + b1)) with the node columns of W1 applied once per node:
@@ -706,7 +709,7 @@ class _SparseLayer(nn.Module):
         n, sel = x.shape[0], self._sel()
         if self.ogb or self.msg_kind == "gin":
             xin = self._self_plus_messages(edge_index, x, ids, ef)
-            return self.update_fn(xin, post=post) if native else self.update_fn.torch_forward(xin, post=post)
+            return self.update_fn(xin, post=post, rows="vertex") if native else self.update_fn.torch_forward(xin, post=post)
         parts = [t if idx is None else t[idx] for t, idx in self._row(x, ids, ef).blocks(edge_index[sel], edge_index[1 - sel], None)]
         msgs = self.msg_fn.torch_forward(torch.cat(parts, -1))
         agg = propagate(0, edge_index, sel, n, b=msgs)

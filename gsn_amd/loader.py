@@ -412,6 +412,9 @@ class DataLoader:
         return ep
 
 
+from ._bound import RowBound, masked_training  # noqa: E402,F401  (the training-mode opt-in for padded batches: DESIGN.md 8f)
+
+
 # ---- padded, fixed-shape batches ----------------------------------------------------------------------------------------------------
 class PaddedShape:
     """The static shape of a padded loader: ``n_chunk`` / ``e_chunk`` (the most vertices / edge columns of a pad graph), ``node_capacity``,
@@ -483,7 +486,9 @@ def pad_pointers(sh, b, n_real_nodes, n_real_edges):
 class PaddedBatch(Batch):
     """A padded batch: ``num_graphs = G_cap`` graph slots of which the first ``num_real_graphs`` are real (``num_real_nodes`` vertices,
     ``num_real_edges`` edge columns; ``n_valid``: the same count on the device).  The tensors BELONG TO THE LOADER and are refilled by the
-    next batch: copy what must outlive it."""
+    next batch: copy what must outlive it.  Real rows are always a prefix -- vertices ``[0, N_r)``, edge columns ``[0, E_r)``, graphs
+    ``[0, b)`` -- and the three bounds are on the device (``n_valid`` = b, ``ptr[b]`` = N_r, ``graph_partition[1][b]`` = E_r): what
+    :func:`masked_training` hands to the train-mode BatchNorm kernels."""
     padded = True
 
 
@@ -566,7 +571,10 @@ class PaddedDataLoader(DataLoader):
     refilled (every byte of them is rewritten by every launch).  That is what lets a step over it be captured into a HIP graph once
     (``evaluation.GraphedEpoch``).  Hence one live iterator per loader: a second ``iter()`` while an unfinished one is alive raises
     ``RuntimeError``.  Default capacities hold every batch; with explicit smaller ones a batch that does not fit is delivered as an
-    ordinary unpadded :class:`Batch`.  For evaluation only: the models refuse a padded batch in training mode."""
+    ordinary unpadded :class:`Batch`.  The models take a padded batch in evaluation mode as it is; in training mode they refuse it (its pad
+    rows would enter the BatchNorm statistics) unless the forward runs under :func:`masked_training`, the opt-in under which BatchNorm
+    counts the real rows only (``graphs.PaddedTrainStep`` is the training loop over this loader: one collate launch and one graph replay
+    per batch)."""
 
     def __init__(self, dataset, batch_size=1, shuffle=False, drop_last=False, generator=None, node_capacity=None, edge_capacity=None, fill=None):
         super().__init__(dataset, batch_size, shuffle, drop_last, generator)

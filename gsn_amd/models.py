@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import flags, layers
+from . import _bound, flags, layers
 from .dropout import dropout as native_dropout, resolve_impl
 from .encoding import DiscreteEmbedding
 from .layers import (Codes, GSN_edge_sparse, GSN_edge_sparse_ogb, GSN_sparse, MPNN_edge_sparse, MPNN_edge_sparse_ogb, MPNN_sparse,
@@ -36,10 +36,11 @@ def _register_partition(data, edge_index):
 
 
 def _refuse_padded_training(module, data):
-    """A padded batch (loader.PaddedBatch) is for evaluation: in training mode its pad rows would enter the BatchNorm batch statistics."""
-    if module.training and getattr(data, "padded", False):
+    """A padded batch (loader.PaddedBatch) in training mode: its pad rows would enter the BatchNorm batch statistics -- unless the caller has
+    opened loader.masked_training(batch), under which every train-mode BatchNorm stage takes the statistics of its row class's real rows."""
+    if module.training and getattr(data, "padded", False) and not _bound.is_active():
         raise RuntimeError("%s: a padded batch in training mode (its pad rows would enter the BatchNorm statistics); call model.eval(), "
-                           "or train over loader.DataLoader" % type(module).__name__)
+                           "train over loader.DataLoader, or open loader.masked_training(batch)" % type(module).__name__)
 
 
 _PARAMETER_FREE_ENCODERS = ("one_hot_encoder", "atom_one_hot_encoder", "bond_one_hot_encoder")
@@ -57,7 +58,7 @@ def _codes_of(enc, t):
     return Codes(t, dims, clamp=False, check=False)
 
 
-def _encode_once(memo, enc, x, training):
+def _encode_once(memo, enc, x, training, rows=None):
     """The reference encodes ``data.identifiers`` / ``data.edge_features`` once per LAYER (models_graph_classification.py:213-223); the
     one-hot encoders have no parameters, so every layer's encoder returns the same rows: they are made once per forward.  An encoder
     with parameters is re-used only for the SAME module in eval mode (in train mode its BatchNorm statistics move with every call, as in
@@ -68,10 +69,10 @@ def _encode_once(memo, enc, x, training):
     elif not training:
         key = (id(enc), id(x))
     else:
-        return enc(x)
+        return enc(x, rows=rows)
     hit = memo.get(key)
     if hit is None:
-        hit = memo[key] = enc(x)
+        hit = memo[key] = enc(x, rows=rows)
     return hit
 
 
@@ -129,6 +130,7 @@ class GNNSubstructures(nn.Module):
         self.inject_edge_features = kwargs["inject_edge_features"]
         self.random_features = kwargs["random_features"]
         id_scope = kwargs["id_scope"]
+        self.id_rows = "edge" if id_scope == "local" else "vertex"      # the row class of data.identifiers (loader.masked_training)
         d_msg, d_out, d_h = kwargs["d_msg"], kwargs["d_out"], kwargs["d_h"]
         aggr = kwargs["aggr"] if kwargs["aggr"] is not None else "add"
         flow = kwargs["flow"] if kwargs["flow"] is not None else "target_to_source"
@@ -204,7 +206,7 @@ class GNNSubstructures(nn.Module):
 
     def forward(self, data, print_flag=False, return_intermediate=False):
         _refuse_padded_training(self, data)
-        kwargs = {"degrees": self.degree_encoder(data.degrees)}
+        kwargs = {"degrees": self.degree_encoder(data.degrees, rows="vertex")}
         memo = {}
         edge_index = data.edge_index
         _register_partition(data, edge_index)
@@ -220,7 +222,7 @@ class GNNSubstructures(nn.Module):
             ce = _codes_of(self.edge_encoder[0], data.edge_features) if hasattr(data, "edge_features") else None
             if cx is not None and ci is not None and (ce is not None or not hasattr(data, "edge_features")):
                 codes0 = (cx, ci, ce)
-        x = codes0[0] if codes0 is not None else self.input_node_encoder(data.x)
+        x = codes0[0] if codes0 is not None else self.input_node_encoder(data.x, rows="vertex")
         if self.random_features:
             r = torch.rand(size=(x.shape[0], self.r_d_out), device=x.device).float()
             x = torch.cat((x, r), 1)
@@ -229,9 +231,11 @@ class GNNSubstructures(nn.Module):
             if i == 0 and codes0 is not None:
                 kwargs["identifiers"], kwargs["edge_features"] = codes0[1], codes0[2]
             else:
-                kwargs["identifiers"] = _encode_once(memo, self.id_encoder[i] if self.inject_ids else self.id_encoder[0], data.identifiers, self.training)
+                kwargs["identifiers"] = _encode_once(memo, self.id_encoder[i] if self.inject_ids else self.id_encoder[0], data.identifiers, self.training,
+                                                     rows=self.id_rows)
                 if hasattr(data, "edge_features"):
-                    kwargs["edge_features"] = _encode_once(memo, self.edge_encoder[i] if self.inject_edge_features else self.edge_encoder[0], data.edge_features, self.training)
+                    kwargs["edge_features"] = _encode_once(memo, self.edge_encoder[i] if self.inject_edge_features else self.edge_encoder[0], data.edge_features,
+                                                           self.training, rows="edge")
                 else:
                     kwargs["edge_features"] = None
             # BatchNorm1d + activation of models_graph_classification.py:226-228 ride in the layer's last epilogue
@@ -243,7 +247,7 @@ class GNNSubstructures(nn.Module):
             if self.final_projection[i]:
                 x_global = self.global_pool(x_interm[i], data.batch)
                 jk = self.lin_proj[i]
-                y = jk(x_global) if isinstance(jk, mlp) else run_linear_module(jk, x_global)
+                y = jk(x_global, rows="graph") if isinstance(jk, mlp) else run_linear_module(jk, x_global)
                 if self.dropout_impl == "native":
                     # the jumping-knowledge sum rides in the dropout launch from the second term on (0 + y of the first term stays: -0 -> +0)
                     first = not isinstance(prediction, torch.Tensor)
@@ -278,6 +282,7 @@ class GNN_OGB(nn.Module):
         self.inject_ids = kwargs["inject_ids"]
         self.vn = kwargs["vn"]
         id_scope = kwargs["id_scope"]
+        self.id_rows = "edge" if id_scope == "local" else "vertex"      # the row class of data.identifiers (loader.masked_training)
         d_msg, d_out, d_h = kwargs["d_msg"], kwargs["d_out"], kwargs["d_h"]
         aggr = kwargs["aggr"] if kwargs["aggr"] is not None else "add"
         flow = kwargs["flow"] if kwargs["flow"] is not None else "target_to_source"
@@ -353,14 +358,14 @@ class GNN_OGB(nn.Module):
 
     def forward(self, data, return_intermediate=False):
         _refuse_padded_training(self, data)
-        kwargs = {"degrees": self.degree_encoder(data.degrees)}
+        kwargs = {"degrees": self.degree_encoder(data.degrees, rows="vertex")}
         memo = {}
         edge_index = data.edge_index
         _register_partition(data, edge_index)
         if self.vn:
             n_graphs = layers.num_graphs_of(data.batch)            # (data.batch[-1] + 1 of the reference: sorted graph ids; one read per batch)
-            vn_embedding = self.vn_encoder(torch.zeros(n_graphs, dtype=edge_index.dtype, device=edge_index.device))
-        x = self.input_node_encoder(data.x)
+            vn_embedding = self.vn_encoder(torch.zeros(n_graphs, dtype=edge_index.dtype, device=edge_index.device), rows="graph")
+        x = self.input_node_encoder(data.x, rows="vertex")
         x_interm = [x]
         n_layers = len(self.conv)
         for i in range(n_layers):
@@ -372,8 +377,9 @@ class GNN_OGB(nn.Module):
                 # relu(x_j + (id_e + e_e)): the two encoders' rows summed by one launch, one per-edge stream into the layer
                 kwargs["identifiers"], kwargs["edge_features"] = fused, None
             else:
-                kwargs["identifiers"] = _encode_once(memo, id_enc, data.identifiers, self.training)
-                kwargs["edge_features"] = _encode_once(memo, self.edge_encoder[i], data.edge_features, self.training) if hasattr(data, "edge_features") else None
+                kwargs["identifiers"] = _encode_once(memo, id_enc, data.identifiers, self.training, rows=self.id_rows)
+                kwargs["edge_features"] = (_encode_once(memo, self.edge_encoder[i], data.edge_features, self.training, rows="edge")
+                                           if hasattr(data, "edge_features") else None)
             if self.vn:
                 x_interm[i] = add_by_graph(x_interm[i], vn_embedding, data.batch)
             last = i == n_layers - 1
@@ -392,15 +398,15 @@ class GNN_OGB(nn.Module):
                 # the activation after mlp_vn rides in its last stage unless the residual form needs the raw output
                 if self.dropout_impl == "native":
                     if self.residual:
-                        vn_embedding = self.mlp_vn[i](vn_temp)
+                        vn_embedding = self.mlp_vn[i](vn_temp, rows="graph")
                         vn_embedding = native_dropout(self.activation(vn_embedding), self.dropout_features[i], self.training, vn_embedding)
                     else:
-                        vn_embedding = native_dropout(self.mlp_vn[i](vn_temp, post=(None, self.activation_name)), self.dropout_features[i], self.training)
+                        vn_embedding = native_dropout(self.mlp_vn[i](vn_temp, post=(None, self.activation_name), rows="graph"), self.dropout_features[i], self.training)
                 elif self.residual:
-                    vn_embedding = self.mlp_vn[i](vn_temp)
+                    vn_embedding = self.mlp_vn[i](vn_temp, rows="graph")
                     vn_embedding = vn_embedding + F.dropout(self.activation(vn_embedding), self.dropout_features[i], training=self.training)
                 else:
-                    vn_embedding = F.dropout(self.mlp_vn[i](vn_temp, post=(None, self.activation_name)),
+                    vn_embedding = F.dropout(self.mlp_vn[i](vn_temp, post=(None, self.activation_name), rows="graph"),
                                              self.dropout_features[i], training=self.training)
         prediction = 0
         for i in range(n_layers + 1):

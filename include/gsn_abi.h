@@ -922,6 +922,34 @@ int gsn_bn_finalize_count_hip(int64_t n_cols, int64_t m_rows, double eps, double
                               float *shift, int64_t *num_batches_tracked, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * The same bookkeeping and the BatchNorm adjoint over a PADDED batch (gsn_loader_collate_padded_hip), whose real rows are the prefix
+ * [0, v) of the m_rows rows the stage runs over.  A row bound is (n_valid int64 [1], row_ptr int64 [n_slots + 1] or NULL, n_slots):
+ *     v = clamp(row_ptr ? row_ptr[clamp(*n_valid, 0, n_slots)] : *n_valid, 0, m_rows)
+ * read ON THE DEVICE by every kernel (n_slots = 0 with a NULL row_ptr); no device value causes a read outside row_ptr.  The host m_rows
+ * (the capacity) only sizes launches and buffers, as in gsn_eval_accumulate_counted_hip.
+ *
+ * gsn_bn_finalize_bounded_hip stands in for gsn_bn_finalize_count_hip (one launch): stats = the [2][C] sums over ALL m_rows rows as the
+ * product kernels leave them, h = the materialised pre-BN rows fp32 [m_rows, C].  The sums of the shorter of the row ranges [0, v) and
+ * [v, m_rows) are taken from h -- directly, or subtracted from stats in fp64 -- so at most half the rows are read; then the vectors and
+ * the running statistics follow with count v through the expressions of gsn_bn_finalize_count_hip (v == m_rows: the same bits).
+ * v == 0: mean 0, invstd 1, scale 1, shift 0, running statistics untouched, the batch counted.  v == 1: variance 0, invstd
+ * 1 / sqrt(eps), finite (the caller refuses that batch as torch does).  scratch: gsn_bn_finalize_bounded_scratch_bytes(n_cols) bytes,
+ * 8-byte aligned, ZERO-FILLED by the caller before every call (fp64 partial sums and one ticket per 64 columns).
+ *
+ * gsn_bn_act_bwd_from_h_bounded_hip is gsn_bn_act_bwd_from_h_hip with the column sums over the rows < v, the divisor v, grad_bias over
+ * the rows < v, and grad_h rows >= v written as +0 WITHOUT reading grad_y there (products over all m_rows rows then add exact zeros).
+ * ---------------------------------------------------------------------------------------------------------------- */
+int64_t gsn_bn_finalize_bounded_scratch_bytes(int64_t n_cols);
+int gsn_bn_finalize_bounded_hip(int64_t n_cols, int64_t m_rows, double eps, double momentum, const double *stats, const float *h,
+                                const int64_t *n_valid, const int64_t *row_ptr, int64_t n_slots, void *scratch, const float *gamma,
+                                const float *beta, float *running_mean, float *running_var, float *mean, float *invstd, float *scale,
+                                float *shift, int64_t *num_batches_tracked, void *stream);
+int gsn_bn_act_bwd_from_h_bounded_hip(int64_t m_rows, int64_t n_cols, const float *grad_y, const float *h, const float *mean,
+                                      const float *invstd, const float *coef, const float *shift, int train_bn, int act, double *sums,
+                                      float *grad_h, double *grad_bias, const int64_t *n_valid, const int64_t *row_ptr, int64_t n_slots,
+                                      void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Directional GSN aggregation (directional_gsn/nets/dgn_layer.py:30-56, nets/aggregators.py, nets/scalers.py).
  * For each node v, over its in-edges e = (u -> v) in edge-id order (the target-sorted CSR of edge_index[1]: seg_ptr [N+1],
  * perm [E] edge ids stable by target, src [E] = edge_index[0][perm]), with message h[u] (fp32 [N, d]) and vector field
@@ -1037,6 +1065,14 @@ int gsn_masked_loss_fwd_hip(int kind, int64_t rows, int64_t cols, const float *y
                             void *scratch, int64_t scratch_bytes, void *stream);
 int gsn_masked_loss_bwd_hip(int kind, int64_t rows, int64_t cols, const float *y_hat, const void *y, const float *grad_loss,
                             const int64_t *count, float *grad_y_hat, void *stream);
+/* The same two launches with the row count READ FROM DEVICE MEMORY (a padded batch): rows >= v = clamp(*n_valid, 0, rows) are unlabelled
+ * whatever they hold (integer pad targets of GSN_LOSS_CE are 0, not NaN) and are not read; loss, count and the gradient of the first v
+ * rows are the bits of the entries above called with rows = v, gradient rows >= v are +0.  The host `rows` picks the launch shape and the
+ * scratch size (gsn_masked_loss_scratch_bytes(kind, rows, cols)). */
+int gsn_masked_loss_fwd_counted_hip(int kind, int64_t rows, int64_t cols, const float *y_hat, const void *y, const int64_t *n_valid,
+                                    float *loss, int64_t *count, void *scratch, int64_t scratch_bytes, void *stream);
+int gsn_masked_loss_bwd_counted_hip(int kind, int64_t rows, int64_t cols, const float *y_hat, const void *y, const int64_t *n_valid,
+                                    const float *grad_loss, const int64_t *count, float *grad_y_hat, void *stream);
 
 /* One batch of an evaluation epoch (train_test_funcs.py:193-202 and :234-251 per batch, without their .item() / .cpu()), in the launches
  * of the masked loss: the batch loss through the same device functions and partition (the same bits), then

@@ -67,6 +67,11 @@ def main():
                     help="after the steps, one evaluation epoch (evaluation.test_ogb, ROC-AUC) over --eval-graphs molhiv-shaped graphs: eager over "
                          "gsn_amd.loader.DataLoader, or padded over PaddedDataLoader (one collate launch + one HIP-graph replay per batch)")
     ap.add_argument("--eval-graphs", type=int, default=1024)
+    ap.add_argument("--loader", default="static", choices=["static", "native", "padded"],
+                    help="static: one batch built by hand, every step on it; native: eager steps over the batches of a device-resident "
+                         "gsn_amd.loader.DataLoader of --loader-graphs molhiv-shaped graphs (20 %% NaN labels, masked loss); padded: the same batches "
+                         "in the static tensors of a PaddedDataLoader, the whole step replayed as one HIP graph per batch (graphs.PaddedTrainStep)")
+    ap.add_argument("--loader-graphs", type=int, default=512)
     args = ap.parse_args()
     rank, world, local = (int(os.environ.get(k, d)) for k, d in (("RANK", "0"), ("WORLD_SIZE", "1"), ("LOCAL_RANK", "0")))
     torch.cuda.set_device(local)
@@ -113,6 +118,62 @@ def evaluate(args, model, d_id, dev, rank=0):
     dt = time.perf_counter() - t0
     model.train()
     return {"loader": args.eval, "graphs": G, "batches": len(loader), "ms_per_batch": round(dt / len(loader) * 1e3, 4), "loss": loss, "rocauc": auc}
+
+
+def dataset_graphs(n_graphs, d_id, seed):
+    """``n_graphs`` molhiv-shaped graphs as a list of Data: random atom / bond / identifier codes within the model's feature dims, one 0 / 1
+    label per graph of which 20 % are NaN (the set ``evaluate`` draws too)"""
+    from gsn_amd.data import Data
+    b = synth.zinc_shape_batch(n_graphs, seed=seed, mean_n=25.5, sd_n=8.0, n_min=4, n_max=60)
+    rng = np.random.default_rng(seed)
+    x = np.stack([rng.integers(0, k, b.num_nodes) for k in encoding.ATOM_FEATURE_DIMS], 1)
+    ef = np.stack([rng.integers(0, k, b.num_edges) for k in encoding.BOND_FEATURE_DIMS], 1)
+    ids = np.stack([rng.integers(0, k, b.num_edges) for k in d_id], 1)
+    y = rng.integers(0, 2, (n_graphs, 1, 1)).astype(np.float32)
+    y[rng.random((n_graphs, 1, 1)) < 0.2] = np.nan
+    graphs = []
+    for g in range(n_graphs):
+        n0, n1, e0, e1 = int(b.node_ptr[g]), int(b.node_ptr[g + 1]), int(b.edge_ptr[g]), int(b.edge_ptr[g + 1])
+        graphs.append(Data(edge_index=torch.from_numpy(b.edge_index[:, e0:e1] - n0), x=torch.from_numpy(x[n0:n1]), degrees=torch.zeros(n1 - n0),
+                           edge_features=torch.from_numpy(ef[e0:e1]), y=torch.from_numpy(y[g]), identifiers=torch.from_numpy(ids[e0:e1])))
+    return graphs
+
+
+def loader_step(args, model, params, opt, dev, rank):
+    """``--loader native`` / ``padded``: the whole step over the next batch of a shuffled loader (a new epoch when one runs out).  native: eager,
+    masked loss; padded: graphs.PaddedTrainStep -- forward under loader.masked_training, counted loss, backward, all-reduce and optimizer
+    replayed as ONE HIP graph per batch.  -> (step, mean N, mean E per batch)"""
+    from gsn_amd.evaluation import masked_loss
+    from gsn_amd.graphs import PaddedTrainStep
+    from gsn_amd.loader import DataLoader, DeviceDataset, PaddedDataLoader
+    ds = DeviceDataset(dataset_graphs(max(int(args.loader_graphs), args.batch), model.identifier_dims, 700 + rank), device=dev)
+    gen = torch.Generator()
+    gen.manual_seed(rank)
+    padded = args.loader == "padded"
+    loader = (PaddedDataLoader if padded else DataLoader)(ds, batch_size=args.batch, shuffle=True, drop_last=True, generator=gen)
+    state = {"it": iter(loader)}
+
+    def next_batch():
+        batch = next(state["it"], None)
+        if batch is None:
+            state["it"] = iter(loader)
+            batch = next(state["it"])
+        return batch
+
+    if padded:
+        padded_step = PaddedTrainStep(model, loader, "BCEWithLogitsLoss", opt, params, warmup=max(1, args.warmup))
+        step = lambda: padded_step.step(next_batch())
+    else:
+        def step():
+            batch = next_batch()
+            opt.zero_grad(set_to_none=True)
+            loss = masked_loss("BCEWithLogitsLoss", model(batch), batch.y)
+            loss.backward()
+            gdist.allreduce_gradients(params, average=True)
+            opt.step()
+            return loss
+    per_batch = args.batch / max(len(ds), 1)
+    return step, int(ds.host_sizes("x").sum() * per_batch), int(ds.host_sizes("edge_index").sum() * per_batch)
 
 
 def build(args, dev, rank=0, dropout=0.5):
@@ -178,7 +239,12 @@ def run(args, dev, dist=None, rank=0, world=1):
         opt.step()
         return loss
 
-    if getattr(args, "graph", False):
+    which = getattr(args, "loader", "static")
+    if which != "static":
+        if getattr(args, "graph", False):
+            raise SystemExit("--graph replays the static batch; --loader padded is the replayed step over a loader")
+        step, N, E = loader_step(args, model, params, opt, dev, rank)
+    elif getattr(args, "graph", False):
         from gsn_amd.graphs import GraphedTrainStep
         step = GraphedTrainStep(loss_of, opt, params, warmup=max(1, args.warmup))
     for _ in range(args.warmup):
@@ -197,15 +263,15 @@ def run(args, dev, dist=None, rank=0, world=1):
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    extra = {}
+    extra = {} if which == "static" else {"loader": which}
     if getattr(args, "eval", "none") != "none":
         extra["eval"] = evaluate(args, model, model.identifier_dims, dev, rank)
     return {**extra, "workload": "molhiv-shaped GNN_OGB training step (%d layers, d=%d, vn), batch %d graphs/GPU (N=%d, E=%d)" % (L, dm, args.batch, N, E),
             "n_gpus": world, "graphs_per_s": round(world * args.batch * args.steps / dt, 1),
             "ms_per_step": round(dt / args.steps * 1e3, 3), "parameters": n_params,
             "grad_bucket_MB": round(n_params * 4 / 1e6, 2), "loss": float(loss.item()),
-            "launch": "hip_graph" if getattr(args, "graph", False) else "eager", "optimizer": getattr(args, "optimizer", "sgd"),
-            "loss_fn": getattr(args, "loss", "bce"), "dropout": model.dropout_impl,
+            "launch": "hip_graph" if (getattr(args, "graph", False) or which == "padded") else "eager", "optimizer": getattr(args, "optimizer", "sgd"),
+            "loss_fn": getattr(args, "loss", "bce") if which == "static" else "masked", "dropout": model.dropout_impl,
             "note": "forward and backward on HIP kernels (native adjoints of every stage, DESIGN.md 4); SGD update and glue in PyTorch"}
 
 

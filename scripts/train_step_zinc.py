@@ -5,6 +5,7 @@ data parallel with one flat RCCL gradient all-reduce per step.  Forward and back
 
     python scripts/train_step_zinc.py [--batch 128] [--steps 20]
     python scripts/train_step_zinc.py --loader native          # eager steps over batches of a device-resident DataLoader (gsn_amd.loader)
+    python scripts/train_step_zinc.py --loader padded          # the same batches padded to one shape: collate launch + ONE graph replay per step
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 scripts/train_step_zinc.py"""
 import argparse
 import json
@@ -22,11 +23,11 @@ from gsn_amd import dist as gdist, encoding, models, synth  # noqa: E402
 from gsn_amd.counting import CountPlan, count_batch  # noqa: E402
 
 
-def native_loader(args, dev, rank, plan):
+def native_loader(args, dev, rank, plan, padded=False):
     """``--loader native``: a prepared ZINC-shaped dataset of ``--loader-graphs`` graphs on the device and a shuffled DataLoader over it
-    (gsn_amd.loader: one HIP launch per batch).  -> (loader, d_id)"""
+    (gsn_amd.loader: one HIP launch per batch); ``padded``: a PaddedDataLoader, every batch in one set of static tensors.  -> (loader, d_id)"""
     from gsn_amd.data import Data
-    from gsn_amd.loader import DataLoader, DeviceDataset
+    from gsn_amd.loader import DataLoader, DeviceDataset, PaddedDataLoader
     b = synth.zinc_shape_batch(max(args.loader_graphs, args.batch), seed=200 + rank)
     ids, _ = count_batch(plan, b.node_ptr, b.edge_ptr, torch.from_numpy(b.edge_index), ids_are_global=True, device=dev)
     codes, d_id = encoding.unique_codes(ids)
@@ -40,13 +41,16 @@ def native_loader(args, dev, rank, plan):
                            y=torch.from_numpy(rng.standard_normal(1).astype(np.float32)), identifiers=codes[e0:e1].clone()))
     gen = torch.Generator()
     gen.manual_seed(rank)
-    return DataLoader(DeviceDataset(graphs, device=dev), batch_size=args.batch, shuffle=True, drop_last=True, generator=gen), d_id
+    cls = PaddedDataLoader if padded else DataLoader
+    return cls(DeviceDataset(graphs, device=dev), batch_size=args.batch, shuffle=True, drop_last=True, generator=gen), d_id
 
 
 def build(args, dev, rank=0):
     """(model, data, params, optimizer, loss closure, N, E) of the step."""
     if getattr(args, "loader", "static") == "native":
         return build_native(args, dev, rank)
+    if getattr(args, "loader", "static") == "padded":
+        return build_padded(args, dev, rank)
     b = synth.zinc_shape_batch(args.batch, seed=200 + rank)
     N, E = b.num_nodes, b.num_edges
     plan = CountPlan.get([list(nx.cycle_graph(k).edges) for k in range(3, 7)], "edge", False)
@@ -89,6 +93,29 @@ def build_native(args, dev, rank):
     return model, None, params, opt, loss_of, int(sizes("x").sum() * per_batch), int(sizes("edge_index").sum() * per_batch)
 
 
+def build_padded(args, dev, rank):
+    """``--loader padded``: the batches of ``--loader native`` padded to one shape (gsn_amd.loader.PaddedDataLoader) and the whole step --
+    forward under loader.masked_training, counted loss, backward, all-reduce, optimizer -- replayed as ONE HIP graph per batch
+    (gsn_amd.graphs.PaddedTrainStep).  The "loss closure" returned here IS the step: run() calls nothing around it."""
+    from gsn_amd.graphs import PaddedTrainStep
+    plan = CountPlan.get([list(nx.cycle_graph(k).edges) for k in range(3, 7)], "edge", False)
+    loader, d_id = native_loader(args, dev, rank, plan, padded=True)
+    model, params, opt = make_model(args, dev, d_id)
+    padded_step = PaddedTrainStep(model, loader, "L1Loss", opt, params, warmup=max(1, getattr(args, "warmup", 1)))
+    state = {"it": iter(loader)}
+
+    def step():
+        batch = next(state["it"], None)
+        if batch is None:
+            state["it"] = iter(loader)
+            batch = next(state["it"])
+        return padded_step.step(batch)
+
+    sizes = loader.dataset.host_sizes
+    per_batch = args.batch / max(len(loader.dataset), 1)
+    return model, None, params, opt, step, int(sizes("x").sum() * per_batch), int(sizes("edge_index").sum() * per_batch)
+
+
 def make_model(args, dev, d_id):
     L, d = 4, 128
     act = getattr(args, "activation", "relu")      # (the tests of replay == eager use elu: no ReLU kink for last-bit noise to flip)
@@ -126,7 +153,10 @@ def run(args, dev, dist=None, rank=0, world=1):
         opt.step()
         return loss
 
-    if getattr(args, "graph", False):
+    padded = getattr(args, "loader", "static") == "padded"
+    if padded:
+        step = loss_of          # (build_padded: the replayed step itself)
+    elif getattr(args, "graph", False):
         from gsn_amd.graphs import GraphedTrainStep
         step = GraphedTrainStep(loss_of, opt, params, warmup=max(1, args.warmup))
     for _ in range(args.warmup):
@@ -149,7 +179,7 @@ def run(args, dev, dist=None, rank=0, world=1):
     res = ({"workload": "ZINC-shaped GNNSubstructures training step (4 x GSN_edge_sparse general d=128), batch %d graphs/GPU (N=%d, E=%d)" % (args.batch, N, E),
             "n_gpus": world, "graphs_per_s": round(world * args.batch * args.steps / dt, 1),
             "ms_per_step": round(dt / args.steps * 1e3, 3), "parameters": n_params, "loss": float(loss.item()),
-            "launch": "hip_graph" if getattr(args, "graph", False) else "eager", "optimizer": getattr(args, "optimizer", "sgd")})
+            "launch": "hip_graph" if (getattr(args, "graph", False) or padded) else "eager", "optimizer": getattr(args, "optimizer", "sgd")})
     if getattr(args, "loader", "static") != "static":
         res["loader"] = args.loader          # (N, E of the workload line: the dataset's mean per batch)
     return res
@@ -162,9 +192,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--graph", action="store_true", help="replay the whole step as one HIP graph (gsn_amd.graphs.GraphedTrainStep)")
     ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adam", "adam_native"])
-    ap.add_argument("--loader", default="static", choices=["static", "native"],
-                    help="static: one batch built by hand, every step on it; native: batches of a device-resident gsn_amd.loader.DataLoader")
-    ap.add_argument("--loader-graphs", type=int, default=1024, help="graphs of the dataset behind --loader native")
+    ap.add_argument("--loader", default="static", choices=["static", "native", "padded"],
+                    help="static: one batch built by hand, every step on it; native: batches of a device-resident gsn_amd.loader.DataLoader; "
+                         "padded: the same batches in the static tensors of a PaddedDataLoader, the step replayed as one HIP graph per batch")
+    ap.add_argument("--loader-graphs", type=int, default=1024, help="graphs of the dataset behind --loader native / padded")
     ap.add_argument("--dropout", default=None, choices=["torch", "native"],
                     help="native: gsn_amd.dropout on the jumping-knowledge projections (default: GSN_DROPOUT, else torch)")
     ap.add_argument("--dropout-p", type=float, default=0.0, help="dropout probability of the projections (the reference's run uses none)")
