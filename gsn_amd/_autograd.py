@@ -6,18 +6,193 @@ import torch
 
 from . import _abi, _bound, flags
 from ._caches import _note_cache
-from ._dense import _Stage, _block_array, _bn_resolve, _f16x3_takes, _linear_hip
+from ._dense import _Stage, _block_array, _bn_batch_vectors, _bn_eval_vectors, _bn_resolve, _f16x3_takes, _linear_hip
 from ._index import _csr_for, propagate
 from ._runtime import _ACT_CODE, _f32c, _timed, _zeros
 
-# ------------------------------------------------------------------------------------------------------------------
-# native backward of dense stage lists (inputs = plain row-major blocks): gsn_bn_act_bwd_hip, gsn_wgrad_hip and the
-# forward linear kernel on W^T for the input gradient
-# ------------------------------------------------------------------------------------------------------------------
+# native backward of dense stage lists (inputs = plain row-major blocks): gsn_bn_act_bwd_hip, gsn_wgrad_hip and the forward linear kernel
+# on W^T for the input gradient
+PLAIN, AFFINE, BN_BATCH, BN_RUNNING = range(4)
+_BN_ROWS = (BN_BATCH, BN_RUNNING)
 
 
-def _transposed(w):
+class _StageRec:
+    """One ``Linear (+BatchNorm) (+activation)`` stage of a _DenseStagesFn call, built once per call by ``_layout``.
+
+    ``kind``: PLAIN; AFFINE (BatchNorm on its running statistics, gamma / beta frozen: a per-column affine map in the epilogue of the product);
+    BN_BATCH (batch statistics: train mode, or no running statistics); BN_RUNNING (running statistics with gradients for gamma / beta).  The
+    last two materialise their pre-BN rows.  ``w_i, b_i, g_i, beta_i``: the positions of weight, bias, gamma and beta in ``tensors`` (blocks of
+    stage 0, then per stage weight, [bias], [gamma, beta]; None: the stage has none).  ``act``: the activation's code.
+
+    What forward kept for the adjoint, as indices into ``ctx.saved_tensors`` (None: not kept): ``h`` the pre-BN rows, ``y`` the fp32 output
+    (None on a BatchNorm stage: the output was written as fp16 planes only), ``mean, invstd, scale, shift`` the BatchNorm vectors (AFFINE:
+    ``scale`` alone).  ``x_scratch``: the forward product's row scratch (the fp16 planes of the stage's input rows, kept when the weight
+    wants a gradient and the product ran on the fp16x3 kernel: gsn_wgrad_f16x3_hip multiplies it with the planes of gH) -- held here and NOT
+    given to save_for_backward: saved-tensor hooks never saw it."""
+    __slots__ = ("kind", "bn", "act", "n_out", "k_total", "w_i", "b_i", "g_i", "beta_i", "h", "y", "mean", "invstd", "scale", "shift", "x_scratch")
+
+    def __init__(self, st, tensors):
+        put = lambda t: tensors.append(t) or len(tensors) - 1
+        bn = st.bn
+        self.bn, self.act = bn, _ACT_CODE[st.act]
+        self.n_out, self.k_total = st.weight.shape
+        if bn is None or bn.training or bn.running_mean is None:
+            self.kind = PLAIN if bn is None else BN_BATCH
+        else:
+            self.kind = BN_RUNNING if bn.affine and (bn.weight.requires_grad or bn.bias.requires_grad) else AFFINE
+        self.w_i = put(st.weight)
+        self.b_i = None if st.bias is None else put(st.bias)
+        self.g_i, self.beta_i = (put(bn.weight), put(bn.bias)) if bn is not None and bn.affine else (None, None)
+        self.h = self.y = self.mean = self.invstd = self.scale = self.shift = self.x_scratch = None
+
+
+def _layout(stages):
+    """``(records, tensors)`` of a stage list, the one walk of the tensor positions: the ``records[0].w_i`` blocks of stage 0, then what each record puts."""
+    tensors = [d for d, _ in stages[0].blocks]
+    return [_StageRec(st, tensors) for st in stages], tensors
+
+
+# --- route decisions: each stated once -------------------------------------------------------------------------------
+def _plane_rows(n_out, ptr):
+    """Can a BatchNorm pass write rows of this width at this address as fp16 planes (a row scratch of the fp16x3 kernel) instead of fp32 rows?"""
+    return n_out % 4 == 0 and n_out <= 640 and ptr % 16 == 0
+
+
+def _output_as_planes(rec, nxt, want_w_next, m_rows, h):
+    """The stage output only feeds the next product (on the fp16x3 kernel) and, in the backward pass, that product's plane weight gradient:
+    BatchNorm + activation write the row scratch of Y -- no fp32 Y, no pre-pass over it (gsn_bn_act_planes_hip)."""
+    return (flags.BN_ACT_PLANES and nxt is not None and _plane_rows(rec.n_out, h.data_ptr()) and flags.WGRAD_F16X3 and want_w_next
+            and _f16x3_takes(m_rows, nxt.n_out, [rec.n_out], stats=nxt.kind == BN_BATCH))
+
+
+def _gh_as_planes(rec, bound, want_w, need_x, m_rows, g, h):
+    """A BatchNorm stage whose gH is read as fp16 planes only -- by the input-gradient product on the fp16x3 kernel (or by nobody) and by the
+    plane weight gradient: the adjoint pass writes gH's row scratch and no fp32 gH (gsn_bn_act_bwd_planes_hip).  Not under a bound: there fp32
+    gH with +0 pad rows, split by gsn_linear_f16x3_split_rows_hip where wanted."""
+    return (bound is None and flags.BN_BWD_PLANES and rec.kind in _BN_ROWS and want_w and rec.x_scratch is not None and _plane_rows(rec.n_out, g.data_ptr())
+            and (not need_x or _f16x3_takes(m_rows, rec.k_total, [rec.n_out], aligned=h.data_ptr() % 16 == 0)))
+
+
+def _split_gh_alone(rec, xs, g_scr, gh, m_rows):
+    """No input-gradient product on the fp16x3 kernel left the planes of gH beside the weight gradient: a pre-pass of its own makes them."""
+    return xs is not None and not g_scr and rec.n_out % 4 == 0 and gh is not None and gh.data_ptr() % 16 == 0 and m_rows >= flags.WGRAD_F16X3_SPLIT_ROWS
+
+
+def _fused_finalize_act(bound, m_rows):
+    """Finalize + normalise + activate in one launch, where a launch costs more than the pass (never under a bound: the bounded finalize has no such form)."""
+    return bound is None and 1 < m_rows <= flags.FUSE_BN_ACT_ROWS
+
+
+def _weight_transposed(w, m_rows):
+    """W as the input-gradient product gX = gH W reads it.  The fp16x3 kernel prepares its planes from any strides; the bf16x6 kernel stages a
+    strided W with scalar loads -- fine where a launch costs more than the staging (small batches), a copy + float4 staging above."""
+    if w.shape[1] > flags.LINEAR_F16X3_MIN_N or m_rows <= 16384:
+        return w.detach().t()
     return w.detach().to(torch.float32).t().contiguous()
+
+
+# --- the steps of a stage --------------------------------------------------------------------------------------------
+def _bn_vectors(rec, h, stats, m_rows, bound):
+    """Statistics -> vectors of a BatchNorm stage: ``([mean, scale, shift], invstd, y)``, ``y`` the stage output where the finalize launch wrote it too."""
+    y = None
+    if rec.kind == BN_BATCH:
+        fused = _fused_finalize_act(bound, m_rows)
+        y = torch.empty_like(h) if fused else None
+        params, invstd = _bn_batch_vectors(rec.bn, h.device, lambda: stats, m_rows, True, fuse_act=(h, rec.act, y) if fused else None, bound=bound,
+                                           h=h if bound is not None else None)
+    else:
+        params, invstd = _bn_eval_vectors(rec.bn)
+    return [_f32c(v) for v in params], invstd.contiguous(), y
+
+
+def _normalise(rec, as_planes, h, vecs, m_rows):
+    """act(bn(h)) as a launch of its own: ``(y, None)``, or ``(None, row scratch of y)`` when the output goes to planes only."""
+    L = _abi.lib()
+    head = (m_rows, rec.n_out, h.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(), vecs[2].data_ptr(), rec.act)
+    with _abi.device_guard(h.device), _timed("bn_act", 8.0 * h.numel()):
+        if as_planes:
+            planes = torch.empty(int(L.gsn_linear_f16x3_scratch_bytes(m_rows, rec.n_out)), dtype=torch.uint8, device=h.device)
+            _abi.check(L.gsn_bn_act_planes_hip(*head, None, planes.data_ptr(), _abi.current_stream()), "gsn_bn_act_planes_hip")
+            return None, planes
+        y = torch.empty_like(h)
+        _abi.check(L.gsn_bn_act_hip(*head, y.data_ptr(), _abi.current_stream()), "gsn_bn_act_hip")
+        return y, None
+
+
+def _bn_act_adjoint(rec, kept, g, gbias, sums, bound, m_rows, as_planes):
+    """gY -> gH through the activation and the BatchNorm of a stage; the column sums for gamma / beta go to ``sums``, the bias gradient to
+    ``gbias``.  Returns ``(gH, None)``, or ``(None, row scratch of gH)``.  BatchNorm stages take the activation's derivative from z
+    recomputed out of the pre-BN rows (the stage output is not read again); the others read the stage output."""
+    L = _abi.lib()
+    n_out, dev = rec.n_out, g.device
+    gh = None if as_planes else torch.empty((m_rows, n_out), dtype=torch.float32, device=dev)
+    gh_scratch = None
+    with _abi.device_guard(dev), _timed("bn_act_bwd", 16.0 * m_rows * n_out):
+        if rec.kind in _BN_ROWS:
+            head = (kept[rec.h].data_ptr(), kept[rec.mean].data_ptr(), kept[rec.invstd].data_ptr(), kept[rec.scale].data_ptr(),
+                    kept[rec.shift].data_ptr(), 1 if rec.kind == BN_BATCH else 2, rec.act, sums.data_ptr())
+            if as_planes:
+                gh_scratch = torch.empty(int(L.gsn_linear_f16x3_scratch_bytes(m_rows, n_out)), dtype=torch.uint8, device=dev)
+                name, tail = "gsn_bn_act_bwd_planes_hip", (gh_scratch.data_ptr(), gbias.data_ptr())
+            elif bound is not None:
+                name, tail = "gsn_bn_act_bwd_from_h_bounded_hip", (gh.data_ptr(), gbias.data_ptr(), *bound.pointers())
+            else:
+                name, tail = "gsn_bn_act_bwd_from_h_hip", (gh.data_ptr(), gbias.data_ptr())
+        else:
+            name, tail = "gsn_bn_act_bwd_hip", (gh.data_ptr(), gbias.data_ptr())
+            head = (kept[rec.y].data_ptr(), None, None, None, None if rec.scale is None else kept[rec.scale].data_ptr(), 0, rec.act, None)
+        rc = getattr(L, name)(m_rows, n_out, g.data_ptr(), *head, *tail, _abi.current_stream())
+    _abi.check(rc, name)
+    return gh, gh_scratch
+
+
+def _input_rows(prev, kept, blocks0, m_rows):
+    """The fp32 input rows of the stage behind ``prev`` (None: stage 0's blocks); where ``prev`` wrote planes only, made again from its pre-BN rows."""
+    if prev is None:
+        return blocks0
+    if prev.y is not None:
+        return [kept[prev.y]]
+    h = kept[prev.h]
+    y = torch.empty_like(h)
+    with _abi.device_guard(h.device):
+        _abi.check(_abi.lib().gsn_bn_act_hip(m_rows, h.shape[1], h.data_ptr(), kept[prev.mean].data_ptr(), kept[prev.scale].data_ptr(),
+                                             kept[prev.shift].data_ptr(), prev.act, y.data_ptr(), _abi.current_stream()), "gsn_bn_act_hip")
+    return [y]
+
+
+def _weight_gradient(rec, gw, gh, xs, g_scr, xin_rows, gather, m_rows):
+    """gW = gH^T X into the zero-filled ``gw``: the plane kernel on the two row scratches (``g_scr``: gH's, if a product or the adjoint left
+    it; ``xs``: the forward product's), else gsn_wgrad_hip on fp32 rows -- ``xin_rows()`` makes them, gathered blocks read where they lie."""
+    L = _abi.lib()
+    dev, n_out, k_total = gw.device, rec.n_out, rec.k_total
+    if _split_gh_alone(rec, xs, g_scr, gh, m_rows):
+        sc = torch.empty(int(L.gsn_linear_f16x3_scratch_bytes(m_rows, n_out)), dtype=torch.uint8, device=dev)
+        one = _block_array([(gh, None)], [])
+        with _abi.device_guard(dev):
+            _abi.check(L.gsn_linear_f16x3_split_rows_hip(m_rows, 1, one, sc.data_ptr(), _abi.current_stream()), "gsn_linear_f16x3_split_rows_hip")
+        g_scr.append(sc)
+    if xs is not None and g_scr:
+        with _abi.device_guard(dev), _timed("wgrad", 2.0 * m_rows * n_out * k_total):
+            _abi.check(L.gsn_wgrad_f16x3_hip(m_rows, n_out, k_total, g_scr[0].data_ptr(), xs.data_ptr(), gw.data_ptr(), _abi.current_stream()),
+                       "gsn_wgrad_f16x3_hip")
+        return
+    xin = xin_rows()
+    keep = []
+    modes = [None] * len(xin) if gather is None else gather[2]
+    arr = _block_array([(t, None if m is None else gather[0][m]) for t, m in zip(xin, modes)], keep)
+    with _abi.device_guard(dev), _timed("wgrad", 2.0 * m_rows * n_out * k_total):
+        _abi.check(L.gsn_wgrad_hip(m_rows, n_out, gh.data_ptr(), len(xin), arr, gw.data_ptr(), _abi.current_stream()), "gsn_wgrad_hip")
+
+
+def _block_gradients(grads, blocks0, wants, gather, gx):
+    """gX of stage 0 handed to its blocks: column slices; for a block gathered through edge_index[mode] the per-edge gradients summed per vertex."""
+    o = 0
+    for bi, t in enumerate(blocks0):
+        wd = t.shape[1]
+        if wants[bi]:
+            mode = None if gather is None else gather[2][bi]
+            grads[bi] = gx[:, o:o + wd] if mode is None else _segment_sum_cols(gather[0], mode, gather[1], gx, o, wd)
+        o += wd
 
 
 class _DenseStagesFn(torch.autograd.Function):
@@ -25,270 +200,109 @@ class _DenseStagesFn(torch.autograd.Function):
     statistics of train-mode BatchNorm stages).  Backward: per stage  gY -> gH (BN + activation adjoint) -> gW, gb, gX."""
 
     @staticmethod
-    def forward(ctx, spec, *tensors):
-        # spec: list of dicts {n_blocks, has_bias, bn (module or None), act};  tensors: blocks of stage 0, then per stage
-        # weight, [bias], [gamma, beta]
-        it = iter(tensors)
-        blocks0 = [next(it) for _ in range(spec[0]["n_blocks"])]
-        # gathered stage-0 blocks (the x_i / x_j / per-end-point blocks of an edge stage): read where they lie through edge_index[mode],
-        # by the forward product AND by the weight gradient -- no assembled [E, K] copy of the rows
-        gather = spec[0].get("gather")
+    def forward(ctx, recs, gather, bound, *tensors):
+        # recs, tensors: _layout of the stage list.  gather = (edge_index, n_nodes, modes) or None: the stage-0 blocks (the x_i / x_j /
+        # per-end-point blocks of an edge stage) are read where they lie through edge_index[mode], by the forward product AND by the weight
+        # gradient -- no assembled [E, K] copy of the rows.  bound: a _bound.RowBound or None (the rows are a padded batch, BatchNorm
+        # statistics over its real rows only)
+        wants = ctx.needs_input_grad[3:]
+        blocks0 = tensors[:recs[0].w_i]
         if gather is not None:
-            g_ei, g_n, g_modes = gather
-            idx0 = [None if m is None else g_ei[m] for m in g_modes]
-            m_rows = g_ei.shape[1]
+            idx0 = [None if m is None else gather[0][m] for m in gather[2]]
+            m_rows = gather[0].shape[1]
         else:
             idx0 = [None] * len(blocks0)
             m_rows = blocks0[0].shape[0]
-        bound = spec[0].get("bound")      # (a _bound.RowBound: the rows are a padded batch, BatchNorm statistics over its real rows only)
-        saved, meta = [], []
-        y = None
-        # per stage: the forward product's row scratch (fp16 planes of the stage's input rows), kept when the weight wants a gradient and the
-        # product ran on the fp16x3 kernel -- the backward pass multiplies it with the planes of gH (gsn_wgrad_f16x3_hip)
-        x_scratch = []
-        presplit_next, y_shape, y_dropped = None, None, set()
-        w_pos = spec[0]["n_blocks"]
-        for si, sp in enumerate(spec):
-            scr = [] if (flags.WGRAD_F16X3 and ctx.needs_input_grad[1 + w_pos] and (si > 0 or gather is None)) else None
-            w_pos += 1 + (1 if sp["has_bias"] else 0) + (2 if (sp["bn"] is not None and sp["bn"].affine) else 0)
-            # rows split already by the stage before (gsn_bn_act_planes_hip): the product without its pre-pass; `y_shape` stands in for the rows
-            pre, presplit_next = presplit_next, None
-            w = next(it)
-            b = next(it) if sp["has_bias"] else None
-            bn = sp["bn"]
-            gamma = beta = None
-            if bn is not None and bn.affine:
-                gamma, beta = next(it), next(it)
-            blks = [(t, ix) for t, ix in zip(blocks0, idx0)] if si == 0 else [(y if pre is None else y_shape, None)]
-            n_out = w.shape[0]
-            bn_train = bn is not None and (bn.training or bn.running_mean is None)
-            bn_affine_grad = bn is not None and bn.affine and (bn.weight.requires_grad or bn.bias.requires_grad)
-            if bn is not None and not bn_train and not bn_affine_grad:
-                # BatchNorm on its running statistics, gamma / beta frozen: a per-column affine map in the epilogue of the product
-                st = _Stage(w, b, bn, sp["act"])
-                _bn_resolve(st, None, m_rows, False)
-                mean32, scale, shift = st.bn_params
-                y = _linear_hip(blks, w, b, mean32, scale, shift, _ACT_CODE[sp["act"]], m_rows, scratch_out=scr, presplit=pre)
-                saved += [y, _f32c(scale)]
-                meta.append(("affine", len(saved) - 2))
-            elif bn is not None:
-                # batch statistics (train mode), or running statistics with gradients for gamma / beta: pre-BN rows materialised
-                st = _Stage(w, b, bn, sp["act"])
-                fused_act = False
-                if bn_train:
-                    stats = _zeros(2 * n_out, torch.float64, w.device).view(2, n_out)
-                    h = _linear_hip(blks, w, b, None, None, None, 0, m_rows, out=True, stats=stats, scratch_out=scr, presplit=pre)
-                    # (under a bound: the bounded finalize, then the normalise + activation pass over all rows as a launch of its own)
-                    fused_act = bound is None and 1 < m_rows <= flags.FUSE_BN_ACT_ROWS
-                    yy = torch.empty_like(h) if fused_act else None
-                    _bn_resolve(st, lambda: stats, m_rows, True, fuse_act=(h, _ACT_CODE[sp["act"]], yy) if fused_act else None, bound=bound,
-                                h=h if bound is not None else None)
-                else:
-                    h = _linear_hip(blks, w, b, None, None, None, 0, m_rows, out=True, scratch_out=scr, presplit=pre)
-                    yy = None
-                    _bn_resolve(st, None, m_rows, False)
-                mean32, scale, shift = st.bn_params
-                vecs = [_f32c(v) for v in (mean32, scale, shift)]
-                if not fused_act:
-                    # the stage output only feeds the next product (on the fp16x3 kernel) and, in the backward pass, that product's plane weight
-                    # gradient: BatchNorm + activation write the row scratch of Y -- no fp32 Y, no pre-pass over it (gsn_bn_act_planes_hip)
-                    to_planes = False
-                    if flags.BN_ACT_PLANES and si + 1 < len(spec) and n_out % 4 == 0 and n_out <= 640 and h.data_ptr() % 16 == 0 and m_rows > 0:
-                        nsp, n_next = spec[si + 1], tensors[w_pos].shape[0]
-                        nbn = nsp["bn"]
-                        next_stats = nbn is not None and (nbn.training or nbn.running_mean is None)
-                        to_planes = (flags.WGRAD_F16X3 and ctx.needs_input_grad[1 + w_pos]
-                                     and _f16x3_takes(m_rows, n_next, [n_out], aligned=h.data_ptr() % 16 == 0, stats=next_stats))
-                    with _abi.device_guard(h.device), _timed("bn_act", 8.0 * h.numel()):
-                        if to_planes:
-                            presplit_next = torch.empty(int(_abi.lib().gsn_linear_f16x3_scratch_bytes(m_rows, n_out)), dtype=torch.uint8, device=h.device)
-                            _abi.check(_abi.lib().gsn_bn_act_planes_hip(m_rows, n_out, h.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(), vecs[2].data_ptr(),
-                                                                        _ACT_CODE[sp["act"]], None, presplit_next.data_ptr(), _abi.current_stream()),
-                                       "gsn_bn_act_planes_hip")
-                            y_shape = h
-                            y_dropped.add(si)
-                        else:
-                            yy = torch.empty_like(h)
-                            _abi.check(_abi.lib().gsn_bn_act_hip(m_rows, n_out, h.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(),
-                                                                 vecs[2].data_ptr(), _ACT_CODE[sp["act"]], yy.data_ptr(),
-                                                                 _abi.current_stream()), "gsn_bn_act_hip")
-                invstd = st.bn_invstd
-                saved += [h, h if yy is None else yy, vecs[0], invstd.contiguous(), vecs[1], vecs[2]]      # (no fp32 Y: h keeps its slot)
-                meta.append(("bn" if bn_train else "bn_eval", len(saved) - 6))
-                y = yy
-            else:
-                y = _linear_hip(blks, w, b, None, None, None, _ACT_CODE[sp["act"]], m_rows, scratch_out=scr, presplit=pre)
-                saved += [y]
-                meta.append(("plain", len(saved) - 1))
-            if pre is not None and scr is not None and not scr:
+        kept = []
+        keep = lambda t: kept.append(t) or len(kept) - 1
+        y = rows = pre = None      # the output; the next stage's input rows (where planes only: a stand-in of their shape); their row scratch
+        for si, rec in enumerate(recs):
+            nxt = recs[si + 1] if si + 1 < len(recs) else None
+            w, b = tensors[rec.w_i], None if rec.b_i is None else tensors[rec.b_i]
+            scr = [] if (flags.WGRAD_F16X3 and wants[rec.w_i] and (si > 0 or gather is None)) else None
+            blks = list(zip(blocks0, idx0)) if si == 0 else [(rows, None)]
+            # the product: with the epilogue of a PLAIN / AFFINE stage, or plain pre-BN rows (with their column statistics on batch statistics)
+            stats = _zeros(2 * rec.n_out, torch.float64, w.device).view(2, rec.n_out) if rec.kind == BN_BATCH else None
+            epilogue = _bn_eval_vectors(rec.bn)[0] if rec.kind == AFFINE else (None, None, None)
+            out = _linear_hip(blks, w, b, *epilogue, 0 if rec.kind in _BN_ROWS else rec.act, m_rows, out=True, stats=stats, scratch_out=scr, presplit=pre)
+            if pre is not None and scr is not None and not scr:      # (rows split already by the stage before: that scratch is this product's)
                 scr.append(pre)
-            x_scratch.append(scr[0] if scr else None)
-        ctx.spec, ctx.meta, ctx.m_rows = spec, meta, m_rows
-        ctx.x_scratch = x_scratch
-        ctx.y_dropped = y_dropped
-        ctx.bound = bound
-        ctx.n_saved = len(saved)
-        ctx.save_for_backward(*saved, *tensors)
+            rec.x_scratch = scr[0] if scr else None
+            pre = None
+            if rec.kind in _BN_ROWS:
+                vecs, invstd, y = _bn_vectors(rec, out, stats, m_rows, bound)
+                if y is None:
+                    y, pre = _normalise(rec, _output_as_planes(rec, nxt, nxt is not None and wants[nxt.w_i], m_rows, out), out, vecs, m_rows)
+                rec.h = keep(out)
+                rec.y = None if y is None else keep(y)
+                rec.mean, rec.invstd, rec.scale, rec.shift = keep(vecs[0]), keep(invstd), keep(vecs[1]), keep(vecs[2])
+                rows = out if y is None else y
+            else:
+                y = rows = out
+                rec.y = keep(y)
+                if rec.kind == AFFINE:
+                    rec.scale = keep(_f32c(epilogue[1]))
+        ctx.recs, ctx.gather, ctx.bound, ctx.m_rows, ctx.n_kept = recs, gather, bound, m_rows, len(kept)
+        ctx.save_for_backward(*kept, *tensors)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        spec, meta, m_rows = ctx.spec, ctx.meta, ctx.m_rows
-        allt = ctx.saved_tensors
-        saved, tensors = allt[:ctx.n_saved], allt[ctx.n_saved:]
-        L = _abi.lib()
-        # locate the per-stage tensors again
-        pos = spec[0]["n_blocks"]
-        blocks0 = list(tensors[:pos])
-        per = []
-        for sp in spec:
-            ent = {"w": tensors[pos], "w_i": pos}
-            pos += 1
-            if sp["has_bias"]:
-                ent["b_i"] = pos; pos += 1
-            if sp["bn"] is not None and sp["bn"].affine:
-                ent["g"] = tensors[pos]; ent["g_i"] = pos; ent["beta_i"] = pos + 1; pos += 2
-            per.append(ent)
+        recs, gather, m_rows = ctx.recs, ctx.gather, ctx.m_rows
+        kept = ctx.saved_tensors
+        tensors = kept[ctx.n_kept:]
+        wants = ctx.needs_input_grad[3:]
+        blocks0 = list(tensors[:recs[0].w_i])
         grads = [None] * len(tensors)
         dev = gy.device
         g = gy.to(torch.float32).contiguous()
         # every zero-initialised accumulator of this backward from two arenas (one fill each instead of three small fills per stage)
-        n64 = sum(3 * ent["w"].shape[0] for ent in per)
-        n32 = sum(ent["w"].numel() for si, ent in enumerate(per) if ctx.needs_input_grad[1 + ent["w_i"]])
-        z64 = _zeros(n64, torch.float64, dev)
-        z32 = _zeros(n32, torch.float32, dev)
+        z64 = _zeros(sum(3 * rec.n_out for rec in recs), torch.float64, dev)
+        z32 = _zeros(sum(rec.n_out * rec.k_total for rec in recs if wants[rec.w_i]), torch.float32, dev)
         o64 = o32 = 0
         casts = []
-        for si in range(len(spec) - 1, -1, -1):
-            sp, ent = spec[si], per[si]
-            kind, off = meta[si]
-            w = ent["w"]
-            n_out, k_total = w.shape
-            gbias = z64[o64:o64 + n_out]
-            sums_z = z64[o64 + n_out:o64 + 3 * n_out].view(2, n_out)
-            o64 += 3 * n_out
-            act = _ACT_CODE[sp["act"]]
-            # a BatchNorm stage whose gH is read as fp16 planes only -- by the input-gradient product on the fp16x3 kernel (or by nobody) and by the
-            # plane weight gradient: the adjoint pass writes gH's row scratch and no fp32 gH (gsn_bn_act_bwd_planes_hip)
-            need_x = si > 0 or any(ctx.needs_input_grad[1 + bi] for bi in range(len(blocks0)))
-            want_w = ctx.needs_input_grad[1 + ent["w_i"]]
-            # (under a bound the plane-writing adjoint is not used: fp32 gH with +0 pad rows, split by gsn_linear_f16x3_split_rows_hip where wanted)
-            bound = ctx.bound if kind in ("bn", "bn_eval") else None
-            planes_only = (bound is None and flags.BN_BWD_PLANES and kind in ("bn", "bn_eval") and want_w and ctx.x_scratch[si] is not None and n_out % 4 == 0 and n_out <= 640
-                           and g.data_ptr() % 16 == 0 and (not need_x or _f16x3_takes(m_rows, k_total, [n_out], aligned=saved[off].data_ptr() % 16 == 0)))
-            gh = None if planes_only else torch.empty((m_rows, n_out), dtype=torch.float32, device=dev)
-            gh_scratch = None
-            with _abi.device_guard(dev), _timed("bn_act_bwd", 16.0 * m_rows * n_out):
-                if planes_only:
-                    h, y, mean32, invstd, scale, shift = saved[off:off + 6]
-                    sums = sums_z
-                    gh_scratch = torch.empty(int(L.gsn_linear_f16x3_scratch_bytes(m_rows, n_out)), dtype=torch.uint8, device=dev)
-                    rc = L.gsn_bn_act_bwd_planes_hip(m_rows, n_out, g.data_ptr(), h.data_ptr(), mean32.data_ptr(), invstd.data_ptr(), scale.data_ptr(),
-                                                     shift.data_ptr(), 1 if kind == "bn" else 2, act, sums.data_ptr(), gh_scratch.data_ptr(),
-                                                     gbias.data_ptr(), _abi.current_stream())
-                elif bound is not None:
-                    h, y, mean32, invstd, scale, shift = saved[off:off + 6]
-                    sums = sums_z
-                    nv, rp, ns = bound.pointers()
-                    rc = L.gsn_bn_act_bwd_from_h_bounded_hip(m_rows, n_out, g.data_ptr(), h.data_ptr(), mean32.data_ptr(), invstd.data_ptr(),
-                                                             scale.data_ptr(), shift.data_ptr(), 1 if kind == "bn" else 2, act, sums.data_ptr(),
-                                                             gh.data_ptr(), gbias.data_ptr(), nv, rp, ns, _abi.current_stream())
-                elif kind in ("bn", "bn_eval"):
-                    h, y, mean32, invstd, scale, shift = saved[off:off + 6]
-                    sums = sums_z
-                    # (the activation's derivative from z recomputed out of the pre-BN rows: the stage output is not read again)
-                    rc = L.gsn_bn_act_bwd_from_h_hip(m_rows, n_out, g.data_ptr(), h.data_ptr(), mean32.data_ptr(), invstd.data_ptr(),
-                                                     scale.data_ptr(), shift.data_ptr(), 1 if kind == "bn" else 2, act, sums.data_ptr(),
-                                                     gh.data_ptr(), gbias.data_ptr(), _abi.current_stream())
-                elif kind == "affine":
-                    y, scale = saved[off:off + 2]
-                    sums = None
-                    rc = L.gsn_bn_act_bwd_hip(m_rows, n_out, g.data_ptr(), y.data_ptr(), None, None, None, scale.data_ptr(), 0, act, None,
-                                              gh.data_ptr(), gbias.data_ptr(), _abi.current_stream())
-                else:
-                    y = saved[off]
-                    sums = None
-                    rc = L.gsn_bn_act_bwd_hip(m_rows, n_out, g.data_ptr(), y.data_ptr(), None, None, None, None, 0, act, None,
-                                              gh.data_ptr(), gbias.data_ptr(), _abi.current_stream())
-            _abi.check(rc, "gsn_bn_act_bwd_planes_hip" if planes_only else "gsn_bn_act_bwd_hip")
+        for si in range(len(recs) - 1, -1, -1):
+            rec = recs[si]
+            n_out = rec.n_out
+            gbias, sums = z64[o64:o64 + n_out], z64[o64 + n_out:o64 + 3 * n_out].view(2, n_out)
             # (fp64 column sums -> fp32 gradients: ONE conversion of the whole arena behind the loop, the gradients are its slices)
-            o0 = o64 - 3 * n_out
-            if kind in ("bn", "bn_eval") and "g_i" in ent:
-                casts.append((ent["g_i"], o0 + 2 * n_out, n_out))
-                casts.append((ent["beta_i"], o0 + n_out, n_out))
-            if "b_i" in ent:
-                casts.append((ent["b_i"], o0, n_out))
+            if rec.kind in _BN_ROWS and rec.g_i is not None:
+                casts += [(rec.g_i, o64 + 2 * n_out, n_out), (rec.beta_i, o64 + n_out, n_out)]
+            if rec.b_i is not None:
+                casts.append((rec.b_i, o64, n_out))
+            o64 += 3 * n_out
+            need_x = si > 0 or any(wants[:len(blocks0)])
+            want_w = wants[rec.w_i]
+            bound = ctx.bound if rec.kind in _BN_ROWS else None
+            h = kept[rec.h] if rec.kind in _BN_ROWS else None
+            as_planes = _gh_as_planes(rec, bound, want_w, need_x, m_rows, g, h)
+            gh, gh_scratch = _bn_act_adjoint(rec, kept, g, gbias, sums, bound, m_rows, as_planes)
             # input gradient first: on the fp16x3 kernel its row pre-pass leaves the fp16 planes of gH, which the weight gradient multiplies as well
-            xs = ctx.x_scratch[si] if want_w else None
+            xs = rec.x_scratch if want_w else None
             g_scr = [] if xs is not None else None
             gx = None
             if need_x:
-                # gX = gH W: W read as its transpose.  The fp16x3 kernel prepares its planes from any strides; the bf16x6 kernel stages a
-                # strided W with scalar loads -- fine where a launch costs more than the staging (small batches), a copy + float4 staging above
-                wt = w.detach().t() if (w.shape[1] > flags.LINEAR_F16X3_MIN_N or m_rows <= 16384) else _transposed(w)
-                if planes_only:         # (the rows are split already; `h` stands in for gH's shape)
-                    gx = _linear_hip([(saved[off], None)], wt, None, None, None, None, 0, m_rows, split_k=True, presplit=gh_scratch)
+                wt = _weight_transposed(tensors[rec.w_i], m_rows)
+                if as_planes:         # (the rows are split already; `h` stands in for gH's shape)
+                    gx = _linear_hip([(h, None)], wt, None, None, None, None, 0, m_rows, split_k=True, presplit=gh_scratch)
                 else:
                     gx = _linear_hip([(gh, None)], wt, None, None, None, None, 0, m_rows, split_k=True, scratch_out=g_scr)
-            if planes_only:
+            if as_planes:
                 g_scr.append(gh_scratch)
-            # weight gradient
-            def xin_rows():
-                if si == 0:
-                    return blocks0
-                poff = meta[si - 1][1]
-                if (si - 1) in ctx.y_dropped:      # (the stage output was written as planes only: the fp32 rows again, from the pre-BN rows)
-                    ph, _, pmean, _, pscale, pshift = saved[poff:poff + 6]
-                    yy = torch.empty_like(ph)
-                    with _abi.device_guard(dev):
-                        _abi.check(L.gsn_bn_act_hip(m_rows, ph.shape[1], ph.data_ptr(), pmean.data_ptr(), pscale.data_ptr(), pshift.data_ptr(),
-                                                    _ACT_CODE[spec[si - 1]["act"]], yy.data_ptr(), _abi.current_stream()), "gsn_bn_act_hip")
-                    return [yy]
-                return [saved[poff + (1 if meta[si - 1][0] in ("bn", "bn_eval") else 0)]]
             if want_w:
-                gw = z32[o32:o32 + n_out * k_total].view(n_out, k_total)
-                o32 += n_out * k_total
-                if xs is not None and not g_scr and n_out % 4 == 0 and gh is not None and gh.data_ptr() % 16 == 0 and m_rows >= flags.WGRAD_F16X3_SPLIT_ROWS:
-                    # no input-gradient product on the fp16x3 kernel beside it: the planes of gH from the pre-pass alone
-                    sc = torch.empty(int(L.gsn_linear_f16x3_scratch_bytes(m_rows, n_out)), dtype=torch.uint8, device=dev)
-                    one = _block_array([(gh, None)], [])
-                    with _abi.device_guard(dev):
-                        _abi.check(L.gsn_linear_f16x3_split_rows_hip(m_rows, 1, one, sc.data_ptr(), _abi.current_stream()), "gsn_linear_f16x3_split_rows_hip")
-                    g_scr.append(sc)
-                if xs is not None and g_scr:
-                    with _abi.device_guard(dev), _timed("wgrad", 2.0 * m_rows * n_out * k_total):
-                        _abi.check(L.gsn_wgrad_f16x3_hip(m_rows, n_out, k_total, g_scr[0].data_ptr(), xs.data_ptr(), gw.data_ptr(), _abi.current_stream()),
-                                   "gsn_wgrad_f16x3_hip")
-                else:
-                    xin = xin_rows()
-                    keep = []
-                    gather = spec[0].get("gather") if si == 0 else None
-                    modes = [None] * len(xin) if gather is None else gather[2]
-                    arr = _block_array([(t, None if m is None else gather[0][m]) for t, m in zip(xin, modes)], keep)
-                    with _abi.device_guard(dev), _timed("wgrad", 2.0 * m_rows * n_out * k_total):
-                        _abi.check(L.gsn_wgrad_hip(m_rows, n_out, gh.data_ptr(), len(xin), arr, gw.data_ptr(), _abi.current_stream()),
-                                   "gsn_wgrad_hip")
-                grads[ent["w_i"]] = gw
-            if need_x:
-                if si > 0:
-                    g = gx
-                else:
-                    gather = spec[0].get("gather")
-                    o = 0
-                    for bi, t in enumerate(blocks0):
-                        wd = t.shape[1]
-                        if ctx.needs_input_grad[1 + bi]:
-                            mode = None if gather is None else gather[2][bi]
-                            if mode is None:
-                                grads[bi] = gx[:, o:o + wd]
-                            else:       # rows gathered through edge_index[mode]: the per-edge gradients summed per vertex (the propagate kernel)
-                                grads[bi] = _segment_sum_cols(gather[0], mode, gather[1], gx, o, wd)
-                        o += wd
+                gw = grads[rec.w_i] = z32[o32:o32 + n_out * rec.k_total].view(n_out, rec.k_total)
+                o32 += n_out * rec.k_total
+                _weight_gradient(rec, gw, gh, xs, g_scr, lambda: _input_rows(recs[si - 1] if si else None, kept, blocks0, m_rows),
+                                 gather if si == 0 else None, m_rows)
+            if si > 0:
+                g = gx
+            elif need_x:
+                _block_gradients(grads, blocks0, wants, gather, gx)
         if casts:
             c32 = z64.to(torch.float32)
             for gi, o0, n in casts:
                 grads[gi] = c32[o0:o0 + n]
-        return (None,) + tuple(grads)
+        return (None, None, None) + tuple(grads)
 
 
 def _segment_sum_cols(edge_index, mode, n_nodes, rows, col0, width):
@@ -367,20 +381,10 @@ def run_stages_autograd(stages, m_rows, training, gather=None, rows=None):
     bound = None
     if _bound.is_active() and any(st.bn is not None for st in stages):      # (column sums over rows: batch statistics, or gamma / beta gradients)
         bound = _bound.active(rows, "run_stages_autograd")
-    spec, tensors = [], []
-    tensors += [d for d, _ in stages[0].blocks]
-    for i, st in enumerate(stages):
-        spec.append({"n_blocks": len(st.blocks) if i == 0 else 0, "has_bias": st.bias is not None, "bn": st.bn, "act": st.act})
-        if i == 0 and gather is not None and any(m is not None for m in gather[2]):
-            spec[0]["gather"] = gather
-        if i == 0 and bound is not None:
-            spec[0]["bound"] = bound
-        tensors.append(st.weight)
-        if st.bias is not None:
-            tensors.append(st.bias)
-        if st.bn is not None and st.bn.affine:
-            tensors += [st.bn.weight, st.bn.bias]
-    return _DenseStagesFn.apply(spec, *tensors)
+    if gather is not None and not any(m is not None for m in gather[2]):
+        gather = None
+    recs, tensors = _layout(stages)
+    return _DenseStagesFn.apply(recs, gather, bound, *tensors)
 
 
 def _transposed_weight(lin):

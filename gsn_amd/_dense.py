@@ -297,7 +297,7 @@ def _layer_fused(x, csr, edge_stages, node_stages, training, owner=None, gen=0, 
     if len(node_stages[0].blocks) != 1 or node_stages[1].blocks:     # ([x | S | deg]: S and deg are produced inside the kernel)
         return None
     for st in stages:
-        _bn_resolve(st, None, 0, False)
+        st.bn_params, st.bn_invstd = _bn_eval_vectors(st.bn)
     # `keep`: the weights and BatchNorm vectors, what a recorded launch keeps; this call's rows and indices only live through the call
     keep, rows = [], []
     eb = edge_stages[0].blocks
@@ -433,105 +433,100 @@ def _rows_forward(x, csr, ge, g0, g1, d_x, prep, fl):
     return out
 
 
-def _bn_resolve(stage, stats_fn, m_rows, training, fuse_act=None, bound=None, h=None):
-    """Fill stage.bn_params = (mean, scale, shift).  Train mode: batch statistics from a statistics pass (fp64 column
-    sums), running statistics updated exactly like nn.BatchNorm1d.  ``bound`` (a _bound.RowBound, with the materialised pre-BN rows ``h``): the
-    rows are a padded batch and the statistics are those of its real rows, counted on the device (gsn_bn_finalize_bounded_hip)."""
-    bn = stage.bn
+def _bn_eval_vectors(bn):
+    """``((mean, scale, shift), invstd)`` of a BatchNorm1d on its running statistics (``(None, None)`` without a module): they depend only on the
+    module's buffers / parameters -> cached on their versions and pointers."""
     if bn is None:
-        stage.bn_params = None
-        return
-    if training or bn.running_mean is None:
-        if bound is None:
-            _bound.refuse("_bn_resolve without a bound")      # (under masked_training no statistic is silently taken over all rows)
-        elif training and bound.host_rows == 1:
-            raise ValueError("Expected more than 1 value per channel when training, got input size torch.Size([1, %d])" % bn.num_features)
-        if training and m_rows == 1 and bound is None:
-            raise ValueError("Expected more than 1 value per channel when training, got input size torch.Size([%d, %d])" % (m_rows, bn.num_features))
-        if m_rows == 0:
-            # no rows (an edge-less batch in front of an edge stage): nn.BatchNorm1d returns the empty tensor, leaves the running statistics
-            # alone and still counts the batch; the vectors below are never applied to a row
-            n_out, dev = bn.num_features, stage.weight.device
-            if training and bn.track_running_stats and bn.num_batches_tracked is not None:
-                bn.num_batches_tracked += 1             # (an ordinary in-place op: the version counter moves with it eagerly ...)
-                if flags.RAW_WRITTEN is not None:              # (... and a replay of the captured add must move it too)
-                    flags.RAW_WRITTEN.append(bn.num_batches_tracked)
-            vec = torch.zeros((4, n_out), dtype=torch.float32, device=dev)
-            vec[1:3] = 1.0
-            stage.bn_params = (vec[0], vec[2], vec[3])
-            stage.bn_invstd = vec[1]
-            return
-        stats = stats_fn()
-        n_out = stats.shape[1]
-        dev = stats.device
-        vec = torch.empty((4, n_out), dtype=torch.float32, device=dev)       # mean, invstd, scale, shift
-        track = training and bn.track_running_stats and bn.running_mean is not None
-        mom = 0.0
-        nbt = None
-        if track:
-            if bn.momentum is not None and bn.num_batches_tracked.is_cuda and bn.num_batches_tracked.dtype == torch.int64:
-                mom, nbt = bn.momentum, bn.num_batches_tracked      # (the counter is incremented by the finalize kernel)
-            else:
-                bn.num_batches_tracked += 1
-                mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
-        gamma = _f32c(bn.weight) if bn.affine else None
-        beta = _f32c(bn.bias) if bn.affine else None
-        v0, v1, v2, v3 = vec.unbind(0)           # (the four rows: one call, and their addresses by arithmetic -- this runs per BatchNorm per step)
-        p0 = vec.data_ptr()
-        with _abi.device_guard(dev):
-            if bound is not None:
-                # (the launch that stands where gsn_bn_finalize_count_hip stands; its scratch -- fp64 partials and tickets -- from the zero arena)
-                if fuse_act is not None or h is None:
-                    raise RuntimeError("_bn_resolve: a row bound goes with the materialised pre-BN rows and no fused activation pass")
-                bound.used = bn.num_features     # (noted for the host-side refusal of a single real row before a replay)
-                L = _abi.lib()
-                scratch = _zeros((int(L.gsn_bn_finalize_bounded_scratch_bytes(n_out)) + 7) // 8, torch.float64, dev)
-                nv, rp, ns = bound.pointers()
-                rc = L.gsn_bn_finalize_bounded_hip(n_out, m_rows, float(bn.eps), float(mom), stats.data_ptr(), h.data_ptr(), nv, rp, ns, scratch.data_ptr(),
-                                                   _abi.ptr(gamma), _abi.ptr(beta), bn.running_mean.data_ptr() if track else None,
-                                                   bn.running_var.data_ptr() if track else None, p0, p0 + 4 * n_out, p0 + 8 * n_out, p0 + 12 * n_out,
-                                                   _abi.ptr(nbt), _abi.current_stream())
-            elif fuse_act is not None:
-                # (h, act code, out): the normalise + activate pass rides the same launch (flags.FUSE_BN_ACT_ROWS: where a launch costs more than it)
-                fh, fact, fout = fuse_act
-                rc = _abi.lib().gsn_bn_finalize_act_hip(n_out, m_rows, float(bn.eps), float(mom), stats.data_ptr(), _abi.ptr(gamma), _abi.ptr(beta),
-                                                        bn.running_mean.data_ptr() if track else None, bn.running_var.data_ptr() if track else None,
-                                                        p0, p0 + 4 * n_out, p0 + 8 * n_out, p0 + 12 * n_out, _abi.ptr(nbt),
-                                                        fh.data_ptr(), int(fact), fout.data_ptr(), _abi.current_stream())
-            else:
-                rc = _abi.lib().gsn_bn_finalize_count_hip(n_out, m_rows, float(bn.eps), float(mom), stats.data_ptr(), _abi.ptr(gamma), _abi.ptr(beta),
-                                                          bn.running_mean.data_ptr() if track else None, bn.running_var.data_ptr() if track else None,
-                                                          p0, p0 + 4 * n_out, p0 + 8 * n_out, p0 + 12 * n_out,
-                                                          _abi.ptr(nbt), _abi.current_stream())
-        _abi.check(rc, "gsn_bn_finalize_bounded_hip" if bound is not None else "gsn_bn_finalize_act_hip" if fuse_act is not None else "gsn_bn_finalize_count_hip")
-        if track:
-            # the kernel wrote the running statistics (and the counter) through raw pointers: PyTorch's version counters, on which the
-            # eval-mode vectors of this module are cached, have to move with them (no launch); a step being captured into a graph notes
-            # the tensors so that every REPLAY can do the same (gsn_amd.graphs.GraphedTrainStep)
-            touched = [bn.running_mean, bn.running_var] + ([nbt] if nbt is not None else [])
-            torch.autograd.graph.increment_version(touched)
-            if flags.RAW_WRITTEN is not None:
-                flags.RAW_WRITTEN.extend(touched)
-        stage.bn_params = (v0, v2, v3)
-        stage.bn_invstd = v1
-        return
-    else:
-        # eval mode: the three vectors depend only on the module's buffers / parameters -> cached on their versions
-        key = (bn.running_mean._version, bn.running_var._version, bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-               (bn.weight._version, bn.bias._version, bn.weight.data_ptr(), bn.bias.data_ptr()) if bn.affine else None)
-        hit = getattr(bn, "_gsn_eval_cache", None)
-        if hit is not None and hit[0] == key:
-            stage.bn_params = hit[1]
-            stage.bn_invstd = hit[2]
-            return
-        mean32 = bn.running_mean
+        return None, None
+    key = (bn.running_mean._version, bn.running_var._version, bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
+           (bn.weight._version, bn.bias._version, bn.weight.data_ptr(), bn.bias.data_ptr()) if bn.affine else None)
+    hit = getattr(bn, "_gsn_eval_cache", None)
+    if hit is None or hit[0] != key:
         invstd = torch.rsqrt(bn.running_var.to(torch.float64) + bn.eps).to(torch.float32)
         scale = invstd * bn.weight.detach() if bn.affine else invstd
         shift = bn.bias.detach() if bn.affine else torch.zeros_like(invstd)
-        stage.bn_params = (mean32.contiguous(), scale.contiguous(), shift.contiguous())
-        stage.bn_invstd = invstd.contiguous()
-        bn._gsn_eval_cache = (key, stage.bn_params, stage.bn_invstd)
+        hit = (key, (bn.running_mean.contiguous(), scale.contiguous(), shift.contiguous()), invstd.contiguous())
+        bn._gsn_eval_cache = hit
         _note_cache(bn, "_gsn_eval_cache")
+    return hit[1], hit[2]
+
+
+def _bn_no_rows(bn, dev, training):
+    """No rows (an edge-less batch in front of an edge stage): nn.BatchNorm1d returns the empty tensor, leaves the running statistics alone and
+    still counts the batch; the identity vectors returned are never applied to a row."""
+    if training and bn.track_running_stats and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked += 1             # (an ordinary in-place op: the version counter moves with it eagerly ...)
+        if flags.RAW_WRITTEN is not None:              # (... and a replay of the captured add must move it too)
+            flags.RAW_WRITTEN.append(bn.num_batches_tracked)
+    vec = torch.zeros((4, bn.num_features), dtype=torch.float32, device=dev)
+    vec[1:3] = 1.0
+    return (vec[0], vec[2], vec[3]), vec[1]
+
+
+def _bn_batch_vectors(bn, dev, stats_fn, m_rows, training, fuse_act=None, bound=None, h=None):
+    """``((mean, scale, shift), invstd)`` of a BatchNorm1d on batch statistics: fp64 column sums from ``stats_fn()`` (a statistics pass) finalised
+    on the device, the running statistics updated exactly like nn.BatchNorm1d.  ``fuse_act = (h, act code, out)``: the normalise + activate pass
+    rides the same launch (flags.FUSE_BN_ACT_ROWS: where a launch costs more than it).  ``bound`` (a _bound.RowBound, with the materialised
+    pre-BN rows ``h``): the rows are a padded batch and the statistics are those of its real rows, counted on the device."""
+    if bound is None:
+        _bound.refuse("_bn_resolve without a bound")      # (under masked_training no statistic is silently taken over all rows)
+    elif training and bound.host_rows == 1:
+        raise ValueError("Expected more than 1 value per channel when training, got input size torch.Size([1, %d])" % bn.num_features)
+    if training and m_rows == 1 and bound is None:
+        raise ValueError("Expected more than 1 value per channel when training, got input size torch.Size([%d, %d])" % (m_rows, bn.num_features))
+    if m_rows == 0:
+        return _bn_no_rows(bn, dev, training)
+    stats = stats_fn()
+    n_out, dev = stats.shape[1], stats.device
+    vec = torch.empty((4, n_out), dtype=torch.float32, device=dev)       # mean, invstd, scale, shift
+    track = training and bn.track_running_stats and bn.running_mean is not None
+    mom, nbt = 0.0, None
+    if track:
+        if bn.momentum is not None and bn.num_batches_tracked.is_cuda and bn.num_batches_tracked.dtype == torch.int64:
+            mom, nbt = bn.momentum, bn.num_batches_tracked      # (the counter is incremented by the finalize kernel)
+        else:
+            bn.num_batches_tracked += 1
+            mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+    gamma, beta = (_f32c(bn.weight), _f32c(bn.bias)) if bn.affine else (None, None)
+    v0, v1, v2, v3 = vec.unbind(0)           # (the four rows: one call, and their addresses by arithmetic -- this runs per BatchNorm per step)
+    p0 = vec.data_ptr()
+    # the three finalize entries share their arguments: (head, [rows and bound], vectors, [fused activation pass], stream)
+    L = _abi.lib()
+    head = (n_out, m_rows, float(bn.eps), float(mom), stats.data_ptr())
+    name, rows, fused = "gsn_bn_finalize_count_hip", (), ()
+    with _abi.device_guard(dev):
+        if bound is not None:
+            # (the launch that stands where gsn_bn_finalize_count_hip stands; its scratch -- fp64 partials and tickets -- from the zero arena)
+            if fuse_act is not None or h is None:
+                raise RuntimeError("_bn_resolve: a row bound goes with the materialised pre-BN rows and no fused activation pass")
+            bound.used = bn.num_features     # (noted for the host-side refusal of a single real row before a replay)
+            scratch = _zeros((int(L.gsn_bn_finalize_bounded_scratch_bytes(n_out)) + 7) // 8, torch.float64, dev)
+            name, rows = "gsn_bn_finalize_bounded_hip", (h.data_ptr(), *bound.pointers(), scratch.data_ptr())
+        elif fuse_act is not None:
+            fh, fact, fout = fuse_act
+            name, fused = "gsn_bn_finalize_act_hip", (fh.data_ptr(), int(fact), fout.data_ptr())
+        rc = getattr(L, name)(*head, *rows, _abi.ptr(gamma), _abi.ptr(beta), bn.running_mean.data_ptr() if track else None,
+                              bn.running_var.data_ptr() if track else None, p0, p0 + 4 * n_out, p0 + 8 * n_out, p0 + 12 * n_out, _abi.ptr(nbt),
+                              *fused, _abi.current_stream())
+    _abi.check(rc, name)
+    if track:
+        # the kernel wrote the running statistics (and the counter) through raw pointers: PyTorch's version counters, on which the
+        # eval-mode vectors of this module are cached, have to move with them (no launch); a step being captured into a graph notes
+        # the tensors so that every REPLAY can do the same (gsn_amd.graphs.GraphedTrainStep)
+        touched = [bn.running_mean, bn.running_var] + ([nbt] if nbt is not None else [])
+        torch.autograd.graph.increment_version(touched)
+        if flags.RAW_WRITTEN is not None:
+            flags.RAW_WRITTEN.extend(touched)
+    return (v0, v2, v3), v1
+
+
+def _bn_resolve(stage, stats_fn, m_rows, training):
+    """Fill stage.bn_params = (mean, scale, shift) and stage.bn_invstd: batch statistics in train mode (or without running statistics), else the cached vectors."""
+    bn = stage.bn
+    if bn is not None and (training or bn.running_mean is None):
+        stage.bn_params, stage.bn_invstd = _bn_batch_vectors(bn, stage.weight.device, stats_fn, m_rows, training)
+    else:
+        stage.bn_params, stage.bn_invstd = _bn_eval_vectors(bn)
 
 
 def run_stages(stages, m_rows, training, csr=None):

@@ -37,7 +37,7 @@ from ._index import (Codes, _AddByGraphFn, _CSR_CACHE, _PARTITION, _PropagateFn,
                      set_batch_partition, set_graph_partition)
 from ._caches import (_CAPTURE_CACHED, _async_validate, _module_fingerprint, _note_cache, drop_capture_caches, drop_input_caches,
                       invalidate_caches)
-from ._dense import _Stage, _bn_resolve, _chain_fits, _launch_stages, _layer_fused, _linear_hip, run_stages
+from ._dense import _Stage, _bn_eval_vectors, _chain_fits, _launch_stages, _layer_fused, _linear_hip, run_stages
 from ._autograd import (_DenseStagesFn, _FoldWeightsFn, _GatherCatFn, _HipWithNativeBackward, _HipWithTorchBackward, _code_stage_segsum,
                         _dense_native_ok, _run, _segment_sum_cols, run_stages_autograd)
 
@@ -645,7 +645,7 @@ class _SparseLayer(nn.Module):
         if 2 * d_n + d_r <= flags.SPLIT_EDGE_MIN_K or d_h % 4 or d_h > 256 or any(b.shape[1] % 4 for b in edge_blocks) \
                 or d_r > (16 if d_h <= 128 else 8) or len(edge_blocks) > 2:
             return None
-        _bn_resolve(st, None, E, False)
+        st.bn_params, st.bn_invstd = _bn_eval_vectors(st.bn)
         w1, b1 = mf.fc[0].weight, mf.fc[0].bias
         bn_key = None if st.bn is None else tuple(t._version for t in (st.bn.running_mean, st.bn.running_var)) + \
             ((st.bn.weight._version, st.bn.bias._version) if st.bn.affine else ())

@@ -203,7 +203,7 @@ class CountLayerStep:
         if self._lay is not None and self._lay[0] == key:
             return self._lay[1]
         for st in stages:
-            _dense._bn_resolve(st, None, 0, False)
+            st.bn_params, st.bn_invstd = _dense._bn_eval_vectors(st.bn)
         keep = []
         # the edge stage's blocks: x through the sorted targets, x through the sorted sources, the edge pack's columns through perm -- their rows
         # are the two packs (empty fp32 placeholders give the widths)
