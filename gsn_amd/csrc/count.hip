@@ -19,90 +19,9 @@
 #include <type_traits>
 
 #include "count_core.h"
+#include "count_plan.h"
 
 namespace gsn {
-
-constexpr int GSN_ENC_MAX_COLS = 64;
-
-// What gsn_count_encode_pack16_side_hip adds to a counting launch (r06): the target-sorted CSR of the batch's columns, the node pack from
-// integer node codes, the edge codes' one-hot columns of the edge pack.  They are made by SIDE WORKGROUPS of the same launch (side_block
-// below), every (SIDE_EVERY + 1)-th workgroup of the grid; the counting workgroups run count_body exactly as without them.
-// gsn_count_encode_keys_side_hip: the same launch leaving COMPACT outputs in place of the packs -- a key byte per vertex and a key word per sorted
-// column from the side workgroups, a 16-bit mask of the identifier classes per column from the counting workgroups (include/gsn_abi.h: gsn_count_keys).
-struct SideArgs {
-    int32_t *csr_seg, *csr_perm, *csr_tgt, *csr_oth;   // csr_seg == null: no CSR
-    int64_t tot_nodes, tot_edges;
-    const int64_t *ncode;      // node codes [tot_nodes][ncode_cols] or null
-    uint16_t *npack;           // fp16 [tot_nodes][32]
-    const int64_t *ecode;      // edge codes [tot_edges][ecode_cols] or null
-    uint16_t *epack;           // fp16 [tot_edges][16]: columns ecode_col0 .. 15 are written
-    int32_t *code_status;      // or null
-    int csr_row;               // the row of edge_index that is the aggregation target
-    int ncode_cols, ncode_clamp, ecode_cols, ecode_clamp, ecode_col0;
-    unsigned ncode_ptr_w[2], ecode_ptr_w[2];    // first pack column of every code column's classes, one BYTE per column + the end (prefix sums; the
-                                                // edge codes' start at ecode_col0) -- as words: byte-sized kernel arguments are vector loads on gfx9
-    // compact outputs (gsn_count_encode_keys_side_hip): what layer 0 reads in place of the two packs
-    uint8_t *nkey;             // [tot_nodes] or null: row of the vertex in the node dictionary = the mixed-radix number of its code digits, column 0
-                               // most significant; without clamp every column has one digit more, "none" (a code outside its classes: zero segment)
-    uint32_t *ekeys;           // [tot_edges] or null, target-sorted order: nkey[target] | nkey[other] << 8 | edge-code class mask << 16
-    unsigned nkey_radix_w;     // digits per node code column, one byte per column
-};
-#ifndef GSN_SIDE_EVERY
-#define GSN_SIDE_EVERY 4
-#endif
-constexpr int SIDE_EVERY = GSN_SIDE_EVERY;  // counting workgroups per side workgroup (A/B: 2: +0.0xx, 8: see profiles/r06_count_side_ab.txt; at 8 waves per SIMD 8 loses 0.017 ms: profiles/count_cycle_occupancy.txt)
-
-struct CountArgs {
-    const uint32_t *plan;      // device
-    int plan_words;
-    int mode, n_cols, n_plans, plans_off, kmax;
-    const int64_t *node_ptr, *edge_ptr, *src, *dst;
-    int ids_are_global;
-    const int32_t *graph_ids;  // or null
-    int n_cap, e_cap;          // LDS capacities (rows of A, columns)
-    int last_cap;              // entries of last[] (edge mode): the slots of the CSR rank a workgroup may address, >= e_cap
-    int n_decl, e_decl;        // the caller's max_nodes / max_edges: a single graph beyond them is reported (GSN_ST_TOO_LARGE)
-    int stack_skip;            // frames of the candidate stack that are never addressed (the smallest n_fixed of the plans)
-    int pair;                  // 1: a workgroup takes the graphs 2 i, 2 i + 1 -- as ONE graph, their disjoint union, when that fits n_cap / e_cap
-    int n_graphs;
-    int stage_out;             // 1: output rows staged in LDS then written coalesced
-    int sym;                   // edge mode with undirected orbit classes: rows (u,v) and (v,u) are equal -> search once
-    int split;                 // workgroups per graph (each takes a contiguous slice of the (column,row) task space)
-    int64_t *out;
-    int32_t *status;
-    // LDS byte offsets
-    int off_valid, off_stack, off_plan, off_eu, off_ev, off_rowstart, off_last, off_out, off_misc;
-    int off_prim, off_revof;   // edge mode: the rows that run searches, in column order; per column the last column of the reverse pair
-    int off_ball;              // distance-pruning tables (radius 2, radius 3: n_cap rows each) or -1
-    int off_degp;              // degree bit planes of the cores, [CORE_MAX + 1][DEG_PLANES][W] words (plans with a chain tail), or -1
-    int degp_mask;             // bit d: some chain-tail plan lives in the d-core
-    int any_tail;              // some plan ends in a closed form (plan_tail != 0)
-    int tail_loop;             // graphs of <= 64 vertices: the last two levels in the tight loop too (dense graphs; GSN_COUNT_TAIL_LOOP)
-    int off_core;              // d-cores of the graph, d = 0 .. CORE_MAX (W words each)
-    int core_mask;             // bit d: some plan needs the d-core
-    int off_ain;               // directed plans: the in-neighbour bit matrix
-    int stride;                // words per plan (plan_stride)
-    int pull_batch;            // idle lanes that wait before the pool's pull arm runs (1: every trip; GSN_PULL_BATCH)
-    int zero_status;           // 1: a workgroup owns its graphs' status words (no split, no graph list) and zeroes them itself -- no memset launch in front
-    // fused identifier encoding (gsn_count_encode_hip): column c of a finished cell also / instead leaves as n_classes[c] floats
-    // with a single 1 (utils_graph_learning.one_hot_encoder, :170-187) -- the int64 round trip through HBM and the one-hot launch go
-    unsigned short enc_n[GSN_ENC_MAX_COLS];   // n_classes per output column (blocks in column order)
-    float *enc_out;            // [rows_total][enc_width] or null
-    int enc_width, enc_clamp, off_enc;
-    int enc_stage;             // 1: cells leave their class index in an LDS byte array, the rows are expanded and written coalesced at the end
-    int off_encst;             // that array: [rows_cap][n_cols] bytes, 0xff = no class (count out of range, unclamped)
-    int enc_from_counts;       // 1: no byte array -- the staged 16-bit counts (stage_out) give the class indices at the end (LDS per workgroup: occupancy)
-    uint16_t *enc16;           // the same rows as fp16 into a column range of an exact row pack (gsn_count_encode_pack16_hip), or null; staged rows only
-    int enc_no32;              // 1: the fp16 pack columns are the ONLY form of the encoded rows (enc_out is a placeholder that is never written)
-    int enc16_stride, enc16_col0;
-    int side_mask;             // bit 0: CSR, bit 1: node pack, bit 2: edge codes; != 0: the grid holds side workgroups
-    int n_items;               // counting work items of the launch (graphs, or pairs of graphs)
-    int lds_bytes;             // dynamic LDS of the launch (a side workgroup sorts as many graphs at a time as fit there)
-    unsigned cyc_len;          // cycle instantiation: the cycle length of output column c in byte c (count_core.h: cycle_plan_lengths)
-    uint16_t *idmask;          // [rows_total] or null: bit enc16_col0 + (first column of c's classes) + class of every column c of a row -- the hot pack
-                               // columns of the row as a bit mask, from the staged class indices (phase 4')
-    SideArgs side;
-};
 
 // The side arguments are read from the kernel-argument segment where they are used (scalar loads through a laundered pointer), not held in
 // scalar registers from the kernel's entry: the molecule instantiation runs at its register bound (amdgpu_waves_per_eu).
@@ -135,7 +54,7 @@ __device__ __forceinline__ int side_byte(const unsigned w0, const unsigned w1, c
 // column's endpoints against their graph); a code outside its classes ORs 1 into *code_status.
 // FL: the launch-uniform flags as a type (CycAny / CycKeys, in front of count_body).  With CycKeys the side outputs are the headline step's
 // and nothing else: CSR with sorted targets and sources, ONE node code column as key bytes, ONE edge code column in the key words, global
-// vertex ids, no row pack -- the arms of every other form are not compiled in (launch<>() sends every other launch to CycAny).
+// vertex ids, no row pack -- the arms of every other form are not compiled in (count_plan.cpp: choose_kernel sends every other launch to CycAny).
 struct CycAny { static constexpr bool KEYS = false; };
 struct CycKeys { static constexpr bool KEYS = true; };
 template <int T, class FL = CycAny>
@@ -455,7 +374,7 @@ __device__ unsigned long long *g_count_prof2;  // [12] wave-level sums over the 
 // MOL: the launch's invariants of the molecule datasets' identifier pass as compile-time constants -- edge mode with undirected orbit
 // classes (symmetric rows), four output columns, one workgroup per pair of graphs (no split), encoded rows staged as class
 // indices -- instead of ~12 launch arguments that are tested in every arm of the pool and held in scalar registers
-// through the whole kernel (106 of them + spills before).  The launcher selects it when all of that holds (launch<>()).
+// through the whole kernel (106 of them + spills before).  The planner selects it when all of that holds (count_plan.cpp: count_molecule_route).
 // CYC = L > 0 (with MOL): every column is a non-induced cycle of length <= L -- no plan table, candidate stack or distance tables in LDS,
 // and the task pool is one bitset path walk per searching row (count_core.h: cycle_walk) that yields the row's four cells at once.
 // FL (CYC only): the flags that are the same for every workgroup of a launch, as a type.  CycAny tests them where they are used (scalar
@@ -598,7 +517,7 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
     };
 
     // ---- phase 0: clear LDS state, copy the plan table ------------------------------------------------------------
-    typedef unsigned lds16_t __attribute__((ext_vector_type(4)));      // CYC: every cleared array starts and ends on 16 bytes (count_launch)
+    typedef unsigned lds16_t __attribute__((ext_vector_type(4)));      // CYC: every cleared array starts and ends on 16 bytes (count_plan.cpp: lds_layout)
     if constexpr (CYC > 0) {
         for (int i = tid; i < (n + 1) / 2; i += T) reinterpret_cast<lds16_t *>(A)[i] = lds16_t{0u, 0u, 0u, 0u};
     } else
@@ -816,7 +735,7 @@ __device__ __forceinline__ int count_body(const Args &a, unsigned char *smem, co
         // last[] is addressed by SLOT, not by column: a graph has two slots per undirected pair, which is more than its columns where pairs
         // come in one direction only.  Every slot in use is cleared (cleared up to E only, the slots beyond held whatever the pass before
         // left there: a stale column id made a live column lose its atomicMax, and rows of graphs with one-way pairs came out zero now and
-        // then), and every slot lies inside last[]: the launcher sizes it for a single graph's slots (count_launch: last_cap >= 2 e_decl or
+        // then), and every slot lies inside last[]: the planner sizes it for a single graph's slots (count_plan.cpp: last_cap >= 2 e_decl or
         // n_decl (n_decl - 1)), and a pair with more slots than that is redone graph by graph.
         if constexpr (!(CYC > 0)) {                      // (the total is rowstart[n]: behind a barrier where more than one wave wrote the row starts)
             __syncthreads();
@@ -1263,7 +1182,7 @@ template <int W, int T, bool DIR, bool TAIL, bool MOL = false, int CYC = 0, clas
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(CYC > 0 ? COUNT_CYC_WAVES : DIR ? 1 : (W == 1 ? COUNT_W1_WAVES : (W == 2 ? COUNT_W2_WAVES : (W == 4 ? COUNT_W4_WAVES : 1))))))
 void count_kernel(CountArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr bool KEYS = CYC > 0 && FL::KEYS;           // (the headline launch: side workgroups, pairs, status words zeroed here -- launch<>())
+    constexpr bool KEYS = CYC > 0 && FL::KEYS;           // (the headline launch: side workgroups, pairs, status words zeroed here -- count_plan.cpp: choose_kernel)
     int bid = (int)blockIdx.x;
     if (KEYS || a.side_mask) {                           // (launches with side workgroups: one workgroup per item, no graph list)
         const int grp = bid / (SIDE_EVERY + 1), j = bid - grp * (SIDE_EVERY + 1);
@@ -1331,8 +1250,6 @@ __global__ void status_zero_kernel(const int32_t *graph_ids, int n, int32_t *sta
     if (i < n) status[graph_ids[i]] = 0;
 }
 
-static inline int align_up(int x, int a) { return (x + a - 1) / a * a; }
-
 template <int W, int T, bool DIR, bool TAIL, bool MOL = false, int CYC = 0, class FL = CycAny>
 static int launch_d(CountArgs &a, int n_items, size_t lds, hipStream_t stream) {
     // (the size varies per call: no once-per-device flag; no label: the error names the byte count)
@@ -1386,335 +1303,87 @@ static int launch_d(CountArgs &a, int n_items, size_t lds, hipStream_t stream) {
 #endif
     return GSN_OK;
 }
-template <int W, int T>
-static int launch(CountArgs &a, int n_items, size_t lds, hipStream_t stream) {
-    // TAIL: the instantiation with the closed forms / the tight loop of the last two levels (count_core.h) -- graphs above 64 vertices, or a
-    // plan that ends in a closed form; the molecule workloads with cycle / clique patterns run the instantiation without them
-    if constexpr (W >= 2) {            // (always with the tails: no second instantiation to compile)
-        return a.off_ain >= 0 ? launch_d<W, T, true, true>(a, n_items, lds, stream) : launch_d<W, T, false, true>(a, n_items, lds, stream);
-    } else {
-        const bool tail = a.any_tail != 0 || a.tail_loop != 0;
-        if (a.off_ain >= 0) return tail ? launch_d<W, T, true, true>(a, n_items, lds, stream) : launch_d<W, T, true, false>(a, n_items, lds, stream);
-        if constexpr (T == 64) {
-#ifdef COUNT_PROF
-            static const bool mol_on = false;           // (the phase profile is read from the generic instantiation, or from the cycle one)
-#else
-            const bool mol_on = sw_on(SW_COUNT_MOL, true);
-#endif
-            const bool mol = mol_on && !tail && a.mode == GSN_MODE_EDGE && a.sym && a.n_cols == 4 && a.pair && a.split == 1 && a.enc_out &&
-                             a.enc_stage && !a.graph_ids;
-            trace("gsn count: molecule instantiation %d cycle walk %d (tail %d mode %d sym %d cols %d pair %d split %d stage %d out %d enc %d enc_stage %d ids %d)\n", (int)mol,
-                        (int)(a.cyc_len != 0), (int)tail, a.mode, a.sym, a.n_cols, a.pair, a.split, a.stage_out, a.out != nullptr, a.enc_out != nullptr, a.enc_stage, a.graph_ids != nullptr);
-            // every column a cycle of length <= 6 (count_launch: the launch's LDS was laid out for it, under these very conditions): the walk
-            if (a.cyc_len) {
-                // (the headline step's flag combination as compile-time constants: count_body, CycKeys)
-                // -- and the launch-uniform rest of it: global vertex ids, pairs, status words zeroed by their workgroups, and side workgroups that
-                // leave the CSR with both sorted endpoint arrays, one node code column as key bytes and one edge code column in the key words
-                // (side_block<T, CycKeys>).  Anything else is CycAny's.
-                const SideArgs &sd = a.side;
-                const bool side_keys = a.side_mask == 7 && sd.csr_tgt && sd.csr_oth && sd.nkey && sd.ekeys && !sd.npack && !sd.epack && sd.ncode_cols == 1 && sd.ecode_cols == 1;
-                const bool keys = a.out && a.stage_out && a.enc_stage && a.enc_from_counts && a.enc_no32 && !a.enc16 && a.idmask && a.split == 1 &&
-                                  a.ids_are_global && a.pair && a.zero_status && side_keys;
-                trace("gsn count: cycle flags %s\n", keys ? "CycKeys" : "CycAny");
-                return keys ? launch_d<1, 64, false, false, true, 6, CycKeys>(a, n_items, lds, stream) : launch_d<1, 64, false, false, true, 6>(a, n_items, lds, stream);
-            }
-            if (mol) {
-                if (int rc = lds_limit(nullptr, {kernel_ptr(&count_kernel_mol)}, nullptr, (int)lds)) return rc;
-                hipLaunchKernelGGL(count_kernel_mol, dim3((unsigned)n_items), dim3(64), lds, stream, a);
-                return launch_check("count_kernel_mol launch");
-            }
-        }
-        return tail ? launch_d<W, T, false, true>(a, n_items, lds, stream) : launch_d<W, T, false, false>(a, n_items, lds, stream);
+static int launch_mol(CountArgs &a, int n_items, size_t lds, hipStream_t stream) {
+    if (int rc = lds_limit(nullptr, {kernel_ptr(&count_kernel_mol)}, nullptr, (int)lds)) return rc;
+    hipLaunchKernelGGL(count_kernel_mol, dim3((unsigned)n_items), dim3(64), lds, stream, a);
+    return launch_check("count_kernel_mol launch");
+}
+
+constexpr int kernel_key(int W, int T, CountKernel k) { return (W * 1024 + T) * 8 + (int)k; }
+
+// The instantiations of the library, one per plan (count_plan.cpp: choose_kernel): one-word graphs have all four of directed x tail, and at
+// 64 threads the molecule and cycle kernels; wider graphs always run with the tails.
+static int dispatch(CountLaunchPlan &p, hipStream_t st) {
+    CountArgs &a = p.args;
+    const int n = p.grid;
+    const size_t lds = (size_t)p.lds_bytes;
+    switch (kernel_key(p.W, p.T, p.kernel)) {
+        case kernel_key(1, 64, DIRECTED_TAIL): return launch_d<1, 64, true, true>(a, n, lds, st);
+        case kernel_key(1, 64, DIRECTED): return launch_d<1, 64, true, false>(a, n, lds, st);
+        case kernel_key(1, 64, CYCLE_KEYS): return launch_d<1, 64, false, false, true, 6, CycKeys>(a, n, lds, st);
+        case kernel_key(1, 64, CYCLE_ANY): return launch_d<1, 64, false, false, true, 6>(a, n, lds, st);
+        case kernel_key(1, 64, CountKernel::MOL): return launch_mol(a, n, lds, st);
+        case kernel_key(1, 64, GENERIC_TAIL): return launch_d<1, 64, false, true>(a, n, lds, st);
+        case kernel_key(1, 64, GENERIC): return launch_d<1, 64, false, false>(a, n, lds, st);
+        case kernel_key(1, 256, DIRECTED_TAIL): return launch_d<1, 256, true, true>(a, n, lds, st);
+        case kernel_key(1, 256, DIRECTED): return launch_d<1, 256, true, false>(a, n, lds, st);
+        case kernel_key(1, 256, GENERIC_TAIL): return launch_d<1, 256, false, true>(a, n, lds, st);
+        case kernel_key(1, 256, GENERIC): return launch_d<1, 256, false, false>(a, n, lds, st);
+        case kernel_key(2, 64, DIRECTED_TAIL): return launch_d<2, 64, true, true>(a, n, lds, st);
+        case kernel_key(2, 64, GENERIC_TAIL): return launch_d<2, 64, false, true>(a, n, lds, st);
+        case kernel_key(2, 256, DIRECTED_TAIL): return launch_d<2, 256, true, true>(a, n, lds, st);
+        case kernel_key(2, 256, GENERIC_TAIL): return launch_d<2, 256, false, true>(a, n, lds, st);
+        case kernel_key(4, 64, DIRECTED_TAIL): return launch_d<4, 64, true, true>(a, n, lds, st);
+        case kernel_key(4, 64, GENERIC_TAIL): return launch_d<4, 64, false, true>(a, n, lds, st);
+        case kernel_key(4, 256, DIRECTED_TAIL): return launch_d<4, 256, true, true>(a, n, lds, st);
+        case kernel_key(4, 256, GENERIC_TAIL): return launch_d<4, 256, false, true>(a, n, lds, st);
+        case kernel_key(8, 64, DIRECTED_TAIL): return launch_d<8, 64, true, true>(a, n, lds, st);
+        case kernel_key(8, 64, GENERIC_TAIL): return launch_d<8, 64, false, true>(a, n, lds, st);
+        case kernel_key(12, 64, DIRECTED_TAIL): return launch_d<12, 64, true, true>(a, n, lds, st);
+        case kernel_key(12, 64, GENERIC_TAIL): return launch_d<12, 64, false, true>(a, n, lds, st);
     }
+    return set_error(GSN_E_UNSUPPORTED, "gsn_count_hip: no count_kernel<%d,%d> of kind %d in this build", p.W, p.T, (int)p.kernel);
 }
 
 }  // namespace gsn
 
 using namespace gsn;
 
-static int count_launch(const uint32_t *plan_host, const uint32_t *plan_dev, int64_t plan_words, int64_t n_graphs,
-                        const int64_t *node_ptr, const int64_t *edge_ptr, const int64_t *edge_index,
-                        int64_t edge_row_stride, int ids_are_global, const int32_t *graph_ids, int64_t n_items,
-                        int64_t max_nodes, int64_t max_edges, int64_t *out, int32_t *status, const int32_t *n_classes,
-                        int enc_clamp, float *enc_out, void *stream, uint16_t *enc16 = nullptr, int64_t enc16_stride = 0, int64_t enc16_col0 = 0, int enc_no32 = 0,
-                        const gsn_count_side *side = nullptr, const gsn_count_keys *keys = nullptr) {
-    if (plan_host && plan_words >= PLAN_HEADER_WORDS && plan_host[0] == PLAN_MAGIC_WIDE) return set_error(GSN_E_UNSUPPORTED, GSN_WIDE_PLAN_REFUSAL);
-    if (!plan_host || !plan_dev || plan_words < PLAN_HEADER_WORDS || plan_host[0] != PLAN_MAGIC)
-        return set_error(GSN_E_INVALID, "gsn_count_hip: not a plan table (build it with gsn_count_plan_build)");
-    if (!node_ptr || !edge_ptr || (!out && !enc_out) || !status) return set_error(GSN_E_INVALID, "gsn_count_hip: null pointer argument");
-    if (enc_out && !n_classes) return set_error(GSN_E_INVALID, "gsn_count_encode_hip: n_classes is null");
-    if (!graph_ids) n_items = n_graphs;
-    if (n_items <= 0) return GSN_OK;
-    if (max_nodes > 768)
-        return set_error(GSN_E_UNSUPPORTED, "graphs with more than 768 vertices (%lld) are outside this build", (long long)max_nodes);
-    if (max_nodes < 1) max_nodes = 1;
-    if (max_edges < 0) max_edges = 0;
-
-    CountArgs a{};
-    a.plan = plan_dev; a.plan_words = (int)plan_words;
-    a.mode = (int)plan_host[1]; a.n_plans = (int)plan_host[3]; a.n_cols = (int)plan_host[4]; a.kmax = (int)plan_host[5];
-    a.plans_off = (int)plan_host[7];
-    a.sym = (a.mode == GSN_MODE_EDGE && (plan_host[6] & 1u) == 0) ? 1 : 0;
-    const bool directed = (plan_host[6] & 2u) != 0;
-    a.stride = plan_stride(plan_host[6]);
-    {
-        const int pull_env = sw_int(SW_PULL_BATCH, 8), pull_batch = pull_env < 1 ? 1 : (pull_env > 64 ? 64 : pull_env);
-        a.pull_batch = pull_batch;
-    }
-    if (directed && a.mode != GSN_MODE_VERTEX) return set_error(GSN_E_UNSUPPORTED, "gsn_count_hip: directed plans are vertex-mode plans");
-    a.node_ptr = node_ptr; a.edge_ptr = edge_ptr;
-    a.src = edge_index; a.dst = edge_index ? edge_index + edge_row_stride : nullptr;
-    a.ids_are_global = ids_are_global; a.graph_ids = graph_ids;
-    a.out = out; a.status = status;
-    a.enc_out = enc_out; a.enc_width = 0; a.enc_clamp = enc_clamp;
-    int64_t enc_width = 0;
-    bool enc_bytes = true;                              // every class index fits a byte (0xff = none)
-    if (enc_out) {
-        if (a.n_cols > GSN_ENC_MAX_COLS)
-            return set_error(GSN_E_UNSUPPORTED, "gsn_count_encode_hip: %d output columns; the fused encoding handles <= %d", a.n_cols, GSN_ENC_MAX_COLS);
-        for (int c = 0; c < a.n_cols; ++c) {
-            if (n_classes[c] < 1 || n_classes[c] > 65535) return set_error(GSN_E_INVALID, "gsn_count_encode_hip: n_classes[%d] = %d", c, n_classes[c]);
-            a.enc_n[c] = (unsigned short)n_classes[c];
-            enc_width += n_classes[c];
-            enc_bytes = enc_bytes && n_classes[c] <= 255;
-        }
-        a.enc_width = (int)enc_width;
-    }
-    if (max_edges > 0 && !edge_index) return set_error(GSN_E_INVALID, "gsn_count_hip: edge_index is null");
-    // side outputs (gsn_count_encode_pack16_side_hip): validated here; the grid gets its side workgroups below
-    if (side) {
-        if (graph_ids) return set_error(GSN_E_UNSUPPORTED, "gsn_count_encode_pack16_side_hip: a graph list (the side outputs cover every graph of the batch)");
-        if (side->seg_ptr) {
-            if ((max_edges > 0 && !side->perm) || side->n_nodes < 0 || side->n_edges < 0 || side->n_nodes >= ((int64_t)1 << 31) - 1 || side->n_edges >= (int64_t)1 << 31)
-                return set_error(GSN_E_INVALID, "gsn_count_encode_pack16_side_hip: CSR outputs / totals");
-            a.side_mask |= 1;
-            a.side.csr_seg = side->seg_ptr; a.side.csr_perm = side->perm; a.side.csr_tgt = side->sorted_target; a.side.csr_oth = side->sorted_other;
-        }
-        a.side.csr_row = side->csr_row ? 1 : 0; a.side.tot_nodes = side->n_nodes; a.side.tot_edges = side->n_edges;
-        if (side->node_codes) {
-            const bool nk = keys && keys->nkey;          // (the node keys may stand in for the node pack)
-            if ((side->node_pack ? (reinterpret_cast<uintptr_t>(side->node_pack) & 15) != 0 : !nk) || side->node_code_cols < 1 || side->node_code_cols > 4)
-                return set_error(GSN_E_INVALID, "gsn_count_encode_pack16_side_hip: node pack (16-byte aligned) and 1..4 node code columns");
-            int o = 0;
-            int64_t dict_rows = 1;
-            for (int c = 0; c < side->node_code_cols; ++c) {
-                if (side->node_n_classes[c] < 1) return set_error(GSN_E_INVALID, "gsn_count_encode_pack16_side_hip: node_n_classes[%d] < 1", c);
-                a.side.ncode_ptr_w[c >> 2] |= (unsigned)o << (8 * (c & 3)); o += side->node_n_classes[c];
-                if (o > 28) return set_error(GSN_E_INVALID, "gsn_count_encode_pack16_side_hip: more than 28 encoded node columns");
-                const int radix = side->node_n_classes[c] + (side->node_clamp ? 0 : 1);
-                a.side.nkey_radix_w |= (unsigned)radix << (8 * c); dict_rows *= radix;
-            }
-            if (nk && dict_rows > 256)
-                return set_error(GSN_E_UNSUPPORTED, "gsn_count_encode_keys_side_hip: a node dictionary of %lld rows (one byte per key: <= 256)", (long long)dict_rows);
-            if (nk && side->node_pack)
-                return set_error(GSN_E_INVALID, "gsn_count_encode_keys_side_hip: node keys stand in for the node pack (side->node_pack must be NULL)");
-            a.side.nkey = nk ? keys->nkey : nullptr;
-            a.side.ncode_ptr_w[side->node_code_cols >> 2] |= (unsigned)o << (8 * (side->node_code_cols & 3));
-            a.side_mask |= 2;
-            a.side.ncode = side->node_codes; a.side.npack = side->node_pack; a.side.ncode_cols = side->node_code_cols; a.side.ncode_clamp = side->node_clamp ? 1 : 0;
-        }
-        if (side->edge_codes) {
-            if ((enc16 ? (enc16_stride != 16 || (reinterpret_cast<uintptr_t>(enc16) & 15)) : !(keys && keys->ekeys)) || side->edge_code_cols < 1 || side->edge_code_cols > 4)
-                return set_error(GSN_E_INVALID, "gsn_count_encode_pack16_side_hip: edge codes need a 16-column, 16-byte-aligned edge pack and 1..4 code columns");
-            if (side->edge_col0 < 0 || (side->edge_col0 & 3) || side->edge_col0 < enc16_col0 + enc_width)
-                return set_error(GSN_E_INVALID, "gsn_count_encode_pack16_side_hip: edge_col0 %d must be a multiple of 4 behind the identifier columns (%lld .. %lld)",
-                                 side->edge_col0, (long long)enc16_col0, (long long)(enc16_col0 + enc_width));
-            int o = side->edge_col0;
-            for (int c = 0; c < side->edge_code_cols; ++c) {
-                if (side->edge_n_classes[c] < 1) return set_error(GSN_E_INVALID, "gsn_count_encode_pack16_side_hip: edge_n_classes[%d] < 1", c);
-                a.side.ecode_ptr_w[c >> 2] |= (unsigned)o << (8 * (c & 3)); o += side->edge_n_classes[c];
-            }
-            a.side.ecode_ptr_w[side->edge_code_cols >> 2] |= (unsigned)o << (8 * (side->edge_code_cols & 3));
-            if (o > 16 || o - side->edge_col0 > 8)
-                return set_error(GSN_E_INVALID, "gsn_count_encode_pack16_side_hip: %d edge code classes at column %d (<= 8, inside the 16 columns)", o - side->edge_col0, side->edge_col0);
-            a.side_mask |= 4;
-            a.side.ecode = side->edge_codes; a.side.epack = enc16; a.side.ecode_cols = side->edge_code_cols; a.side.ecode_clamp = side->edge_clamp ? 1 : 0;
-            a.side.ecode_col0 = side->edge_col0;
-        }
-        a.side.code_status = side->code_status;
-        if (keys && keys->ekeys) {
-            if (!(a.side_mask & 1) || !side->sorted_target || !side->sorted_other)
-                return set_error(GSN_E_INVALID, "gsn_count_encode_keys_side_hip: the edge keys are written with the CSR arrays (seg_ptr, perm, sorted_target, sorted_other)");
-            a.side.ekeys = keys->ekeys;
-        }
-    }
-    if (keys && keys->idmask) {
-        if (directed) return set_error(GSN_E_UNSUPPORTED, "gsn_count_encode_keys_side_hip: directed plans (their instantiations carry no identifier masks)");
-        if (!enc_out || enc16_col0 < 0 || enc16_col0 + enc_width > 16)
-            return set_error(GSN_E_INVALID, "gsn_count_encode_keys_side_hip: the identifier masks hold pack columns %lld .. %lld (<= 16) of an encoded launch", (long long)enc16_col0,
-                             (long long)(enc16_col0 + enc_width));
-        a.idmask = keys->idmask;
-    }
-
-    const int W = max_nodes <= 64 ? 1 : (max_nodes <= 128 ? 2 : (max_nodes <= 256 ? 4 : (max_nodes <= 512 ? 8 : 12)));
-    const bool edge_mode = a.mode == GSN_MODE_EDGE;
-    const int64_t rows_cap = edge_mode ? max_edges : max_nodes;
-    // large graphs (W > 4: 16-bit vertex ids, adjacency up to 72 KiB) keep one wave per workgroup so that the candidate
-    // stack stays small; their parallelism comes from `split` workgroups per graph
-    const int T = (rows_cap * a.n_cols <= 512 || W > 4) ? 64 : 256;
-    a.n_decl = (int)max_nodes; a.e_decl = (int)max_edges;
-    a.n_graphs = (int)n_graphs;
-    // Two consecutive graphs per workgroup, as one graph (count_body): whole batches of small graphs whose plans hold connected patterns
-    // only (every enumerated level of every plan has an adjacency constraint); GSN_COUNT_PAIR=0 switches it off.
-    const int64_t tasks_cap1 = rows_cap * a.n_cols;
-    bool pair = !graph_ids && n_graphs >= 2 && W == 1 && T == 64 && !(n_items < 2048 && tasks_cap1 >= 1024);
-    if (pair && !sw_on(SW_COUNT_PAIR, true)) pair = false;
-    for (int p = 0; pair && p < a.n_plans; ++p) {
-        const uint32_t *w = plan_host + a.plans_off + (int64_t)p * a.stride;
-        const int k = (int)(w[0] & 0xffu), nfix = (int)((w[0] >> 8) & 0xffu);
-        for (int l = nfix; l < k; ++l) {
-            const uint32_t adj = (w[2 + l] & 0xffu) | (directed ? (w[PLAN_STRIDE_WORDS + l] & 0xffu) : 0u);
-            if (adj == 0) pair = false;
-        }
-    }
-    a.pair = pair ? 1 : 0;
-    if (pair) {
-        max_nodes = 2 * max_nodes < 64 ? 2 * max_nodes : 64;
-        max_edges = 2 * max_edges;
-    }
-    const int64_t rows_cap_u = edge_mode ? max_edges : max_nodes;      // (of what a workgroup holds: a graph, or the union of two)
-    a.n_cap = (int)max_nodes; a.e_cap = (int)max_edges;
-
-    // degree planes only when a plan ends in a chain (patterns.cpp: plan_tail_mode == 3): cycles, cliques -- the molecule workloads -- do not
-    a.off_degp = -1; a.degp_mask = 0; a.any_tail = 0;
-    for (int p = 0; p < a.n_plans; ++p) {
-        const uint32_t *w = plan_host + a.plans_off + (int64_t)p * a.stride;
-        if (plan_tail(w)) a.any_tail = 1;
-        if (plan_tail(w) == 3) a.degp_mask |= 1 << plan_core(w);
-    }
-    // one-word graphs: the tight loop over the images of level k - 2 pays where those sets are long -- dense graphs (average degree >= 8 by
-    // the caller's capacities: clique-rich ego networks 1.81 -> 0.96 ms per 1000, 12-regular n = 25 +5 %), not molecules (ZINC 0.073 ->
-    // 0.082 ms with it).  GSN_COUNT_TAIL_LOOP=0 / 1 forces it off / on.
-    a.tail_loop = 0;
-    if (W == 1) {
-        const int forced = sw_int(SW_COUNT_TAIL_LOOP, -1);
-        a.tail_loop = forced >= 0 ? (forced != 0) : ((int64_t)a.e_decl >= 8 * (int64_t)a.n_decl);     // (the caller's capacities, before pairing)
-    }
-    // Cycle columns (count_core.h: cycle_plan_lengths / cycle_walk): a launch that meets the molecule instantiation's conditions (launch<>())
-    // and whose four columns are all non-induced cycles of length <= 6 counts by path walks -- no candidate stack, plan table or distance
-    // tables in its LDS.  Longer cycles (7, 8) keep the interpreter.  GSN_COUNT_CYCLE=0 sends such a launch down the interpreter.
-    a.cyc_len = 0;
-    if (W == 1 && T == 64 && pair && edge_mode && a.sym && !directed && a.n_cols == 4 && enc_out && enc_bytes && !a.any_tail && !a.tail_loop) {
-        const bool cyc_on = sw_on(SW_COUNT_CYCLE, true);
-#ifdef COUNT_PROF
-        static const bool mol_on = true;
-#else
-        const bool mol_on = sw_on(SW_COUNT_MOL, true);
+// Plan (count_plan.cpp: every decision, on the host), status words, trace, dispatch.
+static int count_launch(const CountRequest &rq, void *stream) {
+    CountSwitches sw = CountSwitches::read();
+#ifdef COUNT_PROF       // (the phase profile is read from the generic instantiation, or from the cycle one; here, where the profiling build's define is seen)
+    sw.cycle = sw_on(SW_COUNT_CYCLE, true);
+    sw.mol = false;
 #endif
-        uint8_t len[4];
-        const int lmax = (cyc_on && mol_on) ? cycle_plan_lengths(plan_host, plan_words, len, 4) : 0;
-        if (lmax >= 3 && lmax <= 6) a.cyc_len = (unsigned)len[0] | ((unsigned)len[1] << 8) | ((unsigned)len[2] << 16) | ((unsigned)len[3] << 24);
-    }
-    const bool cyc = a.cyc_len != 0;
-
-    int o = align_up((int)max_nodes * W * 8, 16);
-    a.off_ain = -1;
-    if (directed) { a.off_ain = o; o += align_up((int)max_nodes * W * 8, 16); }
-    a.off_valid = o; o += align_up(W * 8, 16);
-    // candidate stack: one frame per enumerated level below the last (levels n_fixed .. k - 2; .. k - 3 for W >= 2); the frames of the root levels are
-    // never touched, so the array starts at the smallest n_fixed of the plans (stack_skip frames in front of it do not exist)
-    int nfix_min = 255;
-    for (int p = 0; p < a.n_plans; ++p) { const int nf = (int)((plan_host[a.plans_off + (int64_t)p * a.stride] >> 8) & 0xffu); nfix_min = nf < nfix_min ? nf : nfix_min; }
-    if (nfix_min > a.kmax - 1 || a.n_plans == 0) nfix_min = 0;
-    a.stack_skip = nfix_min;
-    // (W >= 2: levels k - 2 and k - 1 never get a frame -- count_core.h counts them in closed form or in tail_loop)
-    const int last_frame = W >= 2 ? a.kmax - 2 : a.kmax - 1;
-    const int depth = last_frame - nfix_min > 1 ? last_frame - nfix_min : 1;
-    a.off_stack = o; o += cyc ? 0 : depth * W * T * 8;
-    a.off_plan = o; o += cyc ? 0 : align_up((int)plan_words * 4, 16);
-    const int vid_bytes = W > 4 ? 2 : 1;
-    a.off_eu = o; o += edge_mode ? align_up((int)max_edges * vid_bytes, 16) : 0;
-    a.off_ev = o; o += edge_mode ? align_up((int)max_edges * vid_bytes, 16) : 0;
-    a.off_rowstart = o; o += edge_mode ? align_up(((int)max_nodes + 1) * (W == 1 ? 2 : 4), 16) : 0;
-    // last[] holds one entry per SLOT of the CSR rank (two per undirected pair): a single graph has at most min(2 e_decl, n_decl (n_decl - 1)) of
-    // them, which a pair's 2 e_decl columns already cover; a pair with more is redone graph by graph (count_body, phase 2)
-    {
-        const int64_t one = 2 * (int64_t)a.e_decl < (int64_t)a.n_decl * (a.n_decl - 1) ? 2 * (int64_t)a.e_decl : (int64_t)a.n_decl * (a.n_decl - 1);
-        a.last_cap = (int)(one > max_edges ? one : max_edges);
-    }
-    a.off_last = o; o += edge_mode ? align_up(a.last_cap * 4, 16) : 0;
-    if (edge_mode && max_edges >= 65535) return set_error(GSN_E_UNSUPPORTED, "gsn_count_hip: %lld columns per workgroup (16-bit column tables; LDS ends far earlier)", (long long)max_edges);
-    a.off_prim = o; o += edge_mode ? align_up((int)max_edges * 2, 16) : 0;
-    a.off_revof = o; o += edge_mode ? align_up((int)max_edges * 2, 16) : 0;
-    a.off_misc = o; o += 32;
-    a.off_enc = o; o += enc_out ? align_up(2 * a.n_cols * 4, 16) : 0;
-    a.off_core = o; o += align_up((CORE_MAX + 1) * W * 8, 16);
-    a.core_mask = 0;
-    for (int p = 0; p < a.n_plans; ++p) a.core_mask |= 1 << plan_core(plan_host + a.plans_off + p * a.stride);
-    // pruning tables only for graphs of <= 64 vertices (molecules): on larger, denser targets the balls are (nearly)
-    // everything and the extra AND per step costs more than it saves (measured: ER G(128,1000) +8 %)
-    a.off_ball = -1;
-    if (W == 1 && a.kmax >= 4 && !directed && !cyc) { a.off_ball = o; o += align_up(2 * (int)max_nodes * W * 8, 16); }
-    if (a.degp_mask) { a.off_degp = o; o += align_up((CORE_MAX + 1) * DEG_PLANES * W * 8, 16); }
-    a.off_out = o;
-    const int64_t stage_bytes = align_up((int)(rows_cap_u * a.n_cols * 2 < ((int64_t)1 << 28) ? rows_cap_u * a.n_cols * 2 : ((int64_t)1 << 28)), 16);      // (16-bit staged counts)
-    // Stage the output rows in LDS (coalesced final write) only while that keeps the workgroup small: the search is
-    // latency-bound on dependent LDS reads, so heavy graphs want as many co-resident workgroups per CU as possible
-    // (>= 8 waves per SIMD) and write their cells straight to HBM instead.
-    const int64_t lds_budget = (T == 64 ? (pair ? 160 * 1024 / 16 : 160 * 1024 / 32) : 160 * 1024 / 8);
-    a.stage_out = (out && o + stage_bytes <= lds_budget) ? 1 : 0;
-    // few heavy graphs: several workgroups per graph so that every CU gets >= 8 of them
-    a.split = 1;
-    const int64_t tasks_cap = rows_cap * a.n_cols;
-    const int64_t split_target_env = sw_int64(SW_COUNT_SPLIT_TARGET, 0), split_target = split_target_env > 0 ? split_target_env : 2048;
-    if (!pair && n_items < split_target && tasks_cap >= 1024) {
-        int64_t sp = (split_target + n_items - 1) / n_items;
-        if (sp > 32) sp = 32;
-        if (sp > tasks_cap / 256) sp = tasks_cap / 256;
-        if (sp > 1) { a.split = (int)sp; a.stage_out = 0; }
-    }
-    if (a.stage_out) o += (int)stage_bytes;
-    // class indices of the encoded rows: staged whenever one workgroup owns the whole graph and the indices fit a byte; else
-    // every cell writes its floats itself
-    a.enc_stage = 0; a.off_encst = o; a.enc_from_counts = 0;
-    a.enc16 = enc16; a.enc16_stride = (int)enc16_stride; a.enc16_col0 = (int)enc16_col0;
-    a.enc_no32 = ((enc16 || a.idmask) && enc_no32) ? 1 : 0;
-    if (enc_out && a.split == 1 && enc_bytes && rows_cap_u * enc_width < (int64_t)1 << 24 && o + rows_cap_u * a.n_cols <= 150 * 1024) {
-        a.enc_stage = 1;
-        const bool bytes_forced = sw_present(SW_COUNT_ENC_BYTES);     // (A/B: keep the byte array beside staged counts)
-        if (a.stage_out && !bytes_forced) a.enc_from_counts = 1;      // the staged 16-bit counts hold what the class indices need: no second array
-        else o += align_up((int)(rows_cap_u * a.n_cols), 16);         // (16-byte aligned: with four columns a row's indices are read as one word)
-    }
-    if (a.side_mask) {
-        if (a.split != 1)
-            return set_error(GSN_E_UNSUPPORTED, "gsn_count_encode_pack16_side_hip: this launch splits a graph over %d workgroups (few heavy graphs): the side workgroups ride a "
-                                                "one-workgroup-per-item grid; use gsn_csr_build_graphs_hip / gsn_one_hot_pack16_hip", a.split);
-        // a side workgroup sorts a graph of the declared sizes in the launch's LDS (several at a time where they fit)
-        const int64_t need = ((int64_t)a.n_decl + 1) * 8 + (int64_t)a.n_decl * 4 + (int64_t)a.e_decl * 7 + 16;
-        if (a.n_decl >= 65535 || a.e_decl >= 65535 || need > 160 * 1024)
-            return set_error(GSN_E_UNSUPPORTED, "gsn_count_encode_pack16_side_hip: graphs of %d vertices / %d columns do not sort in LDS (%lld B)", a.n_decl, a.e_decl, (long long)need);
-        if (need > o) o = align_up((int)need, 16);
-    }
-    if (o > 160 * 1024) return set_error(GSN_E_UNSUPPORTED, "graph too large for LDS (%d B needed)", o);
-    // (a pair of one-word graphs of <= 128 columns each: a few KiB, class indices in a byte -- always staged)
-    if (cyc && !(a.enc_stage && a.split == 1)) return set_error(GSN_E_UNSUPPORTED, "gsn_count_hip: cycle launch without staged class indices (%d B of LDS)", o);
-    if (a.idmask && !a.enc_stage)
-        return set_error(GSN_E_UNSUPPORTED, "gsn_count_encode_keys_side_hip: the identifier masks are written from the staged class indices (one workgroup per graph, n_classes <= 255)");
-    if (enc16 && !a.enc_stage)
-        return set_error(GSN_E_UNSUPPORTED, "gsn_count_encode_pack16_hip: the fp16 rows are written from the staged class indices (one workgroup per graph, "
-                                            "n_classes <= 255); pack the fp32 rows with gsn_pack16_rows_hip instead");
-
+    CountLaunchPlan p;
+    if (int rc = count_plan(rq, sw, &p)) return rc;
+    if (p.grid == 0) return GSN_OK;
+    const CountArgs &a = p.args;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    // per-graph status words start at OK; workgroups raise them with atomicMax.  One workgroup per graph (or pair) and every graph taken:
-    // the workgroup zeroes its own words -- the memset was a 6 us launch (+ the gap behind it) in front of every counting launch
-    a.zero_status = (!graph_ids && a.split == 1) ? 1 : 0;
-    if (!a.zero_status) {
-        hipError_t e = graph_ids ? hipSuccess : hipMemsetAsync(status, 0, sizeof(int32_t) * (size_t)n_graphs, st);
-        if (graph_ids) hipLaunchKernelGGL(status_zero_kernel, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st, graph_ids, (int)n_items, status);
+    if (p.memset_status) {
+        hipError_t e = rq.graph_ids ? hipSuccess : hipMemsetAsync(rq.status, 0, sizeof(int32_t) * (size_t)rq.n_graphs, st);
+        if (rq.graph_ids) hipLaunchKernelGGL(status_zero_kernel, dim3((unsigned)((rq.n_items + 255) / 256)), dim3(256), 0, st, rq.graph_ids, (int)rq.n_items, rq.status);
         if (e != hipSuccess) return set_error(GSN_E_HIP, "hipMemsetAsync(status): %s", hipGetErrorString(e));
     }
-    int items = pair ? (int)((n_graphs + 1) / 2) : (int)n_items * a.split;
-    a.n_items = items; a.lds_bytes = o;
-    if (a.side_mask) items = (items + SIDE_EVERY - 1) / SIDE_EVERY * (SIDE_EVERY + 1);      // every (SIDE_EVERY + 1)-th workgroup is a side workgroup
-    trace("gsn count: count_kernel<%d,%d> workgroups %d pair %d split %d lds %d\n", W, T, items, a.pair, a.split, o);
-    if (W == 1 && T == 64) return launch<1, 64>(a, items, (size_t)o, st);
-    if (W == 1) return launch<1, 256>(a, items, (size_t)o, st);
-    if (W == 2 && T == 64) return launch<2, 64>(a, items, (size_t)o, st);
-    if (W == 2) return launch<2, 256>(a, items, (size_t)o, st);
-    if (W == 4 && T == 64) return launch<4, 64>(a, items, (size_t)o, st);
-    if (W == 4) return launch<4, 256>(a, items, (size_t)o, st);
-    if (W == 8) return launch<8, 64>(a, items, (size_t)o, st);
-    return launch<12, 64>(a, items, (size_t)o, st);
+    trace("gsn count: count_kernel<%d,%d> workgroups %d pair %d split %d lds %d\n", p.W, p.T, p.grid, a.pair, a.split, p.lds_bytes);
+    if (p.W == 1 && p.T == 64 && a.off_ain < 0) {
+        const bool tail = a.any_tail != 0 || a.tail_loop != 0;
+        trace("gsn count: molecule instantiation %d cycle walk %d (tail %d mode %d sym %d cols %d pair %d split %d stage %d out %d enc %d enc_stage %d ids %d)\n", (int)count_molecule_route(a, sw),
+                    (int)(a.cyc_len != 0), (int)tail, a.mode, a.sym, a.n_cols, a.pair, a.split, a.stage_out, a.out != nullptr, a.enc_out != nullptr, a.enc_stage, a.graph_ids != nullptr);
+        if (a.cyc_len) trace("gsn count: cycle flags %s\n", p.kernel == CYCLE_KEYS ? "CycKeys" : "CycAny");
+    }
+    return dispatch(p, st);
+}
+
+// the identifier columns pack_col0 .. of a pack row: inside the row (the widths as far as the arguments can be read; the planner validates them)
+static int pack_columns_check(const char *entry, const CountRequest &rq) {
+    const int64_t pack_stride = rq.enc16_stride;
+    int64_t w = 0;
+    if (rq.n_classes && rq.plan_host && rq.plan_words >= PLAN_HEADER_WORDS) for (uint32_t c = 0; c < rq.plan_host[4] && c < GSN_ENC_MAX_COLS; ++c) w += rq.n_classes[c];
+    if (pack_stride <= 0 || pack_stride > 0x7fffffff || rq.enc16_col0 < 0 || rq.enc16_col0 + w > pack_stride)
+        return set_error(GSN_E_INVALID, "%s: columns %lld .. %lld outside a pack row of %lld", entry, (long long)rq.enc16_col0, (long long)(rq.enc16_col0 + w), (long long)pack_stride);
+    return GSN_OK;
 }
 
 extern "C" int gsn_count_hip(const uint32_t *plan_host, const uint32_t *plan_dev, int64_t plan_words, int64_t n_graphs,
@@ -1722,8 +1391,12 @@ extern "C" int gsn_count_hip(const uint32_t *plan_host, const uint32_t *plan_dev
                              int64_t edge_row_stride, int ids_are_global, const int32_t *graph_ids, int64_t n_items,
                              int64_t max_nodes, int64_t max_edges, int64_t *out, int32_t *status, void *stream) {
     if (!out) return set_error(GSN_E_INVALID, "gsn_count_hip: null pointer argument");
-    return count_launch(plan_host, plan_dev, plan_words, n_graphs, node_ptr, edge_ptr, edge_index, edge_row_stride, ids_are_global,
-                        graph_ids, n_items, max_nodes, max_edges, out, status, nullptr, 0, nullptr, stream);
+    CountRequest rq;
+    rq.plan_host = plan_host; rq.plan_dev = plan_dev; rq.plan_words = plan_words; rq.n_graphs = n_graphs; rq.node_ptr = node_ptr; rq.edge_ptr = edge_ptr;
+    rq.edge_index = edge_index; rq.edge_row_stride = edge_row_stride; rq.ids_are_global = ids_are_global; rq.max_nodes = max_nodes; rq.max_edges = max_edges;
+    rq.out = out; rq.status = status;
+    rq.graph_ids = graph_ids; rq.n_items = n_items;
+    return count_launch(rq, stream);
 }
 
 extern "C" int gsn_count_encode_hip(const uint32_t *plan_host, const uint32_t *plan_dev, int64_t plan_words, int64_t n_graphs,
@@ -1732,8 +1405,13 @@ extern "C" int gsn_count_encode_hip(const uint32_t *plan_host, const uint32_t *p
                                     int64_t max_nodes, int64_t max_edges, int64_t *out, int32_t *status,
                                     const int32_t *n_classes, int clamp, float *enc_out, void *stream) {
     if (!enc_out) return set_error(GSN_E_INVALID, "gsn_count_encode_hip: enc_out is null");
-    return count_launch(plan_host, plan_dev, plan_words, n_graphs, node_ptr, edge_ptr, edge_index, edge_row_stride, ids_are_global,
-                        graph_ids, n_items, max_nodes, max_edges, out, status, n_classes, clamp, enc_out, stream);
+    CountRequest rq;
+    rq.plan_host = plan_host; rq.plan_dev = plan_dev; rq.plan_words = plan_words; rq.n_graphs = n_graphs; rq.node_ptr = node_ptr; rq.edge_ptr = edge_ptr;
+    rq.edge_index = edge_index; rq.edge_row_stride = edge_row_stride; rq.ids_are_global = ids_are_global; rq.max_nodes = max_nodes; rq.max_edges = max_edges;
+    rq.out = out; rq.status = status;
+    rq.graph_ids = graph_ids; rq.n_items = n_items;
+    rq.n_classes = n_classes; rq.enc_clamp = clamp; rq.enc_out = enc_out;
+    return count_launch(rq, stream);
 }
 
 extern "C" int gsn_count_encode_pack16_hip(const uint32_t *plan_host, const uint32_t *plan_dev, int64_t plan_words, int64_t n_graphs,
@@ -1743,16 +1421,18 @@ extern "C" int gsn_count_encode_pack16_hip(const uint32_t *plan_host, const uint
                                            const int32_t *n_classes, int clamp, float *enc_out, uint16_t *pack, int64_t pack_stride,
                                            int64_t pack_col0, void *stream) {
     if (!pack) return set_error(GSN_E_INVALID, "gsn_count_encode_pack16_hip: pack is null");
+    CountRequest rq;
+    rq.plan_host = plan_host; rq.plan_dev = plan_dev; rq.plan_words = plan_words; rq.n_graphs = n_graphs; rq.node_ptr = node_ptr; rq.edge_ptr = edge_ptr;
+    rq.edge_index = edge_index; rq.edge_row_stride = edge_row_stride; rq.ids_are_global = ids_are_global; rq.max_nodes = max_nodes; rq.max_edges = max_edges;
+    rq.out = out; rq.status = status;
+    rq.graph_ids = graph_ids; rq.n_items = n_items;
     // enc_out == NULL (r05): the pack columns are the only form of the encoded rows -- the fp32 one-hot rows (48 bytes per row of four 3-class
     // columns) are not written at all; the kernel takes the same path with a placeholder address it never stores to
-    const int no32 = enc_out ? 0 : 1;
-    if (no32) enc_out = reinterpret_cast<float *>(pack);
-    int64_t w = 0;
-    if (n_classes && plan_host && plan_words >= PLAN_HEADER_WORDS) for (uint32_t c = 0; c < plan_host[4] && c < GSN_ENC_MAX_COLS; ++c) w += n_classes[c];
-    if (pack_stride <= 0 || pack_stride > 0x7fffffff || pack_col0 < 0 || pack_col0 + w > pack_stride)
-        return set_error(GSN_E_INVALID, "gsn_count_encode_pack16_hip: columns %lld .. %lld outside a pack row of %lld", (long long)pack_col0, (long long)(pack_col0 + w), (long long)pack_stride);
-    return count_launch(plan_host, plan_dev, plan_words, n_graphs, node_ptr, edge_ptr, edge_index, edge_row_stride, ids_are_global,
-                        graph_ids, n_items, max_nodes, max_edges, out, status, n_classes, clamp, enc_out, stream, pack, pack_stride, pack_col0, no32);
+    rq.enc_no32 = enc_out ? 0 : 1;
+    rq.n_classes = n_classes; rq.enc_clamp = clamp; rq.enc_out = enc_out ? enc_out : reinterpret_cast<float *>(pack);
+    rq.enc16 = pack; rq.enc16_stride = pack_stride; rq.enc16_col0 = pack_col0;
+    if (int rc = pack_columns_check("gsn_count_encode_pack16_hip", rq)) return rc;
+    return count_launch(rq, stream);
 }
 
 extern "C" int gsn_count_encode_pack16_side_hip(const uint32_t *plan_host, const uint32_t *plan_dev, int64_t plan_words, int64_t n_graphs,
@@ -1762,15 +1442,16 @@ extern "C" int gsn_count_encode_pack16_side_hip(const uint32_t *plan_host, const
                                                 int64_t pack_col0, const gsn_count_side *side, void *stream) {
     if (!side) return set_error(GSN_E_INVALID, "gsn_count_encode_pack16_side_hip: side is null");
     if (!out) return set_error(GSN_E_INVALID, "gsn_count_encode_pack16_side_hip: the int64 counts are always written (out is null)");
-    if (!pack)          // (no identifier pack: plain counts + the CSR / node pack; edge codes need the pack and are refused in count_launch)
-        return count_launch(plan_host, plan_dev, plan_words, n_graphs, node_ptr, edge_ptr, edge_index, edge_row_stride, ids_are_global, nullptr, n_graphs,
-                            max_nodes, max_edges, out, status, nullptr, 0, nullptr, stream, nullptr, 0, 0, 0, side);
-    int64_t w = 0;
-    if (n_classes && plan_host && plan_words >= PLAN_HEADER_WORDS) for (uint32_t c = 0; c < plan_host[4] && c < GSN_ENC_MAX_COLS; ++c) w += n_classes[c];
-    if (pack_stride <= 0 || pack_stride > 0x7fffffff || pack_col0 < 0 || pack_col0 + w > pack_stride)
-        return set_error(GSN_E_INVALID, "gsn_count_encode_pack16_side_hip: columns %lld .. %lld outside a pack row of %lld", (long long)pack_col0, (long long)(pack_col0 + w), (long long)pack_stride);
-    return count_launch(plan_host, plan_dev, plan_words, n_graphs, node_ptr, edge_ptr, edge_index, edge_row_stride, ids_are_global, nullptr, n_graphs,
-                        max_nodes, max_edges, out, status, n_classes, clamp, reinterpret_cast<float *>(pack), stream, pack, pack_stride, pack_col0, 1, side);
+    CountRequest rq;
+    rq.plan_host = plan_host; rq.plan_dev = plan_dev; rq.plan_words = plan_words; rq.n_graphs = n_graphs; rq.node_ptr = node_ptr; rq.edge_ptr = edge_ptr;
+    rq.edge_index = edge_index; rq.edge_row_stride = edge_row_stride; rq.ids_are_global = ids_are_global; rq.max_nodes = max_nodes; rq.max_edges = max_edges;
+    rq.out = out; rq.status = status;
+    rq.n_items = n_graphs; rq.side = side;
+    if (!pack) return count_launch(rq, stream);     // (no identifier pack: plain counts + the CSR / node pack; edge codes need the pack and are refused by the planner)
+    rq.n_classes = n_classes; rq.enc_clamp = clamp; rq.enc_out = reinterpret_cast<float *>(pack); rq.enc_no32 = 1;
+    rq.enc16 = pack; rq.enc16_stride = pack_stride; rq.enc16_col0 = pack_col0;
+    if (int rc = pack_columns_check("gsn_count_encode_pack16_side_hip", rq)) return rc;
+    return count_launch(rq, stream);
 }
 
 extern "C" int gsn_count_encode_keys_side_hip(const uint32_t *plan_host, const uint32_t *plan_dev, int64_t plan_words, int64_t n_graphs,
@@ -1780,7 +1461,13 @@ extern "C" int gsn_count_encode_keys_side_hip(const uint32_t *plan_host, const u
                                               const gsn_count_keys *keys, void *stream) {
     if (!side || !keys || !keys->idmask) return set_error(GSN_E_INVALID, "gsn_count_encode_keys_side_hip: side / keys / keys->idmask is null");
     if (!out) return set_error(GSN_E_INVALID, "gsn_count_encode_keys_side_hip: the int64 counts are always written (out is null)");
+    CountRequest rq;
+    rq.plan_host = plan_host; rq.plan_dev = plan_dev; rq.plan_words = plan_words; rq.n_graphs = n_graphs; rq.node_ptr = node_ptr; rq.edge_ptr = edge_ptr;
+    rq.edge_index = edge_index; rq.edge_row_stride = edge_row_stride; rq.ids_are_global = ids_are_global; rq.max_nodes = max_nodes; rq.max_edges = max_edges;
+    rq.out = out; rq.status = status;
+    rq.n_items = n_graphs; rq.side = side; rq.keys = keys;
     // (no fp32 rows and no pack: the identifier masks are the only form of the encoded rows; enc_out is a placeholder that is never written)
-    return count_launch(plan_host, plan_dev, plan_words, n_graphs, node_ptr, edge_ptr, edge_index, edge_row_stride, ids_are_global, nullptr, n_graphs,
-                        max_nodes, max_edges, out, status, n_classes, clamp, reinterpret_cast<float *>(keys->idmask), stream, nullptr, 16, pack_col0, 1, side, keys);
+    rq.n_classes = n_classes; rq.enc_clamp = clamp; rq.enc_out = reinterpret_cast<float *>(keys->idmask); rq.enc_no32 = 1;
+    rq.enc16_stride = 16; rq.enc16_col0 = pack_col0;
+    return count_launch(rq, stream);
 }
